@@ -1,8 +1,21 @@
 """Headline benchmark: MLUPS of the LBM stream-and-collide hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+Plain run and --full.  A plain run sets up, runs W warm-up steps, keeps the device busy for DEVICE_WARM_S (the same
+workload on a scratch flow, ``warm_device``), times exactly K steps (one K-step call between device synchronisations;
+--batches B makes it B such calls), writes --dump-outputs and prints the line: ``ms_per_step`` is the timed
+time / K.  What else is described below -- the repeated batches and their median, the
+N = 1 roofline (HIP events around the fused launches, the device's copy rate), the ``verified`` re-run,
+``other_configs`` and ``cpu_baseline`` -- runs only with --full; the N > 1 candidates run in both.
+
+--dump-outputs DIR.  After the timed steps, the populations the timed path leaves to its caller (``flow.f`` in
+lettuce's post-streaming convention; per rank ``local_f()`` on the slab path) are written as DIR/f.npy (DIR/f_rank<r>.npy
+with N > 1 ranks) in the run's dtype: the whole array when it has at most DUMP_VALUES elements, else the elements at
+DUMP_VALUES positions drawn with a fixed seed (the same positions for the same shape in every run), in ascending order.
+The inputs are analytic, so the same arguments give the same inputs in every run.
 
 Workload (BASELINE.json): TaylorGreenVortex3D, D3Q19, BGK, fp32, Re 1600, Ma 0.1, synthetic
 (analytic) initial condition incl. the f_neq initialisation.
@@ -21,7 +34,7 @@ own N ranks (a ``torch.distributed.run`` child process, before this process touc
 relays rank 0's JSON line and the exit code; fewer than N visible devices is an error, never a
 silent N = 1 run.  Under a launcher (WORLD_SIZE set) the process is one rank.
 
-Timing.  Five timed batches (barrier + device synchronise on both sides, max over ranks);
+Timing (--full).  Five timed batches (barrier + device synchronise on both sides, max over ranks);
 ``ms_per_step`` / ``value`` are those of the median batch, all five are listed in
 ``batches_ms_per_step``.  A batch is the K-step call repeated R times back to back, R chosen so that
 a batch lasts at least ~50 ms (R = 1 when K steps already do): with the driver's K = 20 a single call
@@ -80,7 +93,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6.3 TB/s copy ceiling
-MIN_BATCH_S = 0.05               # a timed batch lasts at least this long (the K-step call is repeated)
+MIN_BATCH_S = 0.05               # --full: a timed batch lasts at least this long (the K-step call is repeated)
+DEVICE_WARM_S = 0.2              # a plain run: device busy this long between the warm-up and the timed steps
+DUMP_VALUES = 1 << 23            # --dump-outputs: elements written at most (32 MB in fp32, 64 MB in fp64)
+DUMP_SEED = 1234                 # --dump-outputs: seed of the sample positions
 
 WORKLOADS = {
     # name: (flow, stencil, dtype, bytes per node and update, per-GPU block when --size 256)
@@ -92,20 +108,27 @@ WORKLOADS = {
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200,
+                    help="timed steps: a plain run times exactly this many (one call between device synchronisations)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--batches", type=int, default=5,
-                    help="timed batches; the median one is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: repeated timed batches and "
+                         "their median, roofline, the verified re-run, other_configs, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the populations the timed path computed as DIR/f.npy "
+                         "(a fixed, seeded sample of at most DUMP_VALUES elements; module docstring)")
+    ap.add_argument("--batches", type=int, default=None,
+                    help="timed batches, the median one is reported (default: 1 in a plain run, 5 with --full)")
     ap.add_argument("--size", type=int, default=256, help="nodes per side of the per-GPU block")
     ap.add_argument("--workload", choices=["cfg3", "cfg5"], default="cfg3",
                     help="slab path: cfg3 = TGV D3Q19 fp32, 512 x 512 x 64 per GPU (BASELINE configs[2] at N = 8); "
                          "cfg5 = shear layer D3Q19 fp64, 384 x 384 x 96 per GPU (configs[4] at N = 4)")
-    ap.add_argument("--cpu-baseline-steps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-baseline-steps", type=int, default=2, help="--full: oracle steps of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1: skip the cfg4 / cfg5-shape rows of the line (profiling passes)")
+                    help="--full, N = 1: skip the cfg4 / cfg5-shape rows of the line (profiling passes)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the untimed re-run with the one-step kernel (profiling passes)")
+                    help="--full: skip the untimed re-run with the one-step kernel (profiling passes)")
     ap.add_argument("--no-overlap", action="store_true", help="slab path: exchange without overlap")
     ap.add_argument("--transport", choices=["auto", "all", "rccl", "window", "copy"],
                     default=os.environ.get("LT_BENCH_TRANSPORT", "auto"),
@@ -213,6 +236,20 @@ def copy_ceiling(device, nbytes=1 << 30, iters=20):
     return best
 
 
+def warm_device(lt, ctx, n, seconds):
+    """A plain run, after the warm-up steps: the same workload on a scratch flow (at most 256^3; the timed flow is not
+    touched) until the device has been busy with it for ``seconds``.  After set-up and a few ms of warm-up steps the
+    device runs its first ~50 ms of lattice updates up to 10 % slower (idle before makes it worse; streaming copies
+    help less than the lattice kernel itself); --full gets there through the copy rate it measures, the call that
+    sizes the batches and the median of repeated batches."""
+    flow = lt.TaylorGreenVortex(ctx, [min(n, 256)] * 3, 1600, 0.1, lt.D3Q19())
+    sim = lt.Simulation(flow, lt.BGKCollision(flow.units.relaxation_parameter_lu), [])
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        sim(20)                                        # synchronises the device at its end
+    del sim, flow
+
+
 def source_hash():
     """Hash of the kernel sources the in-tree library is built from (lettuce_amd/csrc)."""
     import hashlib
@@ -282,6 +319,31 @@ def repeats_for(seconds_per_call):
     if seconds_per_call <= 0:
         return 1
     return max(1, min(1000, int(math.ceil(MIN_BATCH_S / seconds_per_call))))
+
+
+def timed_batches(args):
+    """timed batches of the run: --batches if given, else 5 with --full and 1 (exactly K timed steps) without"""
+    return max(1, args.batches if args.batches is not None else (5 if args.full else 1))
+
+
+def output_sample(f, limit=DUMP_VALUES):
+    """--dump-outputs: ``f`` as a host array, or the elements at ``limit`` positions drawn with DUMP_SEED (the same
+    positions for the same number of elements in every run), in ascending order, when it has more"""
+    import numpy as np
+    flat = f.detach().reshape(-1)
+    if flat.numel() > limit:
+        index = np.sort(np.random.RandomState(DUMP_SEED).randint(0, flat.numel(), size=limit, dtype=np.int64))
+        flat = flat[torch.from_numpy(index).to(flat.device)]
+    out = flat.cpu().numpy()
+    return out if out.dtype in (np.float32, np.float64) else out.astype(np.float64)
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: <directory>/<name>.npy for every host array of ``arrays``"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
 
 
 # ---- N = 1: the other BASELINE configurations -------------------------------------------------
@@ -411,6 +473,7 @@ def other_configs(lt, device):
 
 # ---- the held line of the N > 1 path ----------------------------------------------------------
 HANG_EXIT_CODE = 0
+WATCHDOG_RANK0_LEAD_S = 5.0      # the other ranks' watchdogs end their rank this long after rank 0's would
 
 
 class HeldLine:
@@ -462,6 +525,10 @@ class HeldLine:
             sys.stderr.write(f"bench.py: rank {self.rank}: a call of candidate {where} did not return within its budget: "
                              f"a GPU or RCCL call is stuck; the rank ends itself\n")
             sys.stderr.flush()
+            if self.rank != 0:
+                # every rank has (about) the same deadline, but each watchdog wakes once a second: a rank that ended
+                # first with a non-zero code would have the launcher stop rank 0 before rank 0's watchdog printed
+                time.sleep(WATCHDOG_RANK0_LEAD_S)
             if self.line is not None:
                 self.line["config"]["transport"]["aborted"] = f"{where}: no return within its budget; held line printed by the watchdog"
                 self.emit()
@@ -525,41 +592,49 @@ def single_gpu_bench(args, lt, device):
     kernel = sim._native.plan.kernel_name()
     resident, resident_stride = sim._native.plan.resident_enabled()
     sim(args.warmup)
-    # the plain copy rate of this device (roofline.copy_ceiling_GBps) is measured before the timed batches
-    ceiling = copy_ceiling(device)
-    # one more untimed K-step call sizes the batches
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    sim(args.steps)
-    torch.cuda.synchronize(device)
-    repeat = repeats_for(time.perf_counter() - t0)
-    pre_timed = None if args.no_verify else flow.f.clone()   # lettuce's convention: post-streaming
-    sim._native.fused_events = (start, end)
+    full, repeat, ceiling, pre_timed = args.full, 1, None, None
+    if full:
+        # the plain copy rate of this device (roofline.copy_ceiling_GBps) is measured before the timed batches
+        ceiling = copy_ceiling(device)
+        # one more untimed K-step call sizes the batches
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        sim(args.steps)
+        torch.cuda.synchronize(device)
+        repeat = repeats_for(time.perf_counter() - t0)
+        pre_timed = None if args.no_verify else flow.f.clone()   # lettuce's convention: post-streaming
+        sim._native.fused_events = (start, end)
+    else:
+        warm_device(lt, ctx, n, DEVICE_WARM_S)
 
     batch_s, batch_fused_ms, batch_info = [], [], []
-    for _ in range(max(1, args.batches)):
+    for _ in range(timed_batches(args)):
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
         for _ in range(repeat):
             sim(args.steps)
         torch.cuda.synchronize(device)
         batch_s.append((time.perf_counter() - t0) / repeat)      # seconds per K steps
-        if args.steps > 1:
+        if full and args.steps > 1:
             batch_info.append(sim._native.plan.last_run_info())
             batch_fused_ms.append(start.elapsed_time(end))       # the fused launches of the batch's last call
-    # lettuce's convention for flow.f is post-streaming; the engine keeps the populations post-collision between
-    # batches and streams when flow.f is read (Flow.f): that one pass, timed here, is what a caller pays per look
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    _ = flow.f
-    torch.cuda.synchronize(device)
-    present_ms = (time.perf_counter() - t0) * 1e3
+    present_ms = None
+    if full:
+        # lettuce's convention for flow.f is post-streaming; the engine keeps the populations post-collision between
+        # batches and streams when flow.f is read (Flow.f): that one pass, timed here, is what a caller pays per look
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        _ = flow.f
+        torch.cuda.synchronize(device)
+        present_ms = (time.perf_counter() - t0) * 1e3
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"f": output_sample(flow.f)})
     mid = median_index(batch_s)
     elapsed = batch_s[mid]
     mlups = args.steps * nodes / 1e6 / elapsed
 
     roofline, check = None, None
-    if args.steps > 1:
+    if full and args.steps > 1:
         # what the events bracketed: the two-step launches (two lattice updates per node each) when
         # lt_run paired its fused steps, else the single-step launches
         info = batch_info[mid]
@@ -635,23 +710,30 @@ def single_gpu_bench(args, lt, device):
         "timing": (f"median of {len(batch_s)} timed batches; a batch is the {args.steps}-step call repeated {repeat}x back "
                    f"to back between device synchronisations (>= {int(MIN_BATCH_S * 1e3)} ms per batch), every number is "
                    f"per {args.steps} steps; the device's plain copy rate (roofline.copy_ceiling_GBps) and one untimed "
-                   f"{args.steps}-step call that sizes the batches come between the warm-up steps and the timed batches"),
+                   f"{args.steps}-step call that sizes the batches come between the warm-up steps and the timed batches"
+                   if full else
+                   f"{len(batch_s)} timed batch(es) of one {args.steps}-step call between device synchronisations, after "
+                   f"the {args.warmup} warm-up steps and {DEVICE_WARM_S} s of the same workload on a scratch flow that "
+                   f"bring the device to its steady state; ms_per_step = the median batch's time / {args.steps}"),
         "repeats_per_batch": repeat,
         "roofline": roofline,
-        "presentation_pass_ms": round(present_ms, 4),
-        "ms_per_step_if_read_after_every_batch": round((elapsed * 1e3 + present_ms) / args.steps, 5),
+        "full": full,
     }
+    if present_ms is not None:
+        line["presentation_pass_ms"] = round(present_ms, 4)
+        line["ms_per_step_if_read_after_every_batch"] = round((elapsed * 1e3 + present_ms) / args.steps, 5)
     if check is not None:
         line.update(check)
     del sim, flow
     torch.cuda.empty_cache()
-    if not args.no_other_configs:
+    if full and not args.no_other_configs:
         try:
             line["other_configs"] = other_configs(lt, device)
         except Exception as exc:                       # the headline line must not depend on the extra rows
             line["other_configs"] = {"error": f"{type(exc).__name__}: {str(exc)[:200]}"}
         torch.cuda.empty_cache()
-    line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(n, args.cpu_baseline_steps)
+    line["cpu_baseline"] = (cpu_baseline(n, args.cpu_baseline_steps) if full and not args.no_cpu_baseline
+                            else None)
     print(json.dumps(line), flush=True)
 
 
@@ -771,10 +853,10 @@ def slab_bench(args, lt, dist, world, rank, local_rank, device):
 
     what = (f"{flow_name} {stencil_name} BGK {'fp32' if dtype == torch.float32 else 'fp64'} "
             f"{global_res[0]}x{global_res[1]}x{global_res[2]} ({nodes_per_rank} nodes per GPU)")
-    # the CPU baseline of the N = 1 line, measured on rank 0's host cores before the candidates while the other ranks
-    # wait in the first collective of the loop (same per-GPU node count; ~20 s)
+    # --full: the CPU baseline of the N = 1 line, measured on rank 0's host cores before the candidates while the other
+    # ranks wait in the first collective of the loop (same per-GPU node count; ~20 s)
     cpu_row = None
-    if rank == 0 and not args.no_cpu_baseline and args.workload == "cfg3":
+    if rank == 0 and args.full and not args.no_cpu_baseline and args.workload == "cfg3":
         cpu_row = cpu_baseline(256 if n == 256 else n, args.cpu_baseline_steps)
         cpu_row["sample"] += "; measured on rank 0 before the process group's first collective"
     traffic_key = {"cfg3": "slab_tgv3d_d3q19_bgk_f32_512x512x64", "cfg5": "slab_shear3d_d3q19_bgk_f64_384x384x96"}.get(args.workload)
@@ -812,6 +894,7 @@ def candidate_loop(args, ranks, wanted, build, what, global_res, nodes_per_rank,
     reference = {}                     # the first candidate's populations after the probe and after its timed batches
     probe_steps = max(args.warmup, 60) if probe_steps is None else probe_steps
     window_ok = None
+    held_output = None                 # --dump-outputs: this rank's sample of the held candidate's final populations
 
     def describe(driver, transport):
         how_copy = ("halo messages moved by device-to-device copies without compute units (copy engines) into receive "
@@ -866,7 +949,8 @@ def candidate_loop(args, ranks, wanted, build, what, global_res, nodes_per_rank,
             "batches_ms_per_step": [round(t / args.steps * 1e3, 5) for t in batch_s],
             "timing": (f"median of {len(batch_s)} timed batches (barrier + device synchronise on both sides, max over "
                        f"ranks); a batch is the {args.steps}-step call repeated {repeat}x back to back "
-                       f"(>= {int(MIN_BATCH_S * 1e3)} ms per batch), every number is per {args.steps} steps"),
+                       + (f"(>= {int(MIN_BATCH_S * 1e3)} ms per batch)" if args.full else "(no repeats: a plain run)")
+                       + f", every number is per {args.steps} steps"),
             "repeats_per_batch": repeat,
             "roofline": roofline,
             "verified": verified,
@@ -949,16 +1033,19 @@ def candidate_loop(args, ranks, wanted, build, what, global_res, nodes_per_rank,
             del state
             # ---- the timed region: W more warm-up steps, then `batches` times (R x) exactly K steps ----
             cand(args.warmup)
-            barrier()
-            t0 = time.perf_counter()
-            cand(args.steps)                    # sizes the batches (untimed)
-            barrier()
-            # later candidates repeat as often as the first one did: the same number of steps, so that the populations
-            # after the timed batches can be compared too
-            repeat = reference.get("repeat") or repeats_for(max_over_ranks(time.perf_counter() - t0))
+            repeat = 1                          # a plain run: exactly K steps per batch
+            if args.full:
+                barrier()
+                t0 = time.perf_counter()
+                cand(args.steps)                # sizes the batches (untimed)
+                barrier()
+                # later candidates repeat as often as the first one did: the same number of steps, so that the
+                # populations after the timed batches can be compared too
+                repeat = reference.get("repeat") or repeats_for(max_over_ranks(time.perf_counter() - t0))
             batch_s, err = [], None
-            for batch in range(max(1, args.batches)):
-                held.at(f"timed batch {batch + 1} of {max(1, args.batches)}")
+            batches = timed_batches(args)
+            for batch in range(batches):
+                held.at(f"timed batch {batch + 1} of {batches}")
                 barrier()
                 t0 = time.perf_counter()
                 try:
@@ -992,7 +1079,6 @@ def candidate_loop(args, ranks, wanted, build, what, global_res, nodes_per_rank,
                     continue
             # what every rank ended with, for the record: RCCL really saw `world` ranks, each with its own slab
             sums = ranks.gather(float(state.double().sum()))
-            del state
             kernel = cand.engine.kernel_name() if hasattr(cand.engine, "kernel_name") else type(cand.engine).__name__
             line = make_line(name, driver, transport, batch_s, repeat, kernel, verified)
             line["config"]["transport"]["rank_checksums"] = sums
@@ -1001,8 +1087,11 @@ def candidate_loop(args, ranks, wanted, build, what, global_res, nodes_per_rank,
                 line["config"]["transport"]["copy_streams"] = cand._cw.n_streams
             if held.line is None or line["value"] > held.line["value"]:
                 held.line = line
+                if args.dump_outputs:           # what this candidate's timed path left on this rank
+                    held_output = output_sample(state, DUMP_VALUES // world)
             else:
                 checks[name] = checks.get(name, "") + "; not faster than the held line"
+            del state
             cand = None
             ranks.release()
         except Exception as exc:                # anything unforeseen in a candidate must not cost the held line
@@ -1017,6 +1106,8 @@ def candidate_loop(args, ranks, wanted, build, what, global_res, nodes_per_rank,
         raise SystemExit(f"no usable slab configuration: {failures}")
     held.emit()
     reference.clear()
+    if held_output is not None:
+        write_outputs(args.dump_outputs, {"f" if world == 1 else f"f_rank{rank}": held_output})
 
 
 if __name__ == "__main__":

@@ -48,8 +48,10 @@ def main():
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.set_num_threads(1)
-    args = bench.parse(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--batches", "2",
-                        "--candidate-budget", "2", "--watchdog-grace", "2", "--first-candidate-budget", "20"])
+    # with a directory as second argument: a plain run (one batch of exactly K steps) that dumps its outputs there
+    mode = ["--dump-outputs", sys.argv[2]] if len(sys.argv) > 2 else ["--batches", "2", "--full"]
+    args = bench.parse(["--gpus", str(world), "--steps", "2", "--warmup", "1"] + mode +
+                       ["--candidate-budget", "2", "--watchdog-grace", "2", "--first-candidate-budget", "20"])
     if "first-never-returns" in stubs:
         args.first_candidate_budget = 2.0
     bench.MIN_BATCH_S = 0.0

@@ -13,8 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "bench_failsoft_worker.py")
 
 
-def _run(stubs, timeout=240):
-    code = ("import bench, sys; sys.exit(bench.launch_ranks(2, [%r], worker=%r, visible=2))" % (stubs, WORKER))
+def _run(stubs, timeout=240, dump_dir=None):
+    argv = [stubs] + ([str(dump_dir)] if dump_dir is not None else [])
+    code = ("import bench, sys; sys.exit(bench.launch_ranks(2, %r, worker=%r, visible=2))" % (argv, WORKER))
     env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=timeout)
@@ -86,3 +87,24 @@ def test_a_reference_candidate_that_never_returns_ends_in_a_line_that_says_so():
     t = line["config"]["transport"]
     assert t["ranks_seen"]["distinct_devices"] == 2
     assert t["chosen"] is None and "watchdog" in t["aborted"] and "single-step/never-returns" in t["aborted"]
+
+
+def test_a_plain_run_times_one_batch_of_k_steps_and_dumps_what_every_rank_computed(tmp_path):
+    """Without --full the loop times one batch of exactly K steps per candidate (no repeats, no sizing call);
+    --dump-outputs writes each rank's populations of the held candidate, the same in every run."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        r, lines = _run("rccl", dump_dir=tmp_path / f"run{run}")
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert len(line["batches_ms_per_step"]) == 1 and line["repeats_per_batch"] == 1
+        assert line["config"]["transport"]["failures"] == {}
+        dumps.append([np.load(tmp_path / f"run{run}" / f"f_rank{rank}.npy") for rank in range(2)])
+    for rank in range(2):
+        a, b = dumps[0][rank], dumps[1][rank]
+        assert a.dtype == np.float64 and a.size == 19 * 8 * 4 * 8 and np.isfinite(a).all()
+        assert np.array_equal(a, b)
+    assert abs(float(dumps[0][0].sum()) - 8 * 4 * 8) < 1e-9          # mass of a rank's slab (rho = 1 on average)

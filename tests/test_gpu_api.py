@@ -531,6 +531,33 @@ def test_bench_slab_path_on_one_gpu(tmp_path, transport):
     assert line["repeats_per_batch"] >= 1 and len(line["batches_ms_per_step"]) == 2
 
 
+def test_bench_plain_run_on_one_gpu(tmp_path):
+    """`bench.py` without --full: W warm-up steps, one timed call of exactly K steps and the headline fields, none of
+    the --full extras; --dump-outputs writes the populations the timed path left (whole here: 19 x 64^3 elements),
+    the same in two runs with the same arguments and equal to the CPU oracle after W + K steps."""
+    import json
+    import subprocess
+    import sys
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--steps", "10", "--warmup",
+                              "4", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 10 and line["warmup"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "MLUPS" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["full"] is False and len(line["batches_ms_per_step"]) == 1 and line["repeats_per_batch"] == 1
+        assert line["roofline"] is None and line["cpu_baseline"] is None and "other_configs" not in line
+        dumps.append(np.load(tmp_path / run / "f.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (19 * 64 ** 3,)
+    assert np.array_equal(dumps[0], dumps[1])
+    ref = orc.taylor_green([64] * 3, 1600, 0.1, "D3Q19", torch.float32)
+    ref.step(4 + 10)
+    want = ref.f.numpy().reshape(-1)
+    assert np.abs(dumps[0] - want).max() <= 1e-5 * np.abs(want).max()
+
+
 def test_non_native_mode_on_a_gpu_device():
     """Context('cuda', use_native=False): the reference's whole-field torch expressions on device
     tensors (per-node contractions evaluated without BLAS) still match the reference vectors."""

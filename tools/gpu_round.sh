@@ -6,6 +6,7 @@
 # under profiles/.  tools/pmc_traffic.py <tag> then turns gpurun_out/<tag>/ into profiles/.
 # Usage (on the GPU box, from the repo root): bash tools/gpu_round.sh <tag> [notests]
 set -o pipefail
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r04z}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -14,15 +15,15 @@ if [ "$2" != "notests" ]; then
 echo "== pytest -m gpu" && timeout -k 10 1200 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest exit $?" | tee -a $OUT/pytest_gpu.log; tail -3 $OUT/pytest_gpu.log
 echo "== smoke" && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log; tail -4 $OUT/smoke.log
 fi
-echo "== bench" && timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"; cut -c1-600 $OUT/bench.json
+echo "== bench" && timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"; cut -c1-600 $OUT/bench.json
 timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2>> $OUT/bench.err; echo "bench (driver flags) exit $?"
-echo "== slab rehearsal" && timeout -k 10 400 python bench.py --slab > $OUT/slab_self_exchange.json 2> $OUT/slab.err; echo "slab exit $?"; cut -c1-400 $OUT/slab_self_exchange.json
+echo "== slab rehearsal" && timeout -k 10 400 python bench.py --slab --full > $OUT/slab_self_exchange.json 2> $OUT/slab.err; echo "slab exit $?"; cut -c1-400 $OUT/slab_self_exchange.json
 timeout -k 10 300 python bench.py --slab --steps 20 --warmup 5 --no-cpu-baseline > $OUT/slab_self_exchange_driver_flags.json 2>> $OUT/slab.err; echo "slab (driver flags) exit $?"
-timeout -k 10 300 python bench.py --slab --workload cfg5 --no-cpu-baseline > $OUT/slab_self_exchange_cfg5.json 2>> $OUT/slab.err; echo "slab cfg5 exit $?"
+timeout -k 10 300 python bench.py --slab --workload cfg5 --no-cpu-baseline --full > $OUT/slab_self_exchange_cfg5.json 2>> $OUT/slab.err; echo "slab cfg5 exit $?"
 export TMPDIR=/tmp
 cd /tmp
 echo "== rocprofv3 kernel trace of the judged command"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py > $OUT/trace_bench.json 2> $OUT/trace.err; echo "trace exit $?"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full > $OUT/trace_bench.json 2> $OUT/trace.err; echo "trace exit $?"
 echo "== rocprofv3 kernel trace of the slab rehearsal"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_slab -- python3 $GRAFT_REPO_ROOT/bench.py --slab --steps 100 --batches 3 --driver two-step --no-cpu-baseline > $OUT/trace_slab_bench.json 2> $OUT/trace_slab.err; echo "slab trace exit $?"
 python3 $GRAFT_REPO_ROOT/tools/slab_timeline.py $OUT/trace_slab $OUT/slab_timeline.json > /dev/null; echo "timeline exit $?"
