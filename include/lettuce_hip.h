@@ -105,8 +105,7 @@ typedef struct lt_plan_desc {
 typedef struct lt_plan lt_plan;
 
 int lt_abi_version(void);
-/* bit 0: the library was built with the experiment kernels (make EXPERIMENTS=1; the entry points under
- * LT_EXPERIMENTS below) */
+/* 0.  (Bit 0 once meant a build with the kernels that lost their A/B; that build no longer exists.) */
 int lt_build_flags(void);
 const char *lt_last_error(void);
 
@@ -336,13 +335,10 @@ int lt_plan_kernel_info(lt_plan *plan, int32_t *vec_width, int32_t *threads_per_
                         int64_t *blocks_per_launch);
 /* Name of the fused kernel variant this plan launches (for matching rocprof rows). */
 const char *lt_plan_kernel_name(lt_plan *plan);
-/* A/B selector.  16-byte variant of the one-step kernel: 0 = aligned vector load + one neighbour
- * element, 1 = unaligned vector load, 2 = aligned vector load + cross-lane shift.  Two-step kernel
- * (D3Q19 / D3Q15 fp32, BGK, reference layout): 0 = product variant, 1 = two nodes per thread in both
- * phases, 2 = two output nodes per thread, 3 = no XCD-aware renumbering of the workgroups, 4 = the round-1
- * renumbering (an eighth of the grid per XCD instead of an eighth of every segment layer), 5 = 32 x 8 tiles for
- * the slab edge launch (two workgroups per CU; measured slower: 99 against 77 us).  1, 2 and 5 are tile variants
- * that lost their A/B: they exist in the experiments build only (LT_ERR_UNSUPPORTED otherwise). */
+/* A/B selector of the two-step kernel's workgroup order: 0 = product variant, 3 = no XCD-aware renumbering of the
+ * workgroups, 4 = the round-1 renumbering (an eighth of the grid per XCD instead of an eighth of every segment
+ * layer).  1, 2 and 5 named tile variants that lost their A/B and were removed (two nodes per thread in both phases,
+ * two output nodes per thread, 32 x 8 tiles for the slab edge launch): LT_ERR_UNSUPPORTED. */
 int lt_plan_set_shift_policy(lt_plan *plan, int32_t policy);
 /* out[i] = x[i] / D as the kernels' equilibrium forms it (div_cs: two or three instructions that return the IEEE
  * quotient by the constant D = 2 cs^2 (which 0) or cs^2 (which 1) rounded to dtype, the reference's divisors:
@@ -361,19 +357,9 @@ int lt_plan_set_graph_mode(lt_plan *plan, int32_t mode);
 /* Tuning knobs.  cache_policy: -1 = automatic (nontemporal accesses when the populations exceed
  * the caches), else bit 0 = nontemporal loads, bit 1 = nontemporal stores (the one-node-per-
  * thread kernels exist for 0 and 3).
- * wide != 0 switches the hot kernel (fused, BGK, no masks) to its 16-byte-per-lane A/B variant,
- * whose shift handling lt_plan_set_shift_policy selects. */
+ * wide != 0 asked for the 16-byte-per-lane variant of the hot kernel, which lost its A/B (8-13 % slower) and
+ * was removed: LT_ERR_UNSUPPORTED. */
 int lt_plan_set_tuning(lt_plan *plan, int32_t cache_policy, int32_t wide);
-#ifdef LT_EXPERIMENTS
-/* (experiments build only: 20 % slower per update than two updates per launch)
- * THREE fused stream-collide steps in one launch (lbm3_kernel): out = (C S)^3 f with both intermediate states in
- * LDS -- one HBM read and one write of the populations per three lattice updates.  Periodic 3-D plans without
- * boundaries in the reference layout whose grid tiles (contiguous extent % 64 (fp32) / 32 (fp64), middle extent % 4);
- * LT_ERR_UNSUPPORTED otherwise.  Bit-identical to three lt_stream_collide calls.  Same contract as the reference's
- * native step applied three times (lettuce/cuda_native/_template.py:58-86). */
-int lt_stream_collide_thrice(lt_plan *plan, const void *f_dev, void *out_dev, double tau, void *stream);
-#endif
-
 /* Two fused steps in one launch: out = (C S)^2 f for the whole periodic grid, the intermediate
  * state staged through LDS (one HBM read and one write of the populations per two lattice updates).
  * Bit-identical to two lt_stream_collide calls.  Exists with BGK / no collision for the 3-D lattices
@@ -390,10 +376,8 @@ int lt_stream_collide_twice(lt_plan *plan, const void *f_dev, void *out_dev, dou
  * redundant arithmetic but replaces n_steps launches; bit-identical to n_steps lt_stream_collide
  * calls.  2-D lattices, extents multiples of 8; plans with masks too (bounce-back, equilibrium and at most
  * one anti-bounce-back outlet, for which one more ring of nodes is recomputed: n_steps <= 7);
- * LT_ERR_UNSUPPORTED otherwise.
- * Small 3-D grids: n_steps = 2 exactly (the 10^3 neighbourhood of an 8^3 tile in LDS): periodic plans in the
- * reference layout without masks, extents multiples of 8, BGK / no collision, every 3-D lattice and dtype whose
- * q x 1000 values fit the LDS (not D3Q27 fp64); bit-identical to two lt_stream_collide calls.
+ * LT_ERR_UNSUPPORTED otherwise, 3-D plans included (a two-step 3-D variant measured slower than two launches and
+ * was removed).
  * lt_plan_set_many_step: lt_run / lt_continue use it for their fused steps: -1 = automatic (2-D grids up
  * to 256 x 256 nodes, with masks up to 256 x 128; BGK / no collision, where it is bit-identical to the one-step
  * kernel; never for 3-D grids, where two steps per launch measured slower than two launches), 0 = never,
@@ -447,20 +431,6 @@ int lt_plan_last_run_info(lt_plan *plan, int64_t *single_step_launches, int64_t 
  * them): -1 = automatic (3, or 4 for fp32 KBC, once the populations stream from HBM and the launch
  * fills the chip several times over; no cap otherwise), 0 = no cap, 2..8 = that many. */
 int lt_plan_set_residency(lt_plan *plan, int32_t workgroups_per_cu);
-#ifdef LT_EXPERIMENTS
-/* (experiments build only: 4-7 % faster than the exact arithmetic where <= 0.45 ms per launch had been the bar, and
- * 1.0-1.5e-6 off the reference's fp32 kinetic energy after 10 steps where SURVEY 8(d) states 1e-6 -- DESIGN.md section 4)
- * Arithmetic of the BGK collision.  0 (default) = the reference's, operation for operation: every rounding of
- * lettuce's whole-field torch operators is reproduced (ATen's summation order, u = j / rho by IEEE division, the
- * division by the rounded constants 2 cs^2 and cs^2, no fused multiply-adds; lettuce/_flow.py:136-172,
- * ext/_equilibrium/quadratic_equilibrium.py:11-25, ext/_collision/bgk_collision.py:17-22), so periodic BGK flows are
- * bit-identical to the reference's CPU path.  1 = fast: the same collision to rounding level in about half the
- * instructions (moments over opposite pairs, one reciprocal of rho, cs^2 = 1/3, contracted multiply-adds), inside
- * the tolerances SURVEY.md 8(d) states (fp32: max |df| <= 1e-5 max |f| after 10 steps, kinetic energy 1e-6 / 5e-5
- * over 10 / 100 steps) but NOT bit-identical to the reference; exists for BGK on periodic 3-D plans without
- * boundaries in the reference layout, never chosen by the engine itself. */
-int lt_plan_set_arithmetic(lt_plan *plan, int32_t mode);
-#endif
 /* First-use check of the two-step kernels of a plan WITH masks.  Before such a plan uses a two-step kernel for the
  * first time (lt_run's pairs, lt_resident_advance, every lt_stream_collide_twice* entry point,
  * lt_plan_two_step_admitted), one double step over all its planes is held against two one-step launches: synthetic

@@ -138,12 +138,6 @@ SYMBOLS = {
     "lt_plan_canary_status": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_char_p)]),
 }
 
-# entry points of the experiments build (make -C lettuce_amd/csrc EXPERIMENTS=1): bound when the library has them
-EXPERIMENT_SYMBOLS = {
-    "lt_stream_collide_thrice": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
-    "lt_plan_set_arithmetic": (ctypes.c_int, [_vp, _i32]),
-}
-
 _LIB = None
 
 
@@ -177,10 +171,6 @@ def load_library() -> ctypes.CDLL:
             raise NativeEngineError(f"{path} does not export {name}") from exc
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.lt_build_flags() & 1:
-        for name, (restype, argtypes) in EXPERIMENT_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
     if lib.lt_abi_version() != LT_ABI_VERSION:
         raise NativeEngineError(f"ABI mismatch: library {lib.lt_abi_version()}, "
                                 f"binding {LT_ABI_VERSION}")
@@ -189,8 +179,8 @@ def load_library() -> ctypes.CDLL:
 
 
 def experiments_built() -> bool:
-    """was the library built with the kernels that lost their A/B (make EXPERIMENTS=1)?"""
-    return bool(load_library().lt_build_flags() & 1)
+    """the build with the kernels that lost their A/B no longer exists"""
+    return False
 
 
 def _stream_handle() -> int:
@@ -732,17 +722,6 @@ class Plan:
         self._check(self.lib.lt_plan_set_two_step(self._handle, int(mode), int(planes_per_workgroup)))
 
     @_on_device
-    def stream_collide_thrice(self, f, out, tau):
-        """out = (collide o stream)^3 f in one launch (both intermediate states in LDS; lbm3_kernel)"""
-        self._tensor_ok(f, self.f_shape); self._tensor_ok(out, self.f_shape)
-        if not experiments_built():
-            raise NativeEngineError("three steps per launch: a kernel of the experiments build "
-                                    "(make -C lettuce_amd/csrc EXPERIMENTS=1)")
-        self._check(self.lib.lt_stream_collide_thrice(self._handle, _ptr(f), _ptr(out), float(tau),
-                                                      _stream_handle()))
-        return out
-
-    @_on_device
     def stream_collide_twice(self, f, out, tau):
         """out = (collide o stream)^2 f in one launch (LDS-staged intermediate state)"""
         self._tensor_ok(f, self.f_shape); self._tensor_ok(out, self.f_shape)
@@ -825,17 +804,6 @@ class Plan:
     def unpack_two_step(self, f, side, buf):
         self._populations_ok(f); self._message_ok(buf, self.two_step_message_blocks())
         self._check(self.lib.lt_slab_unpack_two_step(self._handle, _ptr(f), int(side), _ptr(buf), _stream_handle()))
-
-    def set_arithmetic(self, mode):
-        """"exact" / 0: the reference's arithmetic operation for operation (bit-identical periodic BGK flows);
-        "fast" / 1: the same collision to rounding level in half the instructions (BGK, periodic 3-D plans)"""
-        mode = {"exact": 0, "fast": 1}.get(mode, mode)
-        if not experiments_built():
-            if int(mode) == 0:
-                return
-            raise NativeEngineError("fast arithmetic: a kernel of the experiments build (make -C lettuce_amd/csrc "
-                                    "EXPERIMENTS=1): it missed its bar (DESIGN.md section 4)")
-        self._check(self.lib.lt_plan_set_arithmetic(self._handle, int(mode)))
 
     def set_canary(self, mode: int = 1):
         """first-use check of the masked two-step kernels: 1 = on (default), 0 = trust the kernel, 2 = report a

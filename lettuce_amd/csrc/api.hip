@@ -126,8 +126,7 @@ struct lt_plan {
   int n0, n1, n2;            // memory extents incl. ghost planes
   int interior_begin, interior_end;   // a2 planes that are real nodes
   long long N;               // n0*n1*n2
-  int wide_ok;               // n0 divisible by the 16-byte vector width
-  int shift;
+  int shift;                 // lt_plan_set_shift_policy: workgroup order of the two-step kernel (A/B)
   int tune = -1;             // cache policy: -1 = automatic
   int residency = -1;        // workgroups per CU of the big launches: -1 = automatic, 0 = no cap
   int n_cu = 0;              // compute units of the plan's device
@@ -138,7 +137,6 @@ struct lt_plan {
   long long second_begin = 0, second_end = 0;   // second plane range of the kFusedTwice launch being issued
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // lt_plan_set_fused_events
   long long last_single = 0, last_twice = 0, last_many = 0;   // fused launches of the last lt_run
-  int want_wide = 0;         // 16-byte accesses for the hot kernel (A/B experiments)
   // engine-owned device scratch
   unsigned char *node = nullptr;
   unsigned *nsm_bits = nullptr;
@@ -157,7 +155,6 @@ struct lt_plan {
   unsigned *signal_timed_out = nullptr;
   unsigned long long *signal_now = nullptr;   // where step() finds the counter for the launch being issued (or null)
   const void *ghost_lo_now = nullptr, *ghost_hi_now = nullptr;   // received halo messages the edge launch being issued reads
-  int arith = 0;             // 0 = the reference's arithmetic, operation for operation; 1 = fast (lt_plan_set_arithmetic)
   int defer_stream = 0;      // lt_run / lt_continue stop before their last (streaming) pass (lt_plan_set_deferred_stream)
   // distance between consecutive populations of the caller's buffers, in elements (lt_plan_set_population_stride);
   // 0 = dense (N).  stride_in_now / stride_out_now: what step() uses for the launch being issued when the two
@@ -185,18 +182,13 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau; int masked, tune, wide, shift, residency; } gkey = {};
+  struct { void *a, *b; double tau; int masked, tune, shift, residency; } gkey = {};
 };
 
 namespace {
 
 // elements between consecutive populations of the caller's buffers
 long long pop_stride_of(const lt_plan *p) { return p->pop_stride > 0 ? p->pop_stride : p->N; }
-
-// the collision the kernels are asked for: the plan's, or 3 = BGK in fast arithmetic (lt_plan_set_arithmetic)
-int coll_of(const lt_plan *p) {
-  return (p->arith == 1 && p->desc.collision == LT_COLLISION_BGK) ? 3 : p->desc.collision;
-}
 
 int mem_axis_of(const lt_plan *p, int logical_axis) {
   if (p->unit.d == 1) return 0;
@@ -313,8 +305,7 @@ int pack(lt_plan *p, bool do_pack, void *f, long long plane, int dir, void *buf,
   return LT_OK;
 }
 
-int resolve_tune(const lt_plan *p, int wide) {
-  if (wide) return p->tune < 0 ? 0 : p->tune;
+int resolve_tune(const lt_plan *p) {
   if (p->tune == 0 || p->tune == 3) return p->tune;
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
   return bytes > (128ll << 20) ? 3 : 0;
@@ -394,7 +385,7 @@ TwoStepTile two_step_tile_of(int d, int q, int esize, int n0, bool masked = fals
     // the 160 KB, 4 rows are used (D3Q19 fp64: 168.6 KB -> 32 x 4 tiles, 101 KB); unit.inc applies the same rule
     const int in_plane = q == 15 ? 5 : 9, crossing = (q - in_plane) / 2;
     const long long lds8 = (long long)esize * ((width + 2) * 10 * (4 * crossing + 3 * in_plane + 3 * crossing) + 2 * q);
-    if (lds8 > 160 * 1024) rows = LT_EXPERIMENTS ? 4 : 0;   // (product build: no masked two-step kernel there; it lost its A/B)
+    if (lds8 > 160 * 1024) rows = 0;   // (no masked two-step kernel there: 4-row tiles lost their A/B)
   }
   return {width, rows};
 }
@@ -443,24 +434,6 @@ int resolve_seg_len(const lt_plan *p, int planes) {
     const long long rounds = (blocks + cus - 1) / cus;
     const double score = ((double)planes / (double)(planes + 2 * segs)) *
                          ((double)blocks / (double)(rounds * cus));
-    if (score > best_score) { best_score = score; best = len; }
-  }
-  return best;
-}
-
-// planes per workgroup of the three-step kernel (lbm3_kernel: tiles of 64 / 32 x 4 nodes, one workgroup per CU, a
-// segment of L planes computes L + 4 level-1 and L + 2 level-2 planes)
-int resolve_seg_len3(const lt_plan *p, int planes) {
-  const int width = 256 / p->esize;
-  const long long tiles = (long long)(p->n0 / width) * (p->n1 / 4);
-  const long long cus = p->n_cu > 0 ? p->n_cu : 256;
-  int best = 1;
-  double best_score = -1.0;
-  for (int len = 1; len <= planes; ++len) {
-    if (planes % len) continue;
-    const long long blocks = tiles * (planes / len);
-    const long long rounds = (blocks + cus - 1) / cus;
-    const double score = ((double)len / (double)(len + 3)) * ((double)blocks / (double)(rounds * cus));
     if (score > best_score) { best_score = score; best = len; }
   }
   return best;
@@ -578,7 +551,7 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   a.wrap2 = p->desc.ghost_planes ? 0 : 1;
   a.tau = tau > 0.0 ? tau : 1.0;
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
-  a.layout = p->desc.layout; a.coll = coll_of(p); a.mode = mode;
+  a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = mode;
   a.masked = p->masked;
   a.abb_depth = p->abb_depth;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
@@ -590,17 +563,11 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
       if (b.kind == LT_BOUNDARY_ABB_OUTLET && !(b.flags & LT_BOUNDARY_ABSENT) && mem_axis_of(p, b.axis) == 0)
         a.abb0_slot = i + 1;
     }
-  const bool aligned = ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                       (p->pop_stride * p->esize) % 16 == 0 && p->stride_in_now < 0 && p->stride_out_now < 0;
-  const bool hot = mode == lt::kFused && !a.masked && a.coll == LT_COLLISION_BGK;
-  a.wide = (p->want_wide && hot && p->wide_ok && aligned) ? 1 : 0;
-  a.shift = a.wide ? p->shift : 0;
-  a.tune = resolve_tune(p, a.wide);
+  a.tune = resolve_tune(p);
   a.lds_bytes = resolve_lds(p, ((long long)a.planes * a.n1 * a.n0 + 255) / 256);
   a.seg_len = mode == lt::kFusedTwice ? resolve_seg_len(p, p->unit.d == 2 ? p->n1 : a.planes) : 0;
   a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
-  if (mode == lt::kFusedTwice) a.shift = p->shift;      // tile-shape A/B variant
-  if (mode == lt::kFusedThrice) a.seg_len = p->seg_len > 0 && a.planes % p->seg_len == 0 ? p->seg_len : resolve_seg_len3(p, a.planes);
+  if (mode == lt::kFusedTwice) a.shift = p->shift;      // workgroup-order A/B variant
   if (mode == lt::kFusedMany) a.seg_len = p->many_now;
   a.stream = static_cast<hipStream_t>(stream);
   a.stride_in = p->stride_in_now >= 0 ? p->stride_in_now : p->pop_stride;
@@ -646,7 +613,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
   }
   const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau &&
                     p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
-                    p->gkey.wide == p->want_wide && p->gkey.shift == p->shift;
+                    p->gkey.shift == p->shift;
   if (!same) {
     if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
     hipGraph_t graph = nullptr;
@@ -664,7 +631,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->masked, p->tune, p->want_wide, p->shift, p->residency};
+    p->gkey = {cur, other, tau, p->masked, p->tune, p->shift, p->residency};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -708,7 +675,7 @@ bool two_step_possible(lt_plan *p, const char **why) {
   }
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = coll_of(p); a.mode = lt::kFusedTwice;
+  a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = lt::kFusedTwice;
   a.masked = p->masked;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? tile.width : 0;
@@ -734,10 +701,6 @@ bool two_step_wanted(lt_plan *p) {
   // its multiply-adds differently in the two inlining contexts): never automatic, so that the result of n steps
   // does not depend on how the caller splits them into batches
   if (p->desc.collision == LT_COLLISION_KBC) return false;
-  // fp64 plans with boundaries whose tile has only 4 rows (D3Q19: the third downward slot does not fit beside 8) are
-  // slower than one update per launch: Obstacle D3Q19 256^3 fp64 1.009 against 0.880 ms per update
-  // (tools/fp64_masked_two_step_probe.py; 4 waves per workgroup, 1.6 x redundant first step) -- opt-in only
-  if (p->masked && p->esize == 8 && p->unit.d == 3 && two_step_tile(p).rows == 4) return false;
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
   return bytes > (128ll << 20);
 }
@@ -854,23 +817,27 @@ bool canary_ok(lt_plan *p) {
 }
 
 constexpr int kManyMax = 8;        // == kManyMax of unit.inc
-// steps per many-step launch: a plan with an outlet recomputes one more ring of nodes around each tile; the 3-D
-// kernel does two (its neighbourhood of an 8^3 tile is 10^3 nodes: q x 1000 values of LDS)
+// steps per many-step launch: a plan with an outlet recomputes one more ring of nodes around each tile.  3-D plans
+// have no many-step kernel (lt_stream_collide_many: LT_ERR_UNSUPPORTED); their range stays the removed kernel's two
 int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->masked && p->n_abb > 0) ? 1 : 0); }
 
 // Several steps per launch (lbm_many_kernel): 2-D, tiles of 8 x 8, with masks at most one outlet.  Every
 // workgroup recomputes a halo of K - 1 nodes around its tile (K with an outlet), so this only pays while the
 // grid is launch-bound; "automatic" stops at 256 x 256 nodes, 256 x 128 with masks (measured,
 // tools/small_grid_bench.py, tools/small_masked_bench.py).
+// 3-D: none.  A kernel with two steps per launch for small 3-D grids (removed) measured slower than one
+// launch per step on every grid (tools/small_grid_bench.py, D3Q19 fp32, us per step: 16^3 3.66 -> 4.29, 32^3 4.21 ->
+// 5.79, 48^3 6.5 -> 7.9, 64^3 8.3 -> 15.4): two steps amortise one launch gap (~2 us) but the launch is a chain of two
+// dependent gather -> collide phases with a barrier in between, on 1000-thread workgroups that gather 10-node rows; the
+// 2-D kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
+// 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
-  if (p->many == 0 || p->desc.ghost_planes || p->unit.d < 2 || p->arith != 0) return false;
-  if (p->unit.d == 3 && !LT_EXPERIMENTS) return false;       // lbm_many3d_kernel: slower than two launches on every grid
-  if (p->masked && (p->n_abb > 1 || p->unit.d == 3)) return false;
-  if (p->n0 % 8 != 0 || p->n1 % 8 != 0 || (p->unit.d == 3 && p->n2 % 8 != 0)) return false;
-  if (p->unit.d == 3 && p->desc.layout != LT_LAYOUT_REFERENCE) return false;
+  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2) return false;
+  if (p->masked && p->n_abb > 1) return false;
+  if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = coll_of(p); a.mode = lt::kFusedMany;
+  a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = lt::kFusedMany;
   a.masked = p->masked;
   if (!p->unit.name(a)) return false;
   if (p->many == 1) return true;
@@ -882,13 +849,6 @@ bool many_step_wanted(lt_plan *p) {
   // recomputes a wider ring: 128 x 64 nodes 4.2 -> 2.4 us per step, 128 x 128 4.3 -> 2.5, 256 x 128 4.5 -> 3.3,
   // 256 x 256 5.6 -> 5.7 (tools/small_masked_bench.py, fp64)
   if (p->masked) return p->N <= 256ll * 128ll;
-  // 3-D (lbm_many3d_kernel, two steps per launch): never automatic.  Measured slower than one launch per step on
-  // every grid (tools/small_grid_bench.py, D3Q19 fp32, us per step: 16^3 3.66 -> 4.29, 32^3 4.21 -> 5.79, 48^3 6.5 ->
-  // 7.9, 64^3 8.3 -> 15.4): two steps amortise one launch gap (~2 us) but the launch is a chain of two dependent
-  // gather -> collide phases with a barrier in between, on 1000-thread workgroups that gather 10-node rows; the 2-D
-  // kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
-  // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
-  if (p->unit.d == 3) return false;
   return p->N <= 256ll * 256ll;
 }
 
@@ -907,21 +867,18 @@ int fused_section(lt_plan *p, void *&cur, void *&other, double tau, long long fu
   p->last_many = 0;
   if (many_step_wanted(p) && fused >= 2) {
     // launches of up to kManyMax steps each; the events bracket them
-    long long odd = 0;
     if (p->ev_start) (void)hipEventRecord(p->ev_start, hs);
     while (fused > 0) {
       p->many_now = fused < many_max(p) ? (int)fused : many_max(p);
-      // the 3-D kernel does exactly two steps: an odd one at the end is an ordinary launch
-      const int mode = (p->unit.d == 3 && p->many_now == 1) ? lt::kFused : lt::kFusedMany;
-      rc = step(p, mode, cur, other, tau, 0, p->n2, stream);
+      rc = step(p, lt::kFusedMany, cur, other, tau, 0, p->n2, stream);
       if (rc) return rc;
       void *t = cur; cur = other; other = t;
       fused -= p->many_now;
-      if (mode == lt::kFusedMany) ++p->last_many; else ++odd;
+      ++p->last_many;
     }
     if (p->ev_stop) (void)hipEventRecord(p->ev_stop, hs);
     p->last_twice = 0;
-    p->last_single = odd;
+    p->last_single = 0;
     return LT_OK;
   }
   const long long twice = two_step_wanted(p) ? fused / 2 : 0;
@@ -1006,7 +963,7 @@ int aux(lt_plan *p, int what, const void *f, void *rho, void *u, double *out, vo
 extern "C" {
 
 int lt_abi_version(void) { return LT_ABI_VERSION; }
-int lt_build_flags(void) { return LT_EXPERIMENTS ? 1 : 0; }
+int lt_build_flags(void) { return 0; }
 const char *lt_last_error(void) { return g_error; }
 
 int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
@@ -1050,7 +1007,6 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   p->N = e0 * e1 * e2;
   p->interior_begin = d->ghost_planes;
   p->interior_end = p->n2 - d->ghost_planes;
-  p->wide_ok = (e0 % (16 / p->esize)) == 0;
   p->shift = 0;
   {
     int dev = 0, cus = 0;
@@ -1298,12 +1254,11 @@ int lt_slab_mass_interior(lt_plan *p, const void *f, const uint8_t *mask, int32_
 
 int lt_plan_kernel_info(lt_plan *p, int32_t *vec, int32_t *tpb, int64_t *blocks) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
-  const int v = (p->want_wide && p->wide_ok) ? 16 / p->esize : 1;
-  if (vec) *vec = v;
+  if (vec) *vec = 1;
   if (tpb) *tpb = lt::kThreads;
   if (blocks) {
     const long long nodes = (long long)p->n0 * p->n1 * (p->interior_end - p->interior_begin);
-    *blocks = (nodes / v + lt::kThreads - 1) / lt::kThreads;
+    *blocks = (nodes + lt::kThreads - 1) / lt::kThreads;
   }
   return LT_OK;
 }
@@ -1312,7 +1267,7 @@ const char *lt_plan_kernel_name(lt_plan *p) {
   if (!p) return "";
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = coll_of(p);
+  a.layout = p->desc.layout; a.coll = p->desc.collision;
   // what the fused section launches: lt_run's pairs, or a two-step slab driver on a plan with two
   // ghost planes
   a.mode = (two_step_wanted(p) || p->desc.ghost_planes == 2) ? lt::kFusedTwice : lt::kFused;
@@ -1322,9 +1277,7 @@ const char *lt_plan_kernel_name(lt_plan *p) {
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
   if (a.mode == lt::kFusedTwice && !p->unit.name(a)) a.mode = lt::kFused;
-  a.wide = (p->want_wide && p->wide_ok && !a.masked && a.coll == LT_COLLISION_BGK) ? 1 : 0;
-  a.shift = a.wide ? p->shift : 0;
-  a.tune = resolve_tune(p, a.wide);
+  a.tune = resolve_tune(p);
   const char *n = p->unit.name(a);
   snprintf(p->kernel_name, sizeof p->kernel_name, "%s", n ? n : "");
   return p->kernel_name;
@@ -1381,8 +1334,8 @@ int lt_probe_div_cs(const void *x, void *out, int64_t n, int32_t dtype, int32_t 
 int lt_plan_set_shift_policy(lt_plan *p, int32_t policy) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (policy < 0 || policy > 5) return fail(LT_ERR_INVALID, "shift policy %d", policy);
-  if (!LT_EXPERIMENTS && (policy == 1 || policy == 2 || policy == 5))
-    return fail(LT_ERR_UNSUPPORTED, "shift policy %d is a tile variant of the experiments build (make EXPERIMENTS=1)", policy);
+  if (policy == 1 || policy == 2 || policy == 5)
+    return fail(LT_ERR_UNSUPPORTED, "shift policy %d: its tile variant lost its A/B and was removed", policy);
   if (p->shift != policy) p->canary = 0;
   p->shift = policy;
   return LT_OK;
@@ -1478,14 +1431,6 @@ int lt_plan_set_graph_mode(lt_plan *p, int32_t mode) {
   return LT_OK;
 }
 
-#if LT_EXPERIMENTS
-int lt_stream_collide_thrice(lt_plan *p, const void *f, void *out, double tau, void *stream) {
-  if (!p) return fail(LT_ERR_INVALID, "null plan");
-  if (p->unit.d != 3 || p->desc.ghost_planes || p->masked || p->desc.layout != LT_LAYOUT_REFERENCE)
-    return fail(LT_ERR_UNSUPPORTED, "three steps per launch: periodic 3-D plans without boundaries, reference layout");
-  return step(p, lt::kFusedThrice, f, out, tau, 0, p->n2, stream);
-}
-#endif
 int lt_stream_collide_twice(lt_plan *p, const void *f, void *out, double tau, void *stream) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   const int g = p->desc.ghost_planes;
@@ -1757,20 +1702,6 @@ int lt_ipc_free(void *dev) {
   return LT_OK;
 }
 
-#if LT_EXPERIMENTS
-int lt_plan_set_arithmetic(lt_plan *p, int32_t mode) {
-  if (!p) return fail(LT_ERR_INVALID, "null plan");
-  if (mode != 0 && mode != 1) return fail(LT_ERR_INVALID, "arithmetic %d (0 = the reference's, 1 = fast)", mode);
-  if (mode == 1 && (p->desc.collision != LT_COLLISION_BGK || p->unit.d != 3 || p->desc.n_boundaries > 0 || p->masked ||
-                    p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes))
-    return fail(LT_ERR_UNSUPPORTED, "fast arithmetic exists for BGK on periodic 3-D plans without boundaries in the "
-                                    "reference layout");
-  p->arith = mode;
-  return LT_OK;
-}
-
-#endif
-
 int lt_plan_set_canary(lt_plan *p, int32_t mode) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < 0 || mode > 2) return fail(LT_ERR_INVALID, "canary mode %d (0 skip, 1 check on first use, 2 report a mismatch)", mode);
@@ -1797,11 +1728,10 @@ int lt_plan_set_residency(lt_plan *p, int32_t workgroups_per_cu) {
 int lt_plan_set_tuning(lt_plan *p, int32_t cache_policy, int32_t wide) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (cache_policy < -1 || cache_policy > 3) return fail(LT_ERR_INVALID, "cache policy %d", cache_policy);
-  if (wide && !LT_EXPERIMENTS)
-    return fail(LT_ERR_UNSUPPORTED, "the 16-byte variants of the one-step kernel belong to the experiments build "
-                                    "(make EXPERIMENTS=1; they measured 8-13 %% slower)");
+  if (wide)
+    return fail(LT_ERR_UNSUPPORTED, "the 16-byte variants of the one-step kernel lost their A/B (8-13 %% slower) and "
+                                    "were removed");
   p->tune = cache_policy;
-  p->want_wide = wide ? 1 : 0;
   return LT_OK;
 }
 

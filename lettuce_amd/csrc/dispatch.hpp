@@ -2,14 +2,11 @@
 // per-(stencil, dtype) translation units that instantiate the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
-#ifndef LT_EXPERIMENTS
-#define LT_EXPERIMENTS 0        // make EXPERIMENTS=1: also the kernels that lost their A/B (unit.inc)
-#endif
 #include <stdint.h>
 
 namespace lt {
 
-enum StepMode { kFused = 0, kCollideOnly = 1, kStreamOnly = 2, kFusedTwice = 3, kFusedMany = 4, kFusedThrice = 5 };
+enum StepMode { kFused = 0, kCollideOnly = 1, kStreamOnly = 2, kFusedTwice = 3, kFusedMany = 4 };
 
 struct StepArgs {
   const void *in;
@@ -25,7 +22,7 @@ struct StepArgs {
   const unsigned *nsm_bits;
   const void *bt;        // BoundaryTable<T>* (device)
   int nb;
-  int layout, coll, mode, masked, wide, shift, tune;
+  int layout, coll, mode, masked, shift, tune;
   int strip;             // kFusedTwice on 2-D lattices: columns per workgroup (512 / 256 / 128 / 64)
   int abb_axis;          // kFusedTwice with masks: memory axis of the plan's outlet (2 without one)
   int n_abb;             // anti-bounce-back outlets of the plan

@@ -11,14 +11,12 @@
 // (_simulation.py:177-189).
 //
 // Design for MI355X (HBM-bound: 2*q*sizeof(T) bytes per node, ~2-4 flop/byte, no MFMA):
-//  * SoA per velocity; a thread owns VEC consecutive nodes along the contiguous axis a0
-//    (VEC*sizeof(T) = 16 B), so every population is read and written with one 16-byte
-//    access per lane = 1 KiB per wave instruction, fully coalesced.
+//  * SoA per velocity; a thread owns one node, so consecutive lanes read and write consecutive
+//    elements of every population, fully coalesced (16-byte accesses of several nodes per thread
+//    measured 8-13 % slower in round 1: fewer waves per SIMD).
 //  * Pull scheme: each slot of f*_in is read by exactly one thread, each slot of the output
-//    is written by exactly one thread (no atomics, no write races, no halo re-reads).  The
-//    +-1 shift along a0 is resolved in registers from the aligned 16-byte load plus one
-//    neighbour element (or a cross-lane shift), so HBM traffic stays at the algorithmic
-//    2*q*sizeof(T) per node.
+//    is written by exactly one thread (no atomics, no write races, no halo re-reads), so HBM
+//    traffic stays at the algorithmic 2*q*sizeof(T) per node.
 //  * Everything between the loads and the stores lives in VGPRs; the lattice is a template
 //    parameter so e_q, w_q and the opposite table are folded into the instruction stream.
 #pragma once
@@ -51,7 +49,7 @@ struct KParams {
   const T *in;
   T *out;
   int n0, n1, n2;            // memory extents; n2 includes ghost planes
-  int nv0;                   // n0 / VEC
+  int nv0;                   // one-step kernels: threads per row (n0)
   int p_begin;               // first a2 plane of this launch
   int p_end;                 // two-step kernel: one past the last output plane
   int p_begin2, p_end2;      // two-step kernel: optional second range of output planes (slab edges)
@@ -97,61 +95,21 @@ constexpr double kCs = 0.57735026918962584;   // 1/sqrt(3) rounded to double
 constexpr double kCs2 = kCs * kCs;
 constexpr double kCs4 = kCs2 * kCs2;
 
-// ---- 16-byte vector access ---------------------------------------------------------------
-template <typename T, int VEC> struct Vec;
-template <> struct Vec<float, 4> {
-  typedef float type __attribute__((ext_vector_type(4)));
-  typedef float utype __attribute__((ext_vector_type(4), aligned(4)));
-  typedef unsigned char mtype __attribute__((ext_vector_type(4)));
-};
-template <> struct Vec<float, 2> {
-  typedef float type __attribute__((ext_vector_type(2)));
-  typedef float utype __attribute__((ext_vector_type(2), aligned(4)));
-  typedef unsigned char mtype __attribute__((ext_vector_type(2)));
-};
-template <> struct Vec<double, 2> {
-  typedef double type __attribute__((ext_vector_type(2)));
-  typedef double utype __attribute__((ext_vector_type(2), aligned(8)));
-  typedef unsigned char mtype __attribute__((ext_vector_type(2)));
-};
-
+// ---- population access ----------------------------------------------------------------------
 // NT = nontemporal hint: the populations are streamed once per step and the working set
 // (2.5 GB at 256^3) is far beyond L2 + Infinity Cache, so nothing is gained by keeping lines.
-template <typename T, int VEC, bool NT = false>
-__device__ __forceinline__ void vload(const T *__restrict__ p, T (&r)[VEC]) {
-  if constexpr (VEC == 1) {
-    r[0] = NT ? __builtin_nontemporal_load(p) : *p;
-  } else {
-    using V = typename Vec<T, VEC>::type;
-    const V *vp = reinterpret_cast<const V *>(p);
-    const V v = NT ? __builtin_nontemporal_load(vp) : *vp;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) r[k] = v[k];
-  }
+template <typename T, bool NT = false>
+__device__ __forceinline__ T load(const T *__restrict__ p) {
+  return NT ? __builtin_nontemporal_load(p) : *p;
 }
-template <typename T, int VEC>
-__device__ __forceinline__ void vload_unaligned(const T *__restrict__ p, T (&r)[VEC]) {
-  const typename Vec<T, VEC>::utype v = *reinterpret_cast<const typename Vec<T, VEC>::utype *>(p);
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) r[k] = v[k];
-}
-template <typename T, int VEC, bool NT = false>
-__device__ __forceinline__ void vstore(T *__restrict__ p, const T (&r)[VEC]) {
-  if constexpr (VEC == 1) {
-    if constexpr (NT) __builtin_nontemporal_store(r[0], p); else *p = r[0];
-  } else {
-    using V = typename Vec<T, VEC>::type;
-    V v;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] = r[k];
-    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<V *>(p));
-    else *reinterpret_cast<V *>(p) = v;
-  }
+template <typename T, bool NT = false>
+__device__ __forceinline__ void store(T *__restrict__ p, T v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v;
 }
 
 // ---- node coordinates -----------------------------------------------------------------------
 struct Coord {
-  int c0, c1, c2;      // own (first of VEC along a0)
+  int c0, c1, c2;      // own
   int c1m, c1p;        // periodic neighbours along a1
   int c2m, c2p;        // neighbours along a2 (periodic iff wrap2)
 };
@@ -171,16 +129,11 @@ __device__ __forceinline__ Coord make_coord(const KParams<T> &p, int c0, int c1,
   return c;
 }
 
-// ---- gather: post-streaming populations of VEC nodes ------------------------------------
+// ---- gather: post-streaming populations of one node ------------------------------------
 // f_q(x) = f*_q(x - e_q), periodic (Simulation._stream: torch.roll by +e_q,
-// lettuce/_simulation.py:156-158,164-175).  SHIFT selects how the a0 shift is resolved:
-//   0: aligned 16-B load + one neighbour element load
-//   1: unaligned 16-B load (row ends handled separately)
-//   2: aligned 16-B load + cross-lane shift (ds_bpermute), neighbour element only at wave/row edges
-//   3: aligned 16-B load + wave ROTATE: legal when a row is exactly one wave (n0 == 64 * VEC);
-//      the periodic wrap is then the rotation itself and no neighbour element is ever loaded
-template <typename T, class S, int LAYOUT, bool STREAM, int VEC, int SHIFT, bool NTL = false>
-__device__ __forceinline__ void gather(const KParams<T> &p, const Coord &c, T (&f)[S::Q][VEC]) {
+// lettuce/_simulation.py:156-158,164-175)
+template <typename T, class S, int LAYOUT, bool STREAM, bool NTL = false>
+__device__ __forceinline__ void gather(const KParams<T> &p, const Coord &c, T (&f)[S::Q][1]) {
   using M = MemMap<S, LAYOUT>;
   const int n0 = p.n0, n1 = p.n1;
   const unsigned own = (unsigned)(c.c2 * n1 + c.c1) * (unsigned)n0 + (unsigned)c.c0;
@@ -188,74 +141,17 @@ __device__ __forceinline__ void gather(const KParams<T> &p, const Coord &c, T (&
     constexpr int q = decltype(qc)::value;
     const T *__restrict__ src = p.in + (long long)q * p.Ni;
     if constexpr (!STREAM) {
-      vload<T, VEC, NTL>(src + own, f[q]);
+      f[q][0] = load<T, NTL>(src + own);
     } else {
       constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2);
       const int s1 = e1 == 0 ? c.c1 : (e1 > 0 ? c.c1m : c.c1p);
       const int s2 = e2 == 0 ? c.c2 : (e2 > 0 ? c.c2m : c.c2p);
       const unsigned row = (unsigned)(s2 * n1 + s1) * (unsigned)n0;
       if constexpr (e0 == 0) {
-        vload<T, VEC, NTL>(src + row + c.c0, f[q]);
-      } else if constexpr (VEC == 1) {
+        f[q][0] = load<T, NTL>(src + row + c.c0);
+      } else {
         const int s0 = e0 > 0 ? (c.c0 == 0 ? n0 - 1 : c.c0 - 1) : (c.c0 == n0 - 1 ? 0 : c.c0 + 1);
         f[q][0] = src[row + s0];
-      } else if constexpr (e0 > 0) {
-        // want src[c0-1], src[c0], ..., src[c0+VEC-2]
-        if constexpr (SHIFT == 1) {
-          if (c.c0 != 0) {
-            vload_unaligned<T, VEC>(src + row + c.c0 - 1, f[q]);
-          } else {
-            T a[VEC];
-            vload<T, VEC, NTL>(src + row, a);
-            f[q][0] = src[row + n0 - 1];
-#pragma unroll
-            for (int k = 1; k < VEC; ++k) f[q][k] = a[k - 1];
-          }
-        } else {
-          T a[VEC];
-          vload<T, VEC, NTL>(src + row + c.c0, a);
-          T nb;
-          if constexpr (SHIFT == 3) {
-            nb = __shfl(a[VEC - 1], (threadIdx.x + 63) & 63);
-          } else if constexpr (SHIFT == 2) {
-            nb = __shfl_up(a[VEC - 1], 1);
-            if ((threadIdx.x & 63) == 0 || c.c0 == 0) nb = src[row + (c.c0 == 0 ? n0 - 1 : c.c0 - 1)];
-          } else {
-            nb = src[row + (c.c0 == 0 ? n0 - 1 : c.c0 - 1)];
-          }
-          f[q][0] = nb;
-#pragma unroll
-          for (int k = 1; k < VEC; ++k) f[q][k] = a[k - 1];
-        }
-      } else {
-        // want src[c0+1], ..., src[c0+VEC]
-        const bool last = c.c0 + VEC == n0;
-        if constexpr (SHIFT == 1) {
-          if (!last) {
-            vload_unaligned<T, VEC>(src + row + c.c0 + 1, f[q]);
-          } else {
-            T a[VEC];
-            vload<T, VEC, NTL>(src + row + c.c0, a);
-#pragma unroll
-            for (int k = 0; k < VEC - 1; ++k) f[q][k] = a[k + 1];
-            f[q][VEC - 1] = src[row];
-          }
-        } else {
-          T a[VEC];
-          vload<T, VEC, NTL>(src + row + c.c0, a);
-          T nb;
-          if constexpr (SHIFT == 3) {
-            nb = __shfl(a[0], (threadIdx.x + 1) & 63);
-          } else if constexpr (SHIFT == 2) {
-            nb = __shfl_down(a[0], 1);
-            if ((threadIdx.x & 63) == 63 || last) nb = src[row + (last ? 0 : c.c0 + VEC)];
-          } else {
-            nb = src[row + (last ? 0 : c.c0 + VEC)];
-          }
-#pragma unroll
-          for (int k = 0; k < VEC - 1; ++k) f[q][k] = a[k + 1];
-          f[q][VEC - 1] = nb;
-        }
       }
     }
   });
@@ -440,71 +336,6 @@ __device__ __forceinline__ void collide_bgk(T (&f)[S::Q][VEC], T tau_inv) {
 #pragma clang fp contract(off)
     constexpr int q = decltype(qc)::value;
     f[q][k] = f[q][k] - tau_inv * (f[q][k] - feq);
-  });
-}
-
-// BGK in "fast" arithmetic (COLL = 3; lt_plan_set_arithmetic): the same collision to rounding level instead of bit
-// for bit.  collide_bgk reproduces every rounding of the reference's whole-field torch operators (~290 vector
-// instructions per node: three IEEE divisions by rho, the exact-division emulation 28 times, no fused multiply-adds,
-// ATen's summation order); SURVEY.md 8(d) only asks for max |df| <= 1e-5 max |f| after 10 steps and the kinetic
-// energy to 1e-6 (10 steps) / 5e-5 (100 steps) in fp32.  Here: moments over opposite pairs, one reciprocal of rho,
-// cs^2 = 1/3, omega folded into the weights, everything contracted -- about half the instructions.
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-  return __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-}
-template <typename T, class S, int LAYOUT, int VEC, int k>
-__device__ __forceinline__ void collide_bgk_fast(T (&f)[S::Q][VEC], T omega) {
-  // explicit fused multiply-adds and no contraction by the compiler: every kernel this is inlined into (one-step,
-  // collide-only, two-step) then returns the same bits, whatever the surrounding code
-#pragma clang fp contract(off)
-  using M = MemMap<S, LAYOUT>;
-  T rho = T(0), j[3] = {T(0), T(0), T(0)};
-  static_for<S::Q>([&](auto qc) {
-    constexpr int q = decltype(qc)::value;
-    constexpr int o = S::OPP[q];
-    if constexpr (q == o) {
-      rho += f[q][k];
-    } else if constexpr (q < o) {
-      rho += f[q][k] + f[o][k];
-      add_momentum<S, LAYOUT, q>(j, f[q][k] - f[o][k]);
-    }
-  });
-  const T inv = fast_rcp(rho);
-  // The reference divides by 2 cs^2 ROUNDED to the working dtype (fp32: 0.6666667, 3e-8 too large), which gives its
-  // fp32 equilibrium a momentum deficit of 3e-8 and its kinetic energy a drift of -1.1e-7 per step against its fp64
-  // run.  To stay within 1e-6 of ITS fp32 energy series the velocity carries the same factor:
-  // u = RN(j / rho (1 - delta)), formed inside one fused multiply-add so that the half-ulp correction acts through
-  // the rounding of the product (on a rounded product it would always round away).  fp64: delta = 1e-16, no effect.
-  constexpr double delta = 1.5 * (double)(T)(2.0 * kCs2) - 1.0;
-  T u[3] = {T(0), T(0), T(0)};
-  static_for<S::D>([&](auto ac) {
-    constexpr int a = decltype(ac)::value;
-    const T plain = j[a] * inv;
-    u[a] = fma_t(j[a], inv, T(-delta) * plain);
-  });
-  T uu = u[M::memory(0)] * u[M::memory(0)];
-  if constexpr (S::D > 1) uu = fma_t(u[M::memory(1)], u[M::memory(1)], uu);
-  if constexpr (S::D > 2) uu = fma_t(u[M::memory(2)], u[M::memory(2)], uu);
-  const T c0 = fma_t(T(-1.5), uu, T(1)), keep = T(1) - omega, wr = omega * rho;
-  static_for<S::Q>([&](auto qc) {
-    constexpr int q = decltype(qc)::value;
-    constexpr int o = S::OPP[q];
-    if constexpr (q == o) {
-      f[q][k] = fma_t(keep, f[q][k], (T(S::W[q]) * wr) * c0);
-    } else if constexpr (q < o) {
-      const T eu = dot_e<S, LAYOUT, q>(u);
-      // the weights as literals: w h +- 3 w (e.u) with h = 1 - 1.5 u.u + 4.5 (e.u)^2, then omega rho once.  Measured on
-      // the same buffers against three other arrangements of the same multiply-adds (weights times omega rho in
-      // registers; sums fused the other way round; the compiler's own contraction): 0.4749 against 0.4771 - 0.4845 ms
-      // per launch at 256^3, the exact arithmetic 0.496 - 0.516 (profiles/r04j_fast_arithmetic_variants.jsonl)
-      const T h = fma_t(T(4.5) * eu, eu, c0);
-      const T g = fma_t(T(3.0 * S::W[q]), eu, T(S::W[q]) * h), m = fma_t(T(-3.0 * S::W[q]), eu, T(S::W[q]) * h);
-      f[q][k] = fma_t(keep, f[q][k], wr * g);
-      f[o][k] = fma_t(keep, f[o][k], wr * m);
-    }
   });
 }
 
@@ -733,7 +564,7 @@ __device__ __forceinline__ void neighbour_moments(const KParams<T> &p, int c0, i
                                                   T &rho, T (&j)[3]) {
   const Coord c = make_coord(p, c0, c1, c2);
   T g[S::Q][1];
-  gather<T, S, LAYOUT, STREAM, 1, 0>(p, c, g);
+  gather<T, S, LAYOUT, STREAM>(p, c, g);
   const unsigned own = (unsigned)(c2 * p.n1 + c1) * (unsigned)p.n0 + (unsigned)c0;
   int b = 0;
   if constexpr (MASKED) {
@@ -834,7 +665,7 @@ __device__ __forceinline__ void apply_boundaries(const KParams<T> &p, int b, int
 }
 
 // ---- the kernel ---------------------------------------------------------------------------
-// TUNE bit 0: nontemporal loads, bit 1: nontemporal stores.  One thread per VEC nodes, the grid
+// TUNE bit 0: nontemporal loads, bit 1: nontemporal stores.  One thread per node, the grid
 // covers the work exactly (a capped grid with a grid-stride loop measured 7 % slower and cost
 // 20-30 VGPRs in the KBC kernels).
 // number of populations q' < q with the same velocity component along memory axis a2
@@ -848,37 +679,27 @@ constexpr int crossing_rank() {
 
 // ABBD: plans with ABBD + 1 anti-bounce-back outlets (neighbour_moments, DEPTH)
 template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
-          int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+          int TUNE = 0, bool PACK = false, int ABBD = 0>
 __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
   const unsigned v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= p.nvec_total) return;
   {
   const unsigned rowid = v / (unsigned)p.nv0;
-  const int c0 = (int)(v - rowid * (unsigned)p.nv0) * VEC;
+  const int c0 = (int)(v - rowid * (unsigned)p.nv0);
   const int r2 = (int)(rowid / (unsigned)p.n1);
   const int c1 = (int)(rowid - (unsigned)r2 * (unsigned)p.n1);
   const int c2 = p.p_begin + r2 * p.p_stride;
   const Coord c = make_coord(p, c0, c1, c2);
   const unsigned own = (unsigned)(c2 * p.n1 + c1) * (unsigned)p.n0 + (unsigned)c0;
 
-  T f[S::Q][VEC];
-  gather<T, S, LAYOUT, STREAM, VEC, SHIFT, (TUNE & 1) != 0>(p, c, f);
+  T f[S::Q][1];
+  gather<T, S, LAYOUT, STREAM, (TUNE & 1) != 0>(p, c, f);
 
-  unsigned char nd[VEC];
+  unsigned char nd;
   if constexpr (MASKED) {
-    if constexpr (VEC == 1) {
-      nd[0] = p.node[own];
-    } else {
-      const typename Vec<T, VEC>::mtype m =
-          *reinterpret_cast<const typename Vec<T, VEC>::mtype *>(p.node + own);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) nd[k] = m[k];
-    }
+    nd = p.node[own];
     if constexpr (STREAM) {
-      static_for<VEC>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        if (nd[k] & 0x80) keep_unstreamed<T, S, VEC, k>(p, own, f);
-      });
+      if (nd & 0x80) keep_unstreamed<T, S, 1, 0>(p, own, f);
     }
   }
 
@@ -888,14 +709,14 @@ __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
   // their latency in every wave that ends a row: 0.48 -> 0.60 ms at 512 x 512 x 64 with the Obstacle's outlet)
   int lane_slot = 0;
   T lane_rho = T(1), lane_j[3] = {T(0), T(0), T(0)};
-  if constexpr (COLLIDE && MASKED && VEC == 1 && ABBD == 0) {
+  if constexpr (COLLIDE && MASKED && ABBD == 0) {
     if (p.abb0_slot != 0) {
       const int slot = p.abb0_slot, plane = p.bt->plane[slot];
       const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
       const int first = c0 - lane;                                 // a0 coordinate of lane 0: same in all lanes
       if (plane >= first && plane < first + 64) {
         moments<T, S, LAYOUT, 1, 0>(f, lane_rho, lane_j);
-        lower_boundaries_on_moments<T, S, LAYOUT>(p, nd[0] & 0x7f, slot, own, lane_rho, lane_j);
+        lower_boundaries_on_moments<T, S, LAYOUT>(p, nd & 0x7f, slot, own, lane_rho, lane_j);
         const int from = (lane - p.bt->side[slot]) & 63;
         lane_rho = __shfl(lane_rho, from);
         lane_j[0] = __shfl(lane_j[0], from); lane_j[1] = __shfl(lane_j[1], from); lane_j[2] = __shfl(lane_j[2], from);
@@ -905,24 +726,23 @@ __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
   }
 
   if constexpr (COLLIDE) {
-    static_for<VEC>([&](auto kc) {
-      constexpr int k = decltype(kc)::value;
+    // (a lambda, as the former loop over a thread's nodes was: inlined in that order, the masked kernels keep their
+    // register allocation)
+    [&] {
       int b = 0;
-      if constexpr (MASKED) b = nd[k] & 0x7f;
+      if constexpr (MASKED) b = nd & 0x7f;
       if (b == 0) {
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, VEC, k>(f, p.tau_inv);
-        if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, VEC, k>(f, p.beta, p.inv_beta);
-        if constexpr (COLL == 3) collide_bgk_fast<T, S, LAYOUT, VEC, k>(f, p.tau_inv);
+        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(f, p.tau_inv);
+        if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(f, p.beta, p.inv_beta);
       }
       if constexpr (MASKED)
-        apply_boundaries<T, S, LAYOUT, STREAM, VEC, k, COLL, ABBD>(p, b, c0 + k, c1, c2, own + k, f, lane_slot,
-                                                                    lane_rho, lane_j);
-    });
+        apply_boundaries<T, S, LAYOUT, STREAM, 1, 0, COLL, ABBD>(p, b, c0, c1, c2, own, f, lane_slot, lane_rho, lane_j);
+    }();
   }
 
   static_for<S::Q>([&](auto qc) {
     constexpr int q = decltype(qc)::value;
-    vstore<T, VEC, (TUNE & 2) != 0>(p.out + (long long)q * p.No + own, f[q]);
+    store<T, (TUNE & 2) != 0>(p.out + (long long)q * p.No + own, f[q][0]);
   });
   if constexpr (PACK) {
     // halo packing fused into the boundary-plane launch of the slab driver (saves two pack
@@ -937,17 +757,20 @@ __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
         constexpr int rank = crossing_rank<S, LAYOUT, q>();
         T *buf = e2 < 0 ? p.pack_lo : p.pack_hi;
         const int plane = e2 < 0 ? p.pack_lo_plane : p.pack_hi_plane;
-        if (c2 == plane) vstore<T, VEC, false>(buf + (size_t)rank * plane_nodes + in_plane, f[q]);
+        if (c2 == plane) store<T>(buf + (size_t)rank * plane_nodes + in_plane, f[q][0]);
       }
     });
   }
   }
 }
 
+// VEC (nodes per thread) and SHIFT (how a 16-byte access resolves the a0 shift) name variants that lost their A/B
+// (DESIGN.md section 4); they stay in the signature because kernel names and profiles are keyed on them
 template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
           int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParams<T> p) {
-  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, VEC, SHIFT, TUNE, PACK, ABBD>(p);
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 
 // same kernel with the register allocator told to fit 4 waves per SIMD (<= 128 VGPRs): the masked
@@ -955,7 +778,8 @@ __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParams<T> p) {
 template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
           int VEC, int SHIFT, int TUNE = 0, bool PACK = false>
 __global__ void __launch_bounds__(kThreads, 4) lbm_kernel_occ4(const KParams<T> p) {
-  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, VEC, SHIFT, TUNE, PACK>(p);
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK>(p);
 }
 
 // ---- two fused steps per launch (periodic, no masks) -----------------------------------------
@@ -979,7 +803,6 @@ __global__ void __launch_bounds__(kThreads, 4) lbm_kernel_occ4(const KParams<T> 
 // Arithmetic per node is the one-step kernel's (same pull, same collide): results are bit for bit
 // those of two lbm_kernel launches.  Redundant work: (T0+2)(T1+2)/(T0 T1) in the first step and
 // two extra planes per segment.  HBM traffic (PMC, 256^3): reads 1.05x one pass, writes 1.00x.
-// NPT / NPB: intermediate / output nodes per thread (A/B variants, 1 is the product setting);
 // PACK: slab edge launches that also write the halo message.
 template <typename T, class S, int T0_, int T1>
 struct TwoStep {
@@ -1002,22 +825,21 @@ __device__ __forceinline__ void lds_barrier() {
 // MODE (slab layout): 0 = plain sweep; 1 = edge launch: every workgroup also writes the halo messages, and the
 // planes beyond the cuts are read from the receive buffers when p.ghost_lo / p.ghost_hi are given; 2 = launch
 // over the whole slab whose edge workgroups start first and count themselves done (p.signal).
+// NPT / NPB: intermediate / output nodes per thread.  Two of either lost their A/B; they stay
+// in the signature because kernel names and profiles are keyed on them.
 template <typename T, class S, int LAYOUT, int COLL, int T0_, int T1, int NPT = 1, int MODE = 0,
           int NPB = NPT>
 __global__ void __launch_bounds__(((TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64))
 lbm2_kernel(const KParams<T> p, const int seg_len) {
   constexpr bool PACK = MODE == 1;
   static_assert(MODE == 0 || LAYOUT == 1, "edge / signalling launches exist in the slab layout");
-  // NPT intermediate nodes and NPB output nodes per thread (1 or 2): thread t owns intermediate
-  // nodes t + k NA, k < NPT, and output nodes t + k NB, k < NPB
+  static_assert(NPT == 1 && NPB == 1, "one intermediate and one output node per thread");
   using B = TwoStep<T, S, T0_, T1>;
   using M = MemMap<S, LAYOUT>;
   constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
-  constexpr int NA = NI / NPT, NB = NO / NPB;
-  static_assert(NI % NPT == 0 && NO % NPB == 0, "nodes per thread must divide the tile");
   constexpr int NU = B::template count<LAYOUT, 1>(), NC = B::template count<LAYOUT, 0>(),
                 ND = B::template count<LAYOUT, -1>();
-  static_assert(COLL == 0 || COLL == 1 || COLL == 3, "two-step kernel: streaming only or BGK (exact / fast arithmetic)");
+  static_assert(COLL == 0 || COLL == 1, "two-step kernel: streaming only or BGK");
   __shared__ T lds_u[4][NU][NI];
   __shared__ T lds_c[3][NC][NI];
   __shared__ T lds_d[2][ND][NI];
@@ -1055,7 +877,7 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
   const int range_end = second ? p.p_end2 : p.p_end;
   const int s = second ? p.p_begin2 + (b - segs_a) * seg_len : p.p_begin + b * seg_len;
 
-  const bool in_a = tid < NA, in_b = tid < NB;
+  const bool in_a = tid < NI, in_b = tid < NO;
   // Addresses: the plane part is uniform (scalar registers, recomputed per plane), the in-plane
   // part is a per-thread constant -- nine byte offsets for the nine (e0, e1) pairs of the lattice.
   unsigned voff[NPT][3][3];                          // [k][e1 + 1][e0 + 1], bytes within a plane
@@ -1067,15 +889,10 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
     // phase A: node (i0, i1) of the halo'd tile, global coordinates (g0, g1).  The T0 inner columns
     // of a row go to T0 consecutive threads (a wave reads one aligned 256-byte row segment per
     // population), the two halo columns of all rows to the last threads.
-    const int ia = tid + k * NA;
-    int i1, i0;
-    if (NPT == 1) {
-      constexpr int inner = T0 * B::H1;
-      i1 = ia < inner ? ia / T0 : (ia - inner) >> 1;
-      i0 = ia < inner ? 1 + (ia - i1 * T0) : (((ia - inner) & 1) ? H0 - 1 : 0);
-    } else {
-      i1 = ia / H0; i0 = ia - i1 * H0;
-    }
+    const int ia = tid + k * NI;
+    constexpr int inner = T0 * B::H1;
+    const int i1 = ia < inner ? ia / T0 : (ia - inner) >> 1;
+    const int i0 = ia < inner ? 1 + (ia - i1 * T0) : (((ia - inner) & 1) ? H0 - 1 : 0);
     a_at[k] = i1 * H0 + i0;
     int g0 = t0 + i0 - 1; g0 = g0 < 0 ? g0 + p.n0 : (g0 >= p.n0 ? g0 - p.n0 : g0);
     int g1 = t1 + i1 - 1; g1 = g1 < 0 ? g1 + p.n1 : (g1 >= p.n1 ? g1 - p.n1 : g1);
@@ -1093,7 +910,7 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
   static_for<NPB>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     // phase B: output node (j0, j1) of the tile
-    const int ib = tid + k * NB;
+    const int ib = tid + k * NO;
     const int j1 = ib / T0, j0 = ib - j1 * T0;
     out_off[k] = ((unsigned)(t1 + j1) * (unsigned)p.n0 + (unsigned)(t0 + j0)) * (unsigned)sizeof(T);
     b_at[k] = (j1 + 1) * H0 + (j0 + 1);
@@ -1143,8 +960,6 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
     if (in_a) {
       if constexpr (COLL == 1)
         static_for<NPT>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau_inv); });
-      if constexpr (COLL == 3)
-        static_for<NPT>([&](auto kc) { collide_bgk_fast<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau_inv); });
       static_for<S::Q>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
@@ -1177,8 +992,6 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
     if (in_b) {
       if constexpr (COLL == 1)
         static_for<NPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau_inv); });
-      if constexpr (COLL == 3)
-        static_for<NPB>([&](auto kc) { collide_bgk_fast<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau_inv); });
     }
   };
   // packing: this workgroup writes halo messages (PACK kernels; a launch that covers a whole slab runs the
@@ -1237,7 +1050,7 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
 
   // intermediate planes s-1 .. s+seg_len are needed (relative indices 0 .. seg_len+1)
   const int last = s + seg_len < range_end ? s + seg_len : range_end;
-  if constexpr (PACK && NPT == 1 && NPB == 1) {
+  if constexpr (PACK) {
     if (last - s == 2) {
       // Slab edge launch: two output planes per workgroup, i.e. four intermediate planes and no sweep to amortise a
       // serial prologue over, with all 256 workgroups of a round in lock-step (memory idle while they collide, compute
@@ -1276,7 +1089,6 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
       auto collide_into_lds = [&](T (&src)[S::Q][1], int r, int r3, auto keep) {
         constexpr int KEEP = decltype(keep)::value;
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
-        if constexpr (COLL == 3) collide_bgk_fast<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
         if (in_a) {
           static_for<S::Q>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
@@ -1547,63 +1359,6 @@ lbm_many_kernel(const KParams<T> p, const int K) {
   }
   // after K steps the valid nodes are the tile
   if (in_region && i0 >= halo && i0 < r0 - halo && i1 >= halo && i1 < r1 - halo) {
-    static_for<S::Q>([&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      p.out[(long long)q * p.No + own] = f[q][0];
-    });
-  }
-}
-
-// ---- two steps per launch on small 3-D grids -----------------------------------------------------
-// The 3-D counterpart of lbm_many_kernel for grids that are bound by launch latency (32^3: 3.9 us per step for
-// well under 1 us of work).  A workgroup of 1000 threads loads the 10^3 neighbourhood of its 8^3 tile (one node per
-// thread: the ordinary pull from global memory + collide), leaves the populations in LDS (q x 1000 values: 76 KB
-// for D3Q19 fp32, two workgroups per CU), and the 512 threads of the inner tile pull their second step from there,
-// collide and store.  The shell is recomputed by every workgroup that needs it (1.95 x the arithmetic of the first
-// step) -- free while the chip waits for launches.  Same pull, same collide as the one-step kernel: two launches of
-// lbm_kernel give the same bits (BGK / streaming); grids smaller than the neighbourhood wrap (8^3).
-constexpr int kMany3dTile = 8, kMany3dEdge = kMany3dTile + 2, kMany3dNodes = kMany3dEdge * kMany3dEdge * kMany3dEdge;
-template <typename T, class S, int COLL>
-__global__ void __launch_bounds__(1024) lbm_many3d_kernel(const KParams<T> p) {
-  static_assert(S::D == 3, "3-D lattices");
-  using M = MemMap<S, 0>;
-  constexpr int E = kMany3dEdge, NR = kMany3dNodes, TO = kMany3dTile;
-  __shared__ T lds[S::Q][NR];
-  const int tid = threadIdx.x;
-  const int tiles0 = p.n0 / TO, tiles1 = p.n1 / TO;
-  int b = blockIdx.x;
-  const int t0 = (b % tiles0) * TO; b /= tiles0;
-  const int t1 = (b % tiles1) * TO; b /= tiles1;
-  const int t2 = b * TO;
-  const bool in_region = tid < NR;
-  const int i2 = tid / (E * E), i1 = (tid / E) % E, i0 = tid % E;
-  auto wrap = [](int x, int n) { x %= n; return x < 0 ? x + n : x; };
-  const int g0 = wrap(t0 - 1 + i0, p.n0), g1 = wrap(t1 - 1 + i1, p.n1), g2 = wrap(t2 - 1 + i2, p.n2);
-  T f[S::Q][1];
-  if (in_region) {
-    static_for<S::Q>([&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2);
-      const int s0 = e0 == 0 ? g0 : wrap(g0 - e0, p.n0), s1 = e1 == 0 ? g1 : wrap(g1 - e1, p.n1),
-                s2 = e2 == 0 ? g2 : wrap(g2 - e2, p.n2);
-      f[q][0] = p.in[(long long)q * p.Ni + ((long long)s2 * p.n1 + s1) * p.n0 + s0];
-    });
-    if constexpr (COLL == 1) collide_bgk<T, S, 0, 1, 0>(f, p.tau_inv);
-    static_for<S::Q>([&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      lds[q][tid] = f[q][0];
-    });
-  }
-  __syncthreads();
-  // second step: the nodes of the tile (distance >= 1 from the border of the neighbourhood)
-  if (in_region && i0 >= 1 && i0 <= TO && i1 >= 1 && i1 <= TO && i2 >= 1 && i2 <= TO) {
-    static_for<S::Q>([&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2);
-      f[q][0] = lds[q][tid - (e2 * E + e1) * E - e0];
-    });
-    if constexpr (COLL == 1) collide_bgk<T, S, 0, 1, 0>(f, p.tau_inv);
-    const long long own = ((long long)g2 * p.n1 + g1) * p.n0 + g0;
     static_for<S::Q>([&](auto qc) {
       constexpr int q = decltype(qc)::value;
       p.out[(long long)q * p.No + own] = f[q][0];

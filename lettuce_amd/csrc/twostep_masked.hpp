@@ -121,7 +121,7 @@ lbm2m_kernel(const KParams<T> p, const int seg_len) {
   constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
   constexpr int NU = B::template count<LAYOUT, 1>(), NC = B::template count<LAYOUT, 0>(),
                 ND = B::template count<LAYOUT, -1>();
-  static_assert(COLL == 0 || COLL == 1 || COLL == 2, "two-step kernel: streaming only, BGK or (experiment) KBC");
+  static_assert(COLL == 0 || COLL == 1, "two-step kernel: streaming only or BGK");
   static_assert(NO % 64 == 0, "the output nodes of a tile fill whole waves");
   // (D3Q27: the collision + boundary code of one node is ~3000 instructions and the sweep below inlines it fifteen
   // times -- 300 KB of code against a 64 KB instruction cache.  A compact form with one copy of the prologue plane and
@@ -245,7 +245,6 @@ lbm2m_kernel(const KParams<T> p, const int seg_len) {
     const int bidx = nd & 0x7f;
     if (bidx == 0) {
       if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(g, p.tau_inv);
-      if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(g, p.beta, p.inv_beta);
     }
     if (on_outlet && (bidx == 0 || info.abb_slot <= bidx)) abb_apply_ax<T, S, LAYOUT, AX>(info.abb_side, rn, jn, g);
     if (bidx != 0) {

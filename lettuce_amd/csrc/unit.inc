@@ -9,9 +9,6 @@
 #include "kernels.hpp"
 #include "twostep_masked.hpp"
 #include "twostep2d.hpp"
-#if LT_EXPERIMENTS
-#include "threestep.hpp"
-#endif
 
 // LT_PART: 0 = the whole unit in one translation unit; 1 = everything but the unmasked 3-D two-step launches
 // (lbm2_kernel), which inst2_<tag>.hip (LT_PART 2) instantiates -- its own object file, so that it builds beside the
@@ -28,7 +25,6 @@ namespace {
 
 using S = LT_S;
 using T = LT_T;
-constexpr int kWide = 16 / sizeof(T);
 // two-step tile: rows of 256 bytes (64 fp32 / 32 fp64 nodes -- narrower rows measured 12-39 % slower) and
 // as many rows (8, else 4) as three planes of all populations leave room for in the 160 KB of LDS:
 // D3Q15 / D3Q19 get 8 rows, D3Q27 fp32 gets 4 (0.63 -> 0.49 ms per update at 256^3); D3Q27 fp64
@@ -41,21 +37,22 @@ constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
 
 #if LT_PART != 2
 
-template <int LAYOUT, int COLL, int MODE, bool MASKED, int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+// one node per thread: the kernels' VEC = 1, SHIFT = 0
+template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
 int launch(const StepArgs &a, bool name_only, const char **name) {
   constexpr bool STREAM = MODE != kCollideOnly, COLLIDE = MODE != kStreamOnly;
   constexpr bool OCC4 = (COLL == 2 && MASKED && sizeof(T) == 4 && S::Q == 27 && ABBD == 0);
   void (*kern)(const KParams<T>);
   if constexpr (OCC4)
-    kern = lbm_kernel_occ4<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, VEC, SHIFT, TUNE, PACK>;
+    kern = lbm_kernel_occ4<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK>;
   else
-    kern = lbm_kernel<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, VEC, SHIFT, TUNE, PACK, ABBD>;
+    kern = lbm_kernel<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK, ABBD>;
   if (name_only) {
     static char buf[160];
-    snprintf(buf, sizeof buf, "%s<%s, lt::%s, %d, %d, %s, %s, %s, %d, %d, %d, %s%s>",
+    snprintf(buf, sizeof buf, "%s<%s, lt::%s, %d, %d, %s, %s, %s, 1, 0, %d, %s%s>",
              OCC4 ? "lbm_kernel_occ4" : "lbm_kernel", sizeof(T) == 4 ? "float" : "double", S::NAME, LAYOUT, COLL,
              STREAM ? "true" : "false", COLLIDE ? "true" : "false", MASKED ? "true" : "false",
-             VEC, SHIFT, TUNE, PACK ? "true" : "false", ABBD == 0 ? "" : (ABBD == 1 ? ", 1" : ", 2"));
+             TUNE, PACK ? "true" : "false", ABBD == 0 ? "" : (ABBD == 1 ? ", 1" : ", 2"));
     *name = buf;
     return 0;
   }
@@ -63,7 +60,7 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   p.in = static_cast<const T *>(a.in);
   p.out = static_cast<T *>(a.out);
   p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
-  p.nv0 = a.n0 / VEC;
+  p.nv0 = a.n0;
   p.p_begin = a.p_begin;
   p.p_stride = a.p_stride;
   p.wrap2 = a.wrap2;
@@ -83,7 +80,7 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   p.pack_hi = static_cast<T *>(a.pack_hi);
   p.pack_lo_plane = a.pack_lo_plane;
   p.pack_hi_plane = a.pack_hi_plane;
-  p.abb0_slot = (VEC == 1 && a.n0 % 64 == 0) ? a.abb0_slot : 0;
+  p.abb0_slot = a.n0 % 64 == 0 ? a.abb0_slot : 0;
   if (p.nvec_total == 0) return 0;
   const unsigned grid = (p.nvec_total + kThreads - 1) / kThreads;
   // a.lds_bytes of dynamic LDS that no kernel touches: caps the workgroups resident per CU
@@ -97,14 +94,15 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
 #if LT_PART != 1
 // Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
 // returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
-template <int LAYOUT, int COLL, int T0, int T1, int NPT = 1, int MODE = 0, int NPB = NPT>
+// one node per thread and per block: the kernel's NPT = NPB = 1
+template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0>
 int launch_twice(const StepArgs &a, bool name_only, const char **name) {
-  if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1 || COLL == 3)) {
+  if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1)) {
     using B = TwoStep<T, S, T0, T1>;
     if (name_only) {
       static char buf[96];
-      snprintf(buf, sizeof buf, "lbm2_kernel<%s, lt::%s, %d, %d, %d, %d, %d, %d, %d>", sizeof(T) == 4 ? "float" : "double",
-               S::NAME, LAYOUT, COLL, T0, T1, NPT, MODE, NPB);
+      snprintf(buf, sizeof buf, "lbm2_kernel<%s, lt::%s, %d, %d, %d, %d, 1, %d, 1>", sizeof(T) == 4 ? "float" : "double",
+               S::NAME, LAYOUT, COLL, T0, T1, MODE);
       *name = buf;
       return 0;
     }
@@ -140,8 +138,8 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
     p.lo = a.interior_begin; p.hi = a.interior_end;
     const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len +
                                                                    (a.planes2 + a.seg_len - 1) / a.seg_len));
-    constexpr int threads = (B::NI / NPT + 63) / 64 * 64;
-    hipLaunchKernelGGL((lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, NPT, MODE, NPB>), dim3(grid), dim3(threads), 0,
+    constexpr int threads = (B::NI + 63) / 64 * 64;
+    hipLaunchKernelGGL((lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1>), dim3(grid), dim3(threads), 0,
                        a.stream, p, a.seg_len);
     return (int)hipGetLastError();
   } else {
@@ -149,89 +147,21 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
-#if LT_EXPERIMENTS
-// Three fused steps per launch (threestep.hpp, lbm3_kernel): whole periodic grid, reference layout, no masks;
-// tiles of kTwiceW x 4 nodes (143 KB of LDS for D3Q19 fp32)
-template <int LAYOUT, int COLL, int T0, int T1>
-int launch_thrice(const StepArgs &a, bool name_only, const char **name) {
-  if constexpr (S::D == 3 && (COLL == 0 || COLL == 1)) {
-    using G = ThreeStep<T, S, T0, T1>;
-    if constexpr (G::template lds_bytes<LAYOUT>() <= 160 * 1024 && G::THREADS <= 1024) {
-      if (name_only) {
-        static char buf[96];
-        snprintf(buf, sizeof buf, "lbm3_kernel<%s, lt::%s, %d, %d, %d, %d>", sizeof(T) == 4 ? "float" : "double", S::NAME,
-                 LAYOUT, COLL, T0, T1);
-        *name = buf;
-        return 0;
-      }
-      if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 1 || a.masked || !a.wrap2 || a.planes < 1 || a.p_stride != 1 ||
-          a.planes2 != 0 || a.pack_lo || a.pack_hi || a.n2 < 3)
-        return kNoKernel;
-      KParams<T> p;
-      memset(&p, 0, sizeof p);
-      p.in = static_cast<const T *>(a.in);
-      p.out = static_cast<T *>(a.out);
-      p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
-      p.wrap2 = 1;
-      p.p_begin = a.p_begin;
-      p.p_end = a.p_begin + a.planes;
-      p.N = (long long)a.n0 * a.n1 * a.n2;
-      p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-      p.No = a.stride_out > 0 ? a.stride_out : p.N;
-      p.tau_inv = (T)(1.0 / a.tau);
-      const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len));
-      hipLaunchKernelGGL((lbm3_kernel<T, S, LAYOUT, COLL, T0, T1>), dim3(grid), dim3(G::THREADS), 0, a.stream, p,
-                         a.seg_len);
-      return (int)hipGetLastError();
-    } else {
-      return kNoKernel;
-    }
-  } else {
-    return kNoKernel;
-  }
-}
-
-#endif  // LT_EXPERIMENTS
-
-// the unmasked 3-D two-step (and three-step) launches of this unit
+// the unmasked 3-D two-step launches of this unit
 int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
   const int coll = a.coll;
   constexpr int W = kTwiceW, R = kTwiceR;
-  if (a.mode == kFusedThrice) {
-#if LT_EXPERIMENTS
-    if (a.layout == 0 && coll == 0) return launch_thrice<0, 0, W, 4>(a, name_only, name);
-    if (a.layout == 0 && coll == 1) return launch_thrice<0, 1, W, 4>(a, name_only, name);
-#endif
-    return kNoKernel;
-  }
   if constexpr (R > 0) {
-#if LT_EXPERIMENTS
-    if constexpr (W == 64 && R == 8) {
-      if (a.layout == 0 && coll == 1 && a.shift == 1)
-        return launch_twice<0, 1, W, R, 2>(a, name_only, name);  // A/B: two nodes per thread
-      if (a.layout == 0 && coll == 1 && a.shift == 2)
-        return launch_twice<0, 1, W, R, 1, 0, 2>(a, name_only, name);  // A/B: two output nodes per thread
-    }
-#endif
     if (a.layout == 0 && coll == 0) return launch_twice<0, 0, W, R>(a, name_only, name);
     if (a.layout == 0 && coll == 1) return launch_twice<0, 1, W, R>(a, name_only, name);
-#if LT_EXPERIMENTS
-    if (a.layout == 0 && coll == 3) return launch_twice<0, 3, W, R>(a, name_only, name);   // BGK, fast arithmetic
-#endif
 #if LT_IS_3D
     if (a.layout == 1 && (a.pack_lo || a.pack_hi)) {     // slab edge launch with fused halo packing
-#if LT_EXPERIMENTS
-      if constexpr (W == 64 && R == 8) {
-        // A/B (shift policy 5): half-width tiles for the edge launch -- 77 KB of LDS, two workgroups per CU
-        if (coll == 1 && a.shift == 5 && a.n0 % 32 == 0) return launch_twice<1, 1, 32, 8, 1, 1>(a, name_only, name);
-      }
-#endif
-      if (coll == 0) return launch_twice<1, 0, W, R, 1, 1>(a, name_only, name);
-      if (coll == 1) return launch_twice<1, 1, W, R, 1, 1>(a, name_only, name);
+      if (coll == 0) return launch_twice<1, 0, W, R, 1>(a, name_only, name);
+      if (coll == 1) return launch_twice<1, 1, W, R, 1>(a, name_only, name);
     }
     if (a.layout == 1 && a.signal) {                     // whole slab, edge workgroups first
-      if (coll == 0) return launch_twice<1, 0, W, R, 1, 2>(a, name_only, name);
-      if (coll == 1) return launch_twice<1, 1, W, R, 1, 2>(a, name_only, name);
+      if (coll == 0) return launch_twice<1, 0, W, R, 2>(a, name_only, name);
+      if (coll == 1) return launch_twice<1, 1, W, R, 2>(a, name_only, name);
     }
     if (a.layout == 1 && coll == 0) return launch_twice<1, 0, W, R>(a, name_only, name);
     if (a.layout == 1 && coll == 1) return launch_twice<1, 1, W, R>(a, name_only, name);
@@ -248,12 +178,10 @@ int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
 // the instantiation with a descriptor per population) and three LDS slots of the downward populations fit.
 template <int LAYOUT, int COLL, int T0, int T1, int AX = 2>
 int launch_twice_masked(const StepArgs &a, bool name_only, const char **name) {
-  // product build: BGK / streaming on tiles of 8 rows (4 for D3Q27 fp32).  KBC inside this kernel (256 VGPRs, spills:
-  // not faster than one update per launch) and the 4-row fp64 tiles of D3Q19 (slower than one update per launch) are
-  // experiments (LT_EXPERIMENTS; DESIGN.md section 4)
-  constexpr bool kFourRowDouble = sizeof(T) == 8 && T1 == 4;
-  if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1 || (COLL == 2 && LT_HAS_KBC && sizeof(T) == 4 && LT_EXPERIMENTS))
-                && (!kFourRowDouble || LT_EXPERIMENTS)) {
+  // BGK / streaming on tiles of 8 rows (4 for D3Q27 fp32).  KBC inside this kernel (256 VGPRs, spills: not faster
+  // than one update per launch) and 4-row fp64 tiles of D3Q19 (slower than one update per launch) lost their A/B
+  // (DESIGN.md section 4)
+  if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1) && !(sizeof(T) == 8 && T1 == 4)) {
     if constexpr (two_step_masked_lds<T, S, LAYOUT, T0, T1>() <= 160 * 1024) {
       using B = TwoStep<T, S, T0, T1>;
       if (name_only) {
@@ -284,9 +212,6 @@ int launch_twice_masked(const StepArgs &a, bool name_only, const char **name) {
       p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
       p.No = a.stride_out > 0 ? a.stride_out : p.N;
       p.tau_inv = (T)(1.0 / a.tau);
-      const double beta = 1. / (2 * a.tau);          // kbc_collision.py:97-99
-      p.beta = (T)beta;
-      p.inv_beta = (T)(1. / beta);
       p.node = a.node;
       p.nsm_bits = a.nsm_bits;
       p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
@@ -419,72 +344,33 @@ int launch_many(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
-#if LT_EXPERIMENTS
-// Two steps per launch on small 3-D grids (kernels.hpp, lbm_many3d_kernel): reference layout, no masks, BGK or
-// streaming only; the populations of the 10^3 neighbourhood must fit the LDS (D3Q27 fp64 does not)
-template <int COLL>
-int launch_many3d(const StepArgs &a, bool name_only, const char **name) {
-  if constexpr (S::D == 3 && (COLL == 0 || COLL == 1) && sizeof(T) * S::Q * kMany3dNodes <= 160 * 1024) {
-    if (name_only) {
-      static char buf[96];
-      snprintf(buf, sizeof buf, "lbm_many3d_kernel<%s, lt::%s, %d>", sizeof(T) == 4 ? "float" : "double", S::NAME, COLL);
-      *name = buf;
-      return 0;
-    }
-    if (a.layout != 0 || a.masked || a.n0 % kMany3dTile != 0 || a.n1 % kMany3dTile != 0 || a.n2 % kMany3dTile != 0 ||
-        a.seg_len != 2 || a.planes != a.n2)
-      return kNoKernel;
-    KParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.in = static_cast<const T *>(a.in);
-    p.out = static_cast<T *>(a.out);
-    p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
-    p.N = (long long)a.n0 * a.n1 * a.n2;
-    p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-    p.No = a.stride_out > 0 ? a.stride_out : p.N;
-    p.tau_inv = (T)(1.0 / a.tau);
-    const unsigned grid = (unsigned)((a.n0 / kMany3dTile) * (a.n1 / kMany3dTile) * (a.n2 / kMany3dTile));
-    hipLaunchKernelGGL((lbm_many3d_kernel<T, S, COLL>), dim3(grid), dim3(1024), 0, a.stream, p);
-    return (int)hipGetLastError();
-  } else {
-    return kNoKernel;
-  }
-}
-
-#endif  // LT_EXPERIMENTS
 // Product kernels: one node per thread (VEC = 1).  Measured on MI355X (profiles/r01_variant_sweep*):
 // for this 2q-stream kernel 8 waves/SIMD of scalar accesses beat 16-byte accesses at 3-4
 // waves/SIMD by 8-13 %, and nontemporal stores (+3-4 %) and loads (+1.6 %) help once the
 // populations exceed the caches (TUNE 3).  TUNE 0 (cached accesses) is kept for grids that fit in
 // L2 / Infinity Cache.
 #define LT_TRY(LAYOUT, COLL, MODE, MASKED)                                                       \
-  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked == MASKED && !a.wide) {  \
-    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 1, 0, 0>(a, name_only, name); \
-    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 1, 0, 3>(a, name_only, name); \
+  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked == MASKED) {            \
+    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 0>(a, name_only, name); \
+    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 3>(a, name_only, name); \
   }
-// A/B variants of the hot kernel (fused, BGK, unmasked) with 16-byte accesses: SHIFT selects how
-// the +-1 shift along the contiguous axis is resolved (kernels.hpp, gather)
-#define LT_TRY_WIDE(LAYOUT, SHIFT, TUNE)                                                        \
-  if (a.layout == LAYOUT && coll == 1 && a.mode == kFused && a.masked == 0 && a.wide == 1 &&    \
-      a.shift == SHIFT && a.tune == TUNE)                                                       \
-    return launch<LAYOUT, 1, kFused, false, kWide, SHIFT, TUNE>(a, name_only, name);
 
 // slab boundary-plane launch with fused halo packing (fused mode, slab layout)
 #define LT_TRY_PACK(COLL, MASKED)                                                               \
-  if (a.layout == 1 && coll == COLL && a.mode == kFused && a.masked == MASKED && !a.wide &&      \
+  if (a.layout == 1 && coll == COLL && a.mode == kFused && a.masked == MASKED &&                 \
       a.pack_lo != nullptr && a.abb_depth == 0)                                                                      \
-    return launch<1, COLL, kFused, (MASKED != 0), 1, 0, 0, true>(a, name_only, name);
+    return launch<1, COLL, kFused, (MASKED != 0), 0, true>(a, name_only, name);
 
 // plans with two anti-bounce-back outlets (kernels.hpp, neighbour_moments DEPTH 1): masked kernels that
 // apply boundaries, i.e. fused and collide-only
 #define LT_TRY_TWO_OUTLETS(LAYOUT, COLL, MODE)                                                  \
-  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked && !a.wide && a.abb_depth == 1) \
-    return launch<LAYOUT, COLL, MODE, true, 1, 0, 0, false, 1>(a, name_only, name);
+  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 1) \
+    return launch<LAYOUT, COLL, MODE, true, 0, false, 1>(a, name_only, name);
 
 // outlets on all three axes of a 3-D flow (their planes meet in corners: DEPTH 2), reference layout
 #define LT_TRY_THREE_AXES(COLL, MODE)                                                           \
-  if (a.layout == 0 && coll == COLL && a.mode == MODE && a.masked && !a.wide && a.abb_depth == 2) \
-    return launch<0, COLL, MODE, true, 1, 0, 0, false, 2>(a, name_only, name);
+  if (a.layout == 0 && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 2) \
+    return launch<0, COLL, MODE, true, 0, false, 2>(a, name_only, name);
 
 #define LT_COLLISION_SET(LAYOUT, COLL, MASKED) \
   LT_TRY(LAYOUT, COLL, kFused, MASKED)         \
@@ -492,13 +378,6 @@ int launch_many3d(const StepArgs &a, bool name_only, const char **name) {
 
 int dispatch(const StepArgs &a, bool name_only, const char **name) {
   const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
-  if (a.mode == kFusedMany && S::D == 3) {
-#if LT_EXPERIMENTS
-    if (coll == 0) return launch_many3d<0>(a, name_only, name);
-    if (coll == 1) return launch_many3d<1>(a, name_only, name);
-#endif
-    return kNoKernel;
-  }
   if (a.mode == kFusedMany) {
     if (a.masked) {
       if (coll == 0) return launch_many<0, true>(a, name_only, name);
@@ -510,18 +389,6 @@ int dispatch(const StepArgs &a, bool name_only, const char **name) {
     if (coll == 1) return launch_many<1, false>(a, name_only, name);
     if (coll == 2) return launch_many<2, false>(a, name_only, name);
     return kNoKernel;
-  }
-  if (a.mode == kFusedThrice) {
-#if LT_IS_3D
-    if (a.masked) return kNoKernel;
-#if LT_PART == 1
-    return LT_CAT(twice_, LT_TAG)(a, name_only, name);        // inst2_<tag>.hip
-#else
-    return twice_unmasked(a, name_only, name);
-#endif
-#else
-    return kNoKernel;
-#endif
   }
   if (a.mode == kFusedTwice && S::D == 2) {
     // strips of a.wide2d columns (api.hip: the widest of 512 / 256 / 128 / 64 that divides the contiguous extent)
@@ -551,9 +418,6 @@ int dispatch(const StepArgs &a, bool name_only, const char **name) {
     return launch_twice_masked<LAYOUT_, COLL_, W, RM, AX_>(a, name_only, name);
         LT_TRY_MASKED_TWICE(0, 0, 2) LT_TRY_MASKED_TWICE(0, 1, 2)
         LT_TRY_MASKED_TWICE(0, 0, 0) LT_TRY_MASKED_TWICE(0, 1, 0)
-#if LT_HAS_KBC && LT_IS_3D && LT_EXPERIMENTS
-        LT_TRY_MASKED_TWICE(0, 2, 2)                 // KBC (D3Q27 fp32): the Obstacle in the reference layout (cfg4)
-#endif
 #if LT_IS_3D
         LT_TRY_MASKED_TWICE(1, 0, 2) LT_TRY_MASKED_TWICE(1, 1, 2)
         LT_TRY_MASKED_TWICE(1, 0, 0) LT_TRY_MASKED_TWICE(1, 1, 0)
@@ -598,18 +462,8 @@ int dispatch(const StepArgs &a, bool name_only, const char **name) {
   LT_COLLISION_SET(0, 2, 0)
   LT_COLLISION_SET(0, 2, 1)
 #endif
-#if LT_IS_3D && LT_EXPERIMENTS
-  LT_COLLISION_SET(0, 3, 0)                        // BGK in fast arithmetic: periodic 3-D plans, reference layout
-#endif
   LT_TRY(0, 0, kStreamOnly, 0)
   LT_TRY(0, 0, kStreamOnly, 1)
-#if LT_EXPERIMENTS                                  // 16-byte variants of the hot kernel: 8-13 % slower (round 1)
-  LT_TRY_WIDE(0, 0, 0)
-  LT_TRY_WIDE(0, 1, 0)
-  LT_TRY_WIDE(0, 2, 0)
-  LT_TRY_WIDE(0, 0, 2)
-  LT_TRY_WIDE(0, 2, 3)
-#endif
 #if LT_IS_3D
   // slab layout (multi-GPU z-slabs)
   LT_TRY_PACK(0, 0)
@@ -630,10 +484,6 @@ int dispatch(const StepArgs &a, bool name_only, const char **name) {
 #endif
   LT_TRY(1, 0, kStreamOnly, 0)
   LT_TRY(1, 0, kStreamOnly, 1)
-#if LT_EXPERIMENTS
-  LT_TRY_WIDE(1, 0, 0)
-  LT_TRY_WIDE(1, 2, 3)
-#endif
 #endif
   return kNoKernel;
 }

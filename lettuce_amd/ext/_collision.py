@@ -34,8 +34,8 @@ class BGKCollision(Collision):
     """f - (f - feq(rho, u)) / tau (lettuce/ext/_collision/bgk_collision.py:12-35).
 
     ``arithmetic`` (an attribute, not part of the reference's signature): "exact" (default) -- the HIP engine reproduces
-    the reference's floating-point operations one for one; "fast" -- its shorter collision, equal to rounding level
-    (periodic 3-D flows; ``Simulation`` raises where the engine has no such kernel)."""
+    the reference's floating-point operations one for one.  Anything else (the former "fast") makes ``Simulation``
+    raise: the engine has no such kernel."""
     arithmetic = "exact"
 
     def __init__(self, tau, force: Optional["Force"] = None):

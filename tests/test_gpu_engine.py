@@ -246,14 +246,6 @@ def test_fused_equals_collide_then_stream_and_ab_variants_agree():
             c = torch.empty_like(f)
             plan.stream_collide(f, c, tau)
             assert torch.equal(c, b)
-        from conftest import experiments_built
-        for shift, cache in ((0, 0), (1, 0), (2, 0), (0, 2), (2, 3)) if experiments_built() else ():
-            plan.set_tuning(cache, True)
-            plan.set_shift_policy(shift)
-            assert plan.kernel_info()["vec"] == 16 // f.element_size()
-            c = torch.empty_like(f)
-            plan.stream_collide(f, c, tau)
-            torch.testing.assert_close(c, b, rtol=0, atol=tol)
 
 
 OBSERVED = [("tgv2d_d2q9_bgk_32_f64", "D2Q9", "f64", (0, 10, 100)), ("tgv2d_d2q9_bgk_32_f32", "D2Q9", "f32", (0, 10)),
@@ -599,10 +591,7 @@ def _masked_case(lat, res, dtype, abb, seed, with_field=False, abb_first=False, 
 MASKED_TWO_STEP = [("D3Q19", [8, 16, 64], "f32", (0, 1)), ("D3Q19", [8, 16, 64], "f32", (0, -1)), ("D3Q19", [6, 8, 128], "f32", (1, 1)),
                    ("D3Q19", [6, 16, 64], "f32", (0, 1)), ("D3Q19", [7, 8, 64], "f32", (0, 1)), ("D3Q19", [4, 8, 64], "f32", (2, -1)),
                    ("D3Q19", [5, 8, 64], "f32", None), ("D3Q27", [6, 8, 64], "f32", (0, 1)), ("D3Q27", [5, 4, 64], "f32", None),
-                   ("D3Q15", [6, 8, 64], "f32", (0, 1)), ("D3Q15", [6, 8, 32], "f64", (0, 1)), ("D3Q15", [5, 8, 32], "f64", None),
-                   # round 3: D3Q19 fp64 with boundaries on 32 x 4 tiles (8 rows need 168.6 KB of LDS with the third
-                   # slot of the downward populations)
-                   pytest.param(*("D3Q19", [6, 8, 32], "f64", (0, 1)), marks=pytest.mark.experiments), pytest.param(*("D3Q19", [5, 4, 64], "f64", None), marks=pytest.mark.experiments), pytest.param(*("D3Q19", [4, 12, 32], "f64", (0, 1)), marks=pytest.mark.experiments)]
+                   ("D3Q15", [6, 8, 64], "f32", (0, 1)), ("D3Q15", [6, 8, 32], "f64", (0, 1)), ("D3Q15", [5, 8, 32], "f64", None)]
 
 
 @pytest.mark.parametrize("lat,res,dt,abb", MASKED_TWO_STEP, ids=[f"{t[0]}-{'x'.join(map(str, t[1]))}-{t[2]}-{t[3]}" for t in map(_values, MASKED_TWO_STEP)])
@@ -623,8 +612,7 @@ def test_masked_two_step_launch_is_bit_identical_to_two_masked_single_steps(lat,
 
 MASKED_TWO_STEP_ROWS = [("D3Q19", [4, 8, 64], "f32", (2, 1)), ("D3Q19", [4, 8, 64], "f32", (2, -1)), ("D3Q19", [5, 16, 128], "f32", (2, 1)),
                         ("D3Q19", [6, 16, 128], "f32", (2, -1)), ("D3Q27", [5, 4, 64], "f32", (2, 1)), ("D3Q27", [4, 8, 128], "f32", (2, -1)),
-                        ("D3Q15", [5, 8, 64], "f32", (2, 1)), ("D3Q15", [5, 8, 32], "f64", (2, 1)), ("D3Q15", [4, 16, 64], "f64", (2, -1)),
-                        pytest.param(*("D3Q19", [5, 8, 32], "f64", (2, 1)), marks=pytest.mark.experiments), pytest.param(*("D3Q19", [4, 4, 64], "f64", (2, -1)), marks=pytest.mark.experiments)]
+                        ("D3Q15", [5, 8, 64], "f32", (2, 1)), ("D3Q15", [5, 8, 32], "f64", (2, 1)), ("D3Q15", [4, 16, 64], "f64", (2, -1))]
 
 
 @pytest.mark.parametrize("lat,res,dt,abb", MASKED_TWO_STEP_ROWS, ids=[f"{t[0]}-{'x'.join(map(str, t[1]))}-{t[2]}-{t[3]}" for t in map(_values, MASKED_TWO_STEP_ROWS)])
@@ -734,7 +722,7 @@ def _masked_slab_case(lat, res, dtype, outlet, seed, with_field=False, abb_first
 
 
 MASKED_SLAB = [("D3Q19", [64, 16, 10], "f32"), ("D3Q27", [64, 8, 9], "f32"), ("D3Q15", [128, 8, 8], "f32"),
-               ("D3Q15", [32, 16, 7], "f64"), pytest.param(*("D3Q19", [32, 8, 8], "f64"), marks=pytest.mark.experiments)]
+               ("D3Q15", [32, 16, 7], "f64")]
 
 
 @pytest.mark.parametrize("lat,res,dt", MASKED_SLAB, ids=[f"{t[0]}-{'x'.join(map(str, t[1]))}-{t[2]}" for t in map(_values, MASKED_SLAB)])
@@ -985,71 +973,32 @@ def test_kbc_kernels_agree_bit_for_bit(lat, res, dt):
             assert torch.equal(out, a)
 
 
-# --------------------------------------------------------------------------- BGK in fast arithmetic (opt-in)
-FAST = [("tgv3d_d3q19_bgk_16_f32", "D3Q19", "f32"), ("tgv3d_d3q19_bgk_32_f32", "D3Q19", "f32"),
-        ("tgv3d_d3q19_bgk_16_f64", "D3Q19", "f64"), ("tgv3d_d3q27_bgk_16_f64", "D3Q27", "f64")]
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize("name,lat,dt", FAST, ids=[t[0] for t in FAST])
-def test_fast_arithmetic_bgk_stays_inside_the_stated_tolerances(name, lat, dt):
-    """lt_plan_set_arithmetic(plan, 1): the shorter BGK collision (one reciprocal of rho, cs^2 = 1/3, contracted
-    multiply-adds, moments over opposite pairs) against the reference's own vectors, with the tolerances of SURVEY.md
-    8(d): fp32 max |df| <= 1e-5 max |f| after 10 steps and the kinetic energy to 5e-5 over 100 steps (the
-    reference's own fp32 / fp64 gap is 1.3e-5 at step 100); fp64 1e-12 after 100 steps, energy 1e-9.  The 1e-6 over
-    10 steps is MISSED: 1.0-1.5e-6, depending on the build -- the reference's fp32 energy carries a drift of -1.1e-7
-    per step from its rounded divisors, the fast form reproduces it only statistically (u = RN(j / rho (1 - 3e-8))
-    inside one FMA) and v_rcp_f32's last bit moves the momentum by as much (a 1-ulp bias of the reciprocal is 3e-6 of
-    energy after 10 steps in a host-side emulation).  One of the two reasons the arithmetic is not in the product
-    library; asserted here at 2e-6."""
-    g = golden(name)
-    res = list(g["f0"].shape[1:])
-    plan = plan_for(lat, TORCH_DT[dt], "bgk", res)
-    plan.set_arithmetic("fast")
-    assert ", 3, " in plan.kernel_name()
-    scale = float(np.abs(g["f0"]).max())
-    f10 = run_engine(plan, g["f0"], float(g["tau"]), 10)
-    assert np.abs(f10 - g["f10"]).max() <= (1e-5 if dt == "f32" else 1e-13) * scale
-    if "f100" in g:
-        f100 = run_engine(plan, g["f0"], float(g["tau"]), 100)
-        assert np.abs(f100 - g["f100"]).max() <= (1e-4 if dt == "f32" else 1e-12) * scale
-    units = orc.tgv_units(res, float(g["reynolds"]), float(g["mach"]))
-    to_pu = units.incompressible_energy_to_pu(1.0) * units.length_to_pu(1.0) ** 3
-    cur, other = dev(g["f0"]), torch.empty_like(dev(g["f0"]))
-    done = 0
-    for step, want in zip(g["energy_steps"].tolist(), g["energy_pu"].tolist()):
-        if step > done:
-            cur, other = plan.run(cur, other, float(g["tau"]), step - done)
-            done = step
-        got = float(plan.kinetic_energy_lu(cur).cpu()) * to_pu
-        tol = (2e-6 if step <= 10 else 5e-5) if dt == "f32" else 1e-9
-        assert got == pytest.approx(want, rel=tol), (step, got, want)
-
-
-@pytest.mark.experiments
-def test_fast_arithmetic_in_the_two_step_kernel_and_where_it_is_refused():
-    """the same arithmetic in lbm2_kernel<..., 3, ...> (two updates per launch): equal to the one-step kernel in fast
-    arithmetic bit for bit, within tolerance of the reference's vectors; plans with boundaries, KBC and 2-D plans
-    have no such kernel and say so."""
+# --------------------------------------------------------------------------- variants that lost their A/B
+def test_removed_kernel_variants_are_refused():
+    """16-byte one-step accesses, the tile variants of shift policies 1 / 2 / 5 and fast arithmetic were removed
+    (DESIGN.md section 4): asking for them fails as it did in the product library before, and a 3-D plan asked for
+    many steps per launch still runs one or two steps per launch."""
+    import lettuce_amd as lt
     from lettuce_amd._native import NativeEngineError
-    g = golden("tgv3d_d3q19_bgk_8x16x64_f32")
-    res = list(g["f0"].shape[1:])
-    one = plan_for("D3Q19", torch.float32, "bgk", res)
-    one.set_arithmetic("fast"); one.set_two_step(0)
-    two = plan_for("D3Q19", torch.float32, "bgk", res)
-    two.set_arithmetic(1); two.set_two_step(1)
-    a, b = run_engine(one, g["f0"], float(g["tau"]), 10), run_engine(two, g["f0"], float(g["tau"]), 10)
-    assert two.last_run_info()["two_step_launches"] == 4 and "lbm2_kernel" in two.kernel_name() and ", 3, " in two.kernel_name()
-    np.testing.assert_array_equal(a, b)
-    assert np.abs(b - g["f10"]).max() <= 1e-5 * float(np.abs(g["f10"]).max())
-    assert not np.array_equal(b, g["f10"])                     # rounding level, not bit for bit: why it is opt-in
-    two.set_arithmetic("exact")
-    np.testing.assert_array_equal(run_engine(two, g["f0"], float(g["tau"]), 10), g["f10"])
-    for lat, coll, shape, entries in (("D3Q27", "kbc", [8, 8, 8], []), ("D2Q9", "bgk", [16, 16], []),
-                                      ("D3Q19", "bgk", [8, 8, 8], [{"kind": "bounce_back"}])):
-        plan = plan_for(lat, torch.float32, coll, shape, entries)
-        with pytest.raises(NativeEngineError, match="fast arithmetic"):
-            plan.set_arithmetic("fast")
+    plan = plan_for("D3Q19", torch.float32, "bgk", [64, 8, 8])
+    for call in (lambda: plan.set_tuning(0, True), lambda: plan.set_shift_policy(1), lambda: plan.set_shift_policy(2),
+                 lambda: plan.set_shift_policy(5)):
+        with pytest.raises(NativeEngineError) as err:
+            call()
+        assert err.value.code == 2, err.value.code                  # LT_ERR_UNSUPPORTED
+    g = golden("tgv3d_d3q19_bgk_16_f32")
+    plan = plan_for("D3Q19", torch.float32, "bgk", g["f0"].shape[1:])
+    plan.set_many_step(1)
+    assert "lbm_many" not in plan.kernel_name()
+    np.testing.assert_array_equal(run_engine(plan, g["f0"], float(g["tau"]), 10), g["f10"])
+    info = plan.last_run_info()
+    assert info["many_step_launches"] == 0 and info["single_step_launches"] + 2 * info["two_step_launches"] == 9, info
+    collision = lt.BGKCollision(tau=0.8)
+    collision.arithmetic = "fast"
+    flow = lt.TaylorGreenVortex(lt.Context(device=torch.device("cuda"), dtype=torch.float32, use_native=True),
+                                resolution=[16, 16, 16], reynolds_number=100, mach_number=0.05, stencil=lt.D3Q19())
+    with pytest.raises(NativeEngineError, match="arithmetic"):
+        lt.Simulation(flow, collision, [])
 
 
 # --------------------------------------------------------------------------- two steps per launch
@@ -1551,107 +1500,6 @@ def test_direct_edge_launch_reads_the_received_messages_and_writes_the_outgoing_
     assert torch.equal(got2[:, 2:2 + edge], want[:, 2:2 + edge]) and torch.equal(got_down, want_down)
     with pytest.raises(Exception, match="both received messages or"):
         plan.stream_collide_twice_edges_direct(f, got, 0.7, edge, from_below, None, got_down, got_up)
-
-
-# --------------------------------------------------------------------------- round 3: two steps per launch, small 3-D grids
-@pytest.mark.experiments
-@pytest.mark.parametrize("lat,dt", [("D3Q19", "f32"), ("D3Q19", "f64"), ("D3Q27", "f32"), ("D3Q15", "f32"), ("D3Q15", "f64")])
-@pytest.mark.parametrize("res", [[8, 8, 8], [16, 8, 24], [32, 32, 32], [40, 16, 8]])
-@pytest.mark.parametrize("coll", ["bgk", "none"])
-def test_two_steps_per_launch_on_small_3d_grids_equal_single_steps(lat, dt, res, coll):
-    """lbm_many3d_kernel: the 10^3 neighbourhood of an 8^3 tile in LDS, two stream-collide steps
-    per launch: bit for bit two launches of the one-step kernel, incl. grids smaller than the neighbourhood (8^3:
-    every neighbour is a periodic image of the tile itself) and ragged tile counts."""
-    T = TORCH_DT[dt]
-    L = orc.LATTICES[lat]
-    plan = plan_for(lat, T, coll, res)
-    torch.manual_seed(7)
-    w = torch.rand(L.q, 1, 1, 1, device="cuda", dtype=T) * 0.03 + 0.02
-    f = (w * (1 + 0.05 * torch.rand([L.q] + res, device="cuda", dtype=T))).contiguous()
-    a, b, c = torch.empty_like(f), torch.empty_like(f), torch.empty_like(f)
-    plan.stream_collide(f, a, 0.7)
-    plan.stream_collide(a, b, 0.7)
-    plan.stream_collide_many(f, c, 0.7, 2)
-    assert torch.equal(b, c)
-    with pytest.raises(Exception, match="no kernel|n_steps"):
-        plan.stream_collide_many(f, c, 0.7, 3)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize("lat,dt", [("D3Q19", "f32"), ("D3Q19", "f64"), ("D3Q15", "f32")])
-@pytest.mark.parametrize("res,planes", [([8, 8, 64], 0), ([6, 12, 128], 0), ([16, 16, 64], 4), ([5, 4, 64], 1), ([64, 64, 128], 0)])
-@pytest.mark.parametrize("coll", ["bgk", "none"])
-def test_three_steps_per_launch_equal_three_single_steps(lat, dt, res, planes, coll):
-    """lbm3_kernel (round 3, threestep.hpp): three stream-collide steps per launch with BOTH intermediate states in LDS
-    (tiles of 64 / 32 x 4 nodes and their one- and two-node halos, sixteen waves with one phase -- or two -- each, two
-    barriers per plane): bit for bit three launches of the one-step kernel, for every segment length, on grids whose
-    halos wrap around onto the tile itself.  (Opt-in entry point: measured slower per update than two steps per
-    launch)"""
-    T = TORCH_DT[dt]
-    L = orc.LATTICES[lat]
-    if dt == "f64":
-        res = [res[0], res[1], max(32, res[2] // 2)]
-    plan = plan_for(lat, T, coll, res)
-    plan.set_two_step(1, planes)
-    torch.manual_seed(11)
-    w = torch.rand(L.q, 1, 1, 1, device="cuda", dtype=T) * 0.03 + 0.02
-    f = (w * (1 + 0.05 * torch.rand([L.q] + res, device="cuda", dtype=T))).contiguous()
-    a, b = f.clone(), torch.empty_like(f)
-    for _ in range(3):
-        plan.stream_collide(a, b, 0.7)
-        a, b = b, a
-    out = torch.empty_like(f)
-    plan.stream_collide_thrice(f, out, 0.7)
-    assert torch.equal(out, a)
-
-
-@pytest.mark.experiments
-def test_three_steps_per_launch_reproduce_the_reference_vectors():
-    """... and chained: 3 x 3 steps through lbm3_kernel after the collide-only launch, then the streaming pass, against
-    the reference's populations after 10 steps (periodic BGK: bit for bit)."""
-    g = golden("tgv3d_d3q19_bgk_8x16x64_f32")
-    plan = plan_for("D3Q19", torch.float32, "bgk", g["f0"].shape[1:])
-    tau = float(g["tau"])
-    a = torch.tensor(g["f0"], device="cuda")
-    b = torch.empty_like(a)
-    plan.collide(a, b, tau)
-    for _ in range(3):
-        plan.stream_collide_thrice(b, a, tau)
-        a, b = b, a
-    plan.stream(b, a)
-    np.testing.assert_array_equal(a.cpu().numpy(), g["f10"])
-
-
-@pytest.mark.experiments
-def test_three_steps_per_launch_are_refused_where_they_do_not_apply():
-    plan = plan_for("D3Q27", torch.float32, "bgk", [64, 8, 8])        # two levels of D3Q27 do not fit the LDS
-    f = torch.rand(plan.f_shape, device="cuda") * 0.01 + 0.03
-    with pytest.raises(Exception, match="no kernel"):
-        plan.stream_collide_thrice(f, torch.empty_like(f), 0.7)
-    plan = plan_for("D3Q19", torch.float32, "bgk", [8, 6, 64])        # middle extent % 4
-    f = torch.rand(plan.f_shape, device="cuda") * 0.01 + 0.03
-    with pytest.raises(Exception, match="no kernel"):
-        plan.stream_collide_thrice(f, torch.empty_like(f), 0.7)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize("name,dt,n", [("tgv3d_d3q19_bgk_32_f32", "f32", 10), ("tgv3d_d3q19_bgk_16_f64", "f64", 100)])
-def test_small_3d_grids_run_two_steps_per_launch_and_reproduce_the_reference(name, dt, n):
-    """lt_run on a launch-bound 3-D grid with lt_plan_set_many_step(plan, 1) pairs its fused steps into
-    lbm_many3d_kernel launches and returns the reference's populations bit for bit (periodic BGK), for odd and even
-    step counts.  (Not automatic: measured slower than one launch per step, api.hip many_step_wanted.)"""
-    g = golden(name)
-    plan = plan_for("D3Q19", TORCH_DT[dt], "bgk", g["f0"].shape[1:])
-    assert "lbm_many3d_kernel" not in plan.kernel_name()
-    plan.set_many_step(1)
-    assert "lbm_many3d_kernel" in plan.kernel_name()
-    np.testing.assert_array_equal(run_engine(plan, g["f0"], float(g["tau"]), n), g[f"f{n}"])
-    info = plan.last_run_info()
-    assert info["many_step_launches"] == (n - 1) // 2 and info["single_step_launches"] == (n - 1) % 2 and info["two_step_launches"] == 0, info
-    np.testing.assert_array_equal(run_engine(plan, g["f0"], float(g["tau"]), n - 1 if f"f{n - 1}" in g else n), g[f"f{n - 1}"] if f"f{n - 1}" in g else g[f"f{n}"])
-    plan.set_many_step(0)
-    assert "lbm_many3d_kernel" not in plan.kernel_name()
-    np.testing.assert_array_equal(run_engine(plan, g["f0"], float(g["tau"]), n), g[f"f{n}"])
 
 
 @pytest.mark.parametrize("name,lat,dt,snaps", MASKED_GOLDEN[:2], ids=[t[0] for t in MASKED_GOLDEN[:2]])

@@ -35,8 +35,6 @@ def plan_from(path):
         plan.set_population_stride(-(-(384 * 384 * 96 + 32832) // 64) * 64)
         return plan
     plan = nat.Plan("D3Q19", torch.float32, "bgk", [256, 256, 256], [], device=dev)
-    if os.environ.get("LT_AB_ARITH"):                # "fast": A/B of variants of the fast BGK arithmetic
-        plan.set_arithmetic(os.environ["LT_AB_ARITH"])
     plan.set_two_step(1, 0)
     plan.set_population_stride(-(-(256 ** 3 + 32832) // 64) * 64)
     return plan

@@ -1,5 +1,6 @@
 """Launch-bound grids through lt.Simulation: microseconds per step with one step per launch and with the
-several-steps-per-launch kernels (2-D: up to 8, lbm_many_kernel; 3-D: 2, lbm_many3d_kernel; round 3)."""
+several-steps-per-launch kernel (2-D: up to 8, lbm_many_kernel).  3-D grids have none: the round-3 kernel with two
+steps per launch lost its A/B and was removed, so both modes run the same launches there."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
