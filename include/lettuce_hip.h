@@ -122,7 +122,14 @@ int lt_plan_set_masks(lt_plan *plan, const uint8_t *no_collision_mask_dev,
                       const uint8_t *no_streaming_mask_dev, void *stream);
 
 /* Replace boundary i's parameters (e.g. inlet velocity changed between calls; the reference
- * re-reads them every step, cuda_native/ext/_boundary/equilibrium_pu.py:40-48). */
+ * re-reads them every step, cuda_native/ext/_boundary/equilibrium_pu.py:40-48).  The kind cannot
+ * change.  The new descriptor is checked as lt_plan_create checks it (outlet axis and side); a
+ * refused update leaves the plan unchanged.  When an outlet moves (axis, side or flags) the
+ * admission of the masked two-step kernels is decided again for the new outlet, on the masks the
+ * last lt_plan_set_masks compiled (its no-streaming bits were those of the old outlet: a plan whose
+ * masks no longer match keeps the one-step kernel until lt_plan_set_masks is called with new ones),
+ * and the first-use check (lt_plan_set_canary) runs again; so it does when an equilibrium boundary
+ * switches between a constant feq and a per-node field. */
 int lt_plan_update_boundary(lt_plan *plan, int32_t index, const lt_boundary_desc *desc,
                             void *stream);
 

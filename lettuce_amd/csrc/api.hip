@@ -958,6 +958,57 @@ int aux(lt_plan *p, int what, const void *f, void *rho, void *u, double *out, vo
   return LT_OK;
 }
 
+// The admission tests of the masked two-step kernels (compile_masks_kernel) for the plan's present boundary table:
+// the only no-streaming bits the two-step kernel can take are those of ONE outlet at the last plane of the slowest
+// memory axis or at an end of the rows -- the populations entering through it, on every node of it
+struct MaskCheck {
+  int axis = -1, plane = -1, face = -1;
+  unsigned expected = 0, eq_slots = 0;
+  long long plane_nodes = 0;
+};
+MaskCheck mask_check_of(const lt_plan *p) {
+  MaskCheck c;
+  int outlets = 0;
+  const int sweep = p->unit.d == 2 ? 1 : 2;          // the slowest memory axis: rows in 2-D, planes in 3-D
+  c.plane_nodes = sweep == 1 ? (long long)p->n0 : (long long)p->n0 * p->n1;
+  for (int i = 0; i < p->desc.n_boundaries; ++i) {
+    const lt_boundary_desc &b = p->desc.boundaries[i];
+    if (b.kind == LT_BOUNDARY_EQUILIBRIUM && i + 1 < 32) c.eq_slots |= 1u << (i + 1);   // (only read for plans the two-step kernels admit: <= 15 boundaries)
+    if (b.kind != LT_BOUNDARY_ABB_OUTLET || (b.flags & LT_BOUNDARY_ABSENT)) continue;
+    ++outlets;
+    const int ax = mem_axis_of(p, b.axis);
+    if ((ax == sweep && b.side == 1) || (ax == 0 && p->unit.d == 3)) {
+      c.axis = ax == sweep ? 2 : 0;                  // compile_masks_kernel: 2 = "index / plane_nodes", 0 = a0 column
+      c.plane = ax == sweep ? (sweep == 2 ? p->n2 : p->n1) - 1 - p->desc.ghost_planes : (b.side == 1 ? p->n0 - 1 : 0);
+      if (ax == 0) c.face = b.side == 1 ? 0 : p->n0 - 1;
+      const lt::QList in = crossing_axis(p, ax, -b.side);
+      for (int k = 0; k < in.n; ++k) c.expected |= 1u << in.q[k];
+    }
+  }
+  if (outlets != 1) { c.axis = -1; c.plane = -1; c.face = -1; c.expected = 0; }
+  return c;
+}
+
+// reads the mismatch bits of a compile / recheck launch on `hs` into the plan's admission flags
+int store_admission(lt_plan *p, hipStream_t hs) {
+  unsigned flags = 0;
+  LT_HIP(hipMemcpyAsync(&flags, p->mask_flag, sizeof flags, hipMemcpyDeviceToHost, hs));
+  LT_HIP(hipStreamSynchronize(hs));
+  p->nsm_confined = (flags & 1u) == 0;
+  p->inlet_faces_outlet = (flags & 2u) == 0;
+  return LT_OK;
+}
+
+// the outlets' axes decide how deep an outlet's neighbour must be rebuilt (see lt_plan_create); -1: unsupported
+int abb_depth_of(const lt_plan_desc &d) {
+  int n_abb = 0, axes = 0;
+  for (int i = 0; i < d.n_boundaries; ++i)
+    if (d.boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET) { ++n_abb; axes |= 1 << d.boundaries[i].axis; }
+  const int n_axes = (axes & 1) + ((axes >> 1) & 1) + ((axes >> 2) & 1);
+  const int depth = n_abb <= 1 ? 0 : (n_axes <= 2 ? 1 : n_axes - 1);
+  return depth > 1 && d.layout != LT_LAYOUT_REFERENCE ? -1 : depth;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1027,18 +1078,12 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   // distinct AXES the outlets lie on, minus one.  Kernels exist for depth 0 (one outlet), 1 (any list of outlets on at
   // most two axes: every 2-D flow) and, in the reference layout, 2 (outlets on all three axes, whose planes meet in
   // corners) -- the reference takes any list, lettuce/_simulation.py:57-86.
-  {
-    int axes = 0;
-    for (int i = 0; i < d->n_boundaries; ++i)
-      if (d->boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET) axes |= 1 << d->boundaries[i].axis;
-    const int n_axes = (axes & 1) + ((axes >> 1) & 1) + ((axes >> 2) & 1);
-    p->abb_depth = n_abb <= 1 ? 0 : (n_axes <= 2 ? 1 : n_axes - 1);
-    if (p->abb_depth > 1 && d->layout != LT_LAYOUT_REFERENCE) {
-      lt_plan_destroy(p);
-      return fail(LT_ERR_UNSUPPORTED, "AntiBounceBackOutlets on all three axes (their planes meet in corners, where an "
-                                      "outlet's neighbour depends on two earlier outlets) exist for the reference "
-                                      "layout only; on slabs outlets on one or two axes run, in any number");
-    }
+  p->abb_depth = abb_depth_of(*d);
+  if (p->abb_depth < 0) {
+    lt_plan_destroy(p);
+    return fail(LT_ERR_UNSUPPORTED, "AntiBounceBackOutlets on all three axes (their planes meet in corners, where an "
+                                    "outlet's neighbour depends on two earlier outlets) exist for the reference "
+                                    "layout only; on slabs outlets on one or two axes run, in any number");
   }
   const size_t bt_size = d->dtype == LT_F32 ? sizeof(lt::BoundaryTable<float>)
                                             : sizeof(lt::BoundaryTable<double>);
@@ -1086,37 +1131,18 @@ int lt_plan_set_masks(lt_plan *p, const uint8_t *ncm, const uint8_t *nsm, void *
   if (!p->mask_flag) LT_HIP(hipMalloc((void **)&p->mask_flag, sizeof(unsigned)));
   hipStream_t hs = static_cast<hipStream_t>(stream);
   LT_HIP(hipMemsetAsync(p->mask_flag, 0, sizeof(unsigned), hs));
-  // the only no-streaming bits the two-step kernel can take: those of ONE outlet at the last plane of the
-  // slowest memory axis or at an end of the rows -- the populations entering through it, on every node of it
-  int axis = -1, plane = -1, face = -1, outlets = 0;
-  unsigned expected = 0, eq_slots = 0;
-  const int sweep = p->unit.d == 2 ? 1 : 2;          // the slowest memory axis: rows in 2-D, planes in 3-D
-  for (int i = 0; i < p->desc.n_boundaries; ++i) {
-    const lt_boundary_desc &b = p->desc.boundaries[i];
-    if (b.kind == LT_BOUNDARY_EQUILIBRIUM && i + 1 < 32) eq_slots |= 1u << (i + 1);   // (only read for plans the two-step kernels admit: <= 15 boundaries)
-    if (b.kind != LT_BOUNDARY_ABB_OUTLET || (b.flags & LT_BOUNDARY_ABSENT)) continue;
-    ++outlets;
-    const int ax = mem_axis_of(p, b.axis);
-    if ((ax == sweep && b.side == 1) || (ax == 0 && p->unit.d == 3)) {
-      axis = ax == sweep ? 2 : 0;                    // compile_masks_kernel: 2 = "index / plane_nodes", 0 = a0 column
-      plane = ax == sweep ? (sweep == 2 ? p->n2 : p->n1) - 1 - p->desc.ghost_planes : (b.side == 1 ? p->n0 - 1 : 0);
-      if (ax == 0) face = b.side == 1 ? 0 : p->n0 - 1;
-      const lt::QList in = crossing_axis(p, ax, -b.side);
-      for (int k = 0; k < in.n; ++k) expected |= 1u << in.q[k];
-    }
-  }
-  if (outlets != 1) { axis = -1; plane = -1; face = -1; expected = 0; }
+  const MaskCheck c = mask_check_of(p);
   const unsigned grid = (unsigned)((p->N + lt::kThreads - 1) / lt::kThreads);
   hipLaunchKernelGGL(lt::compile_masks_kernel, dim3(grid), dim3(lt::kThreads), 0, hs, ncm, nsm, p->unit.q, p->N,
-                     p->node, nsm ? p->nsm_bits : nullptr, sweep == 1 ? (long long)p->n0 : (long long)p->n0 * p->n1, p->n0,
-                     axis, plane, expected,
-                     face, eq_slots, p->mask_flag);
+                     p->node, nsm ? p->nsm_bits : nullptr, c.plane_nodes, p->n0, c.axis, c.plane, c.expected,
+                     c.face, c.eq_slots, p->mask_flag);
   LT_HIP(hipGetLastError());
-  unsigned flags = 0;
-  LT_HIP(hipMemcpyAsync(&flags, p->mask_flag, sizeof flags, hipMemcpyDeviceToHost, hs));
-  LT_HIP(hipStreamSynchronize(hs));
-  p->nsm_confined = (flags & 1u) == 0;
-  p->inlet_faces_outlet = (flags & 2u) == 0;
+  const int rc = store_admission(p, hs);
+  if (rc) return rc;
+  if (p->gexec) {                                    // captured with the mask pointers of its time (nsm_bits may be new)
+    (void)hipGraphExecDestroy(p->gexec);
+    p->gexec = nullptr;
+  }
   p->masked = 1;
   p->canary = 0;                                     // new masks: the first-use check runs again
   return LT_OK;
@@ -1125,12 +1151,46 @@ int lt_plan_set_masks(lt_plan *p, const uint8_t *ncm, const uint8_t *nsm, void *
 int lt_plan_update_boundary(lt_plan *p, int32_t index, const lt_boundary_desc *b, void *stream) {
   if (!p || !b) return fail(LT_ERR_INVALID, "null argument");
   if (index < 0 || index >= p->desc.n_boundaries) return fail(LT_ERR_INVALID, "boundary index %d", index);
-  if (b->kind != p->desc.boundaries[index].kind)
-    return fail(LT_ERR_INVALID, "boundary %d: kind cannot change (%d -> %d)", index,
-                p->desc.boundaries[index].kind, b->kind);
+  const lt_boundary_desc old = p->desc.boundaries[index];
+  if (b->kind != old.kind)
+    return fail(LT_ERR_INVALID, "boundary %d: kind cannot change (%d -> %d)", index, old.kind, b->kind);
+  // what lt_plan_create would refuse is refused here too, and leaves the plan as it was
+  int rc = check_boundary(p, *b, 0);
+  if (rc) return rc;
   p->desc.boundaries[index] = *b;
-  return p->desc.dtype == LT_F32 ? upload_boundaries<float>(p, static_cast<hipStream_t>(stream))
-                                 : upload_boundaries<double>(p, static_cast<hipStream_t>(stream));
+  const int depth = abb_depth_of(p->desc);
+  if (depth < 0) {
+    p->desc.boundaries[index] = old;
+    return fail(LT_ERR_UNSUPPORTED, "boundary %d: AntiBounceBackOutlets on all three axes exist for the reference "
+                                    "layout only", index);
+  }
+  p->abb_depth = depth;
+  // an outlet that moves (axis, side, present / absent) changes which kernels apply and what they compute on its plane
+  const bool moved = b->kind == LT_BOUNDARY_ABB_OUTLET &&
+                     (b->axis != old.axis || b->side != old.side || b->flags != old.flags);
+  // an equilibrium boundary that switches between its constant feq and a per-node field takes the other branch of
+  // the kernels' boundary dispatch -- the code the first-use check exists for
+  const bool source = b->kind == LT_BOUNDARY_EQUILIBRIUM && (b->feq_field_dev == nullptr) != (old.feq_field_dev == nullptr);
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  rc = p->desc.dtype == LT_F32 ? upload_boundaries<float>(p, hs) : upload_boundaries<double>(p, hs);
+  if (rc) return rc;
+  if (moved || source) p->canary = 0;                // the first-use check runs again
+  if (moved && p->gexec) {                           // the captured launches carry the old outlet's kernel arguments
+    (void)hipGraphExecDestroy(p->gexec);
+    p->gexec = nullptr;
+  }
+  if (moved && p->masked) {
+    // the admission of the masked two-step kernels was decided for the old outlet: decide it again on the compiled
+    // masks (node bytes and no-streaming bits as lt_plan_set_masks left them) for the new one
+    LT_HIP(hipMemsetAsync(p->mask_flag, 0, sizeof(unsigned), hs));
+    const MaskCheck c = mask_check_of(p);
+    const unsigned grid = (unsigned)((p->N + lt::kThreads - 1) / lt::kThreads);
+    hipLaunchKernelGGL(lt::recheck_masks_kernel, dim3(grid), dim3(lt::kThreads), 0, hs, p->node, p->nsm_bits, p->N,
+                       c.plane_nodes, p->n0, c.axis, c.plane, c.expected, c.face, c.eq_slots, p->mask_flag);
+    LT_HIP(hipGetLastError());
+    return store_admission(p, hs);
+  }
+  return LT_OK;
 }
 
 int lt_collide(lt_plan *p, const void *f, void *o, double tau, void *s) {

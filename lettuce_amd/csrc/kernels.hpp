@@ -1683,12 +1683,23 @@ __global__ void __launch_bounds__(kThreads) halo2_kernel(T *__restrict__ f, T *_
   }
 }
 
-// node descriptor byte + sparse streaming-mask bits from the reference's two mask tensors
-// The masked two-step kernel's admission tests (twostep_masked.hpp), collected in *mismatch:
+// The masked two-step kernel's admission tests (twostep_masked.hpp) on node i (descriptor slot `slot`, no-streaming
+// bits b), as mismatch bits:
 //  bit 0: the no-streaming bits of a node differ from `expected` on the outlet -- a2 plane `plane` (axis = 2)
 //         or a0 column `plane` (axis = 0) -- or from zero elsewhere (axis < 0: no bits anywhere);
 //  bit 1: a node of a0 column `face` (>= 0: the face opposite an a0 outlet) is not an equilibrium node
-//         (eq_slots: bit s set = boundary s is an EquilibriumBoundaryPU).
+//         (eq_slots: bit s set = boundary s is an EquilibriumBoundaryPU; slots from 32 on are never one of them).
+__device__ inline unsigned admission_mismatch(long long i, int slot, unsigned b, long long plane_nodes, int n0, int axis,
+                                              int plane, unsigned expected, int face, unsigned eq_slots) {
+  const int c0 = (int)(i % n0);
+  const bool on_outlet = axis == 2 ? i / plane_nodes == plane : (axis == 0 ? c0 == plane : false);
+  unsigned bad = b != (on_outlet ? expected : 0u) ? 1u : 0u;
+  if (face >= 0 && c0 == face && !(slot < 32 && ((eq_slots >> slot) & 1u))) bad |= 2u;
+  return bad;
+}
+
+// node descriptor byte + sparse streaming-mask bits from the reference's two mask tensors, and the admission tests
+// above collected in *mismatch
 static __global__ void __launch_bounds__(kThreads) compile_masks_kernel(
     const unsigned char *__restrict__ ncm, const unsigned char *__restrict__ nsm, int q,
     long long N, unsigned char *__restrict__ node, unsigned *__restrict__ bits, long long plane_nodes, int n0,
@@ -1703,10 +1714,20 @@ static __global__ void __launch_bounds__(kThreads) compile_masks_kernel(
   const int slot = ncm ? (ncm[i] & 0x7f) : 0;
   node[i] = (unsigned char)(slot | (b ? 0x80 : 0));
   if (bits) bits[i] = b;
-  const int c0 = (int)(i % n0);
-  const bool on_outlet = axis == 2 ? i / plane_nodes == plane : (axis == 0 ? c0 == plane : false);
-  unsigned bad = b != (on_outlet ? expected : 0u) ? 1u : 0u;
-  if (face >= 0 && c0 == face && !((eq_slots >> slot) & 1u)) bad |= 2u;
+  const unsigned bad = admission_mismatch(i, slot, b, plane_nodes, n0, axis, plane, expected, face, eq_slots);
+  if (bad) atomicOr(mismatch, bad);
+}
+
+// the same admission tests on masks compiled before (lt_plan_update_boundary: an outlet moved after
+// lt_plan_set_masks); bits is read only where the node byte says the node has no-streaming bits
+static __global__ void __launch_bounds__(kThreads) recheck_masks_kernel(
+    const unsigned char *__restrict__ node, const unsigned *__restrict__ bits, long long N, long long plane_nodes,
+    int n0, int axis, int plane, unsigned expected, int face, unsigned eq_slots, unsigned *__restrict__ mismatch) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= N) return;
+  const unsigned char n = node[i];
+  const unsigned b = (bits && (n & 0x80)) ? bits[i] : 0u;
+  const unsigned bad = admission_mismatch(i, n & 0x7f, b, plane_nodes, n0, axis, plane, expected, face, eq_slots);
   if (bad) atomicOr(mismatch, bad);
 }
 
