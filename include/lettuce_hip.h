@@ -345,7 +345,9 @@ const char *lt_plan_kernel_name(lt_plan *plan);
 /* A/B selector of the two-step kernel's workgroup order: 0 = product variant, 3 = no XCD-aware renumbering of the
  * workgroups, 4 = the round-1 renumbering (an eighth of the grid per XCD instead of an eighth of every segment
  * layer).  1, 2 and 5 named tile variants that lost their A/B and were removed (two nodes per thread in both phases,
- * two output nodes per thread, 32 x 8 tiles for the slab edge launch): LT_ERR_UNSUPPORTED. */
+ * two output nodes per thread, 32 x 8 tiles for the slab edge launch): LT_ERR_UNSUPPORTED.
+ * 6 = the one-role schedule (every wave runs both phases of the sweep) for the sweeps that by default run with
+ * separate producer and consumer waves -- D3Q19 BGK fp32, both layouts; no effect on the other kernels. */
 int lt_plan_set_shift_policy(lt_plan *plan, int32_t policy);
 /* out[i] = x[i] / D as the kernels' equilibrium forms it (div_cs: two or three instructions that return the IEEE
  * quotient by the constant D = 2 cs^2 (which 0) or cs^2 (which 1) rounded to dtype, the reference's divisors:

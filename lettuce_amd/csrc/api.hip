@@ -1336,6 +1336,7 @@ const char *lt_plan_kernel_name(lt_plan *p) {
   a.abb_depth = p->abb_depth;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
+  a.shift = p->shift;
   if (a.mode == lt::kFusedTwice && !p->unit.name(a)) a.mode = lt::kFused;
   a.tune = resolve_tune(p);
   const char *n = p->unit.name(a);
@@ -1393,7 +1394,7 @@ int lt_probe_div_cs(const void *x, void *out, int64_t n, int32_t dtype, int32_t 
 
 int lt_plan_set_shift_policy(lt_plan *p, int32_t policy) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
-  if (policy < 0 || policy > 5) return fail(LT_ERR_INVALID, "shift policy %d", policy);
+  if (policy < 0 || policy > 6) return fail(LT_ERR_INVALID, "shift policy %d", policy);
   if (policy == 1 || policy == 2 || policy == 5)
     return fail(LT_ERR_UNSUPPORTED, "shift policy %d: its tile variant lost its A/B and was removed", policy);
   if (p->shift != policy) p->canary = 0;

@@ -78,6 +78,8 @@ LT_DECLARE_TWICE(d3q19_f32)
 LT_DECLARE_TWICE(d3q19_f64)
 LT_DECLARE_TWICE(d3q27_f32)
 LT_DECLARE_TWICE(d3q27_f64)
+// ... and those with separate producer and consumer waves, instantiated by inst3_<tag>.hip
+int roles_d3q19_f32(const StepArgs &, bool name_only, const char **name);
 
 LT_DECLARE_UNIT(d1q3_f32)
 LT_DECLARE_UNIT(d1q3_f64)

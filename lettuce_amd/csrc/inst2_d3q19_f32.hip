@@ -5,4 +5,5 @@
 #define LT_HAS_KBC 0
 #define LT_IS_3D 1
 #define LT_PART 2
+#define LT_HAS_ROLES 1       // its plain BGK sweep: inst3_d3q19_f32.hip
 #include "unit.inc"

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "lattice.hpp"
+#include "twostep_roles.hpp"
 
 namespace lt {
 
@@ -827,13 +828,17 @@ __device__ __forceinline__ void lds_barrier() {
 // over the whole slab whose edge workgroups start first and count themselves done (p.signal).
 // NPT / NPB: intermediate / output nodes per thread.  Two of either lost their A/B; they stay
 // in the signature because kernel names and profiles are keyed on them.
+// SCHED (plain sweep): 0 = every wave runs both phases; 1 = producer waves run phase A, consumer waves phase B
+// (twostep_roles.hpp).
 template <typename T, class S, int LAYOUT, int COLL, int T0_, int T1, int NPT = 1, int MODE = 0,
-          int NPB = NPT>
-__global__ void __launch_bounds__(((TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64))
+          int NPB = NPT, int SCHED = 0>
+__global__ void __launch_bounds__((SCHED == 0 ? (TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64
+                                              : RoleWaves<TwoStep<T, S, T0_, T1>::NI, TwoStep<T, S, T0_, T1>::NO>::THREADS))
 lbm2_kernel(const KParams<T> p, const int seg_len) {
   constexpr bool PACK = MODE == 1;
   static_assert(MODE == 0 || LAYOUT == 1, "edge / signalling launches exist in the slab layout");
   static_assert(NPT == 1 && NPB == 1, "one intermediate and one output node per thread");
+  static_assert(SCHED == 0 || (SCHED == 1 && MODE == 0), "separate producer and consumer waves: the plain sweep");
   using B = TwoStep<T, S, T0_, T1>;
   using M = MemMap<S, LAYOUT>;
   constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
@@ -917,6 +922,100 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
   });
   const unsigned plane_nodes = (unsigned)p.n1 * (unsigned)p.n0;
 
+  if constexpr (SCHED == 1) {
+    // Producer waves run phase A only, consumer waves phase B only (twostep_roles.hpp: the skeleton both run, the
+    // wave layout).  A SIMD then holds waves in different phases -- a consumer colliding while the producers wait
+    // for their loads, producers colliding while the consumer waits for LDS -- instead of three waves that wait at
+    // the same moments.  Per node the arithmetic and its order are those of SCHED 0.
+    using R = RoleWaves<NI, NO>;
+    constexpr int CPB = R::CPB, CT = NO / CPB;
+    const int last = s + seg_len < range_end ? s + seg_len : range_end;
+    auto sync = [&]() { lds_barrier(); };
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) < R::PW) {
+      // Every lane loads (those without an intermediate node read the plane's first node): under `if (in_a)` the
+      // other lanes' registers are undefined, the compiler zeroes them AFTER the loads and that write waits for them.
+      if (!in_a) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) voff[0][a][c] = 0u;
+      }
+      T set0[S::Q][1], set1[S::Q][1];
+      auto load = [&](int plane, auto set) {
+        T (&dst)[S::Q][1] = decltype(set)::value == 0 ? set0 : set1;
+        int g2 = plane, g2m = plane - 1, g2p = plane + 1;
+        if (p.wrap2) {
+          g2 = plane < 0 ? plane + p.n2 : (plane >= p.n2 ? plane - p.n2 : plane);
+          g2m = g2 == 0 ? p.n2 - 1 : g2 - 1;
+          g2p = g2 == p.n2 - 1 ? 0 : g2 + 1;
+        }
+        static_for<S::Q>([&](auto qc) {
+          constexpr int q = decltype(qc)::value;
+          constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2);
+          const int z = e2 == 0 ? g2 : (e2 > 0 ? g2m : g2p);
+          const T *base = p.in + ((long long)q * p.Ni + (long long)((unsigned)z * plane_nodes));
+          dst[q][0] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + voff[0][e1 + 1][e0 + 1]);
+        });
+        // (the register-minimising scheduler sinks the loads behind the collide of the other set otherwise)
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto fill = [&](int r, int r3, auto set) {
+        T (&src)[S::Q][1] = decltype(set)::value == 0 ? set0 : set1;
+        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
+        if (in_a) {
+          static_for<S::Q>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
+            if constexpr (e2 > 0) lds_u[r & 3][rank][a_at[0]] = src[q][0];
+            else if constexpr (e2 == 0) lds_c[r3][rank][a_at[0]] = src[q][0];
+            else lds_d[r & 1][rank][a_at[0]] = src[q][0];
+          });
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      role_sweep(s, last, load, fill, sync, [](int, int) {}, [](int) {});
+    } else {
+      // consumer thread c of CT owns the output nodes c, c + CT, ... of the tile: a wave reads whole rows
+      const int c = tid - R::PW * 64;
+      unsigned c_off[CPB];
+      int c_at[CPB];
+      static_for<CPB>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const int ib = c + k * CT;
+        const int j1 = ib / T0, j0 = ib - j1 * T0;
+        c_off[k] = ((unsigned)(t1 + j1) * (unsigned)p.n0 + (unsigned)(t0 + j0)) * (unsigned)sizeof(T);
+        c_at[k] = (j1 + 1) * H0 + (j0 + 1);
+      });
+      T f[S::Q][CPB];
+      auto drain = [&](int r, int r3) {
+        static_for<S::Q>([&](auto qc) {
+          constexpr int q = decltype(qc)::value;
+          constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
+          static_for<CPB>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            const int at = c_at[k] - e1 * H0 - e0;
+            if constexpr (e2 > 0) f[q][k] = lds_u[(r - 1) & 3][rank][at];
+            else if constexpr (e2 == 0) f[q][k] = lds_c[r3][rank][at];
+            else f[q][k] = lds_d[(r + 1) & 1][rank][at];
+          });
+        });
+      };
+      auto emit = [&](int k2) {
+        if constexpr (COLL == 1)
+          static_for<CPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, CPB, decltype(kc)::value>(f, p.tau_inv); });
+        static_for<S::Q>([&](auto qc) {
+          constexpr int q = decltype(qc)::value;
+          T *base = p.out + ((long long)q * p.No + (long long)((unsigned)k2 * plane_nodes));
+          static_for<CPB>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            __builtin_nontemporal_store(f[q][k], reinterpret_cast<T *>(reinterpret_cast<char *>(base) + c_off[k]));
+          });
+        });
+      };
+      role_sweep(s, last, [](int, auto) {}, [](int, int, auto) {}, sync, drain, emit);
+    }
+    return;
+  }
   T pre[S::Q][NPT];
   auto load_a = [&](int plane) {
     // periodic along a2, or a slab whose ghost planes (two per side) hold the neighbours' data

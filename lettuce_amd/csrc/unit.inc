@@ -14,8 +14,14 @@
 // (lbm2_kernel), which inst2_<tag>.hip (LT_PART 2) instantiates -- its own object file, so that it builds beside the
 // rest and can carry its own scheduler setting (Makefile: fp64 D3Q19 is 2.4 % faster with max-ilp, the masked
 // one-step kernels of the same lattice 8 % slower)
+// 3 = the two-step launches with separate producer and consumer waves (the kernel's SCHED = 1) of a unit that has
+// them (LT_HAS_ROLES, inst3_<tag>.hip): again an object of its own, because that schedule wants another scheduler
+// setting than the one-role kernels beside it (Makefile)
 #ifndef LT_PART
 #define LT_PART 0
+#endif
+#ifndef LT_HAS_ROLES
+#define LT_HAS_ROLES 0
 #endif
 #define LT_CAT_(a, b) a##b
 #define LT_CAT(a, b) LT_CAT_(a, b)
@@ -35,7 +41,7 @@ constexpr int kTwiceW = 256 / (int)sizeof(T);
 constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
                         : (sizeof(T) == 4 && kTwicePerNode * (kTwiceW + 2) * 6 <= 160 * 1024 ? 4 : 0);
 
-#if LT_PART != 2
+#if LT_PART < 2
 
 // one node per thread: the kernels' VEC = 1, SHIFT = 0
 template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
@@ -89,20 +95,21 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   return (int)hipGetLastError();
 }
 
-#endif  // LT_PART != 2
+#endif  // LT_PART < 2
 
 #if LT_PART != 1
 // Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
 // returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
 // one node per thread and per block: the kernel's NPT = NPB = 1
-template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0>
+// SCHED 1: separate producer and consumer waves (twostep_roles.hpp)
+template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
 int launch_twice(const StepArgs &a, bool name_only, const char **name) {
   if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1)) {
     using B = TwoStep<T, S, T0, T1>;
     if (name_only) {
       static char buf[96];
-      snprintf(buf, sizeof buf, "lbm2_kernel<%s, lt::%s, %d, %d, %d, %d, 1, %d, 1>", sizeof(T) == 4 ? "float" : "double",
-               S::NAME, LAYOUT, COLL, T0, T1, MODE);
+      snprintf(buf, sizeof buf, "lbm2_kernel<%s, lt::%s, %d, %d, %d, %d, 1, %d, 1%s>", sizeof(T) == 4 ? "float" : "double",
+               S::NAME, LAYOUT, COLL, T0, T1, MODE, SCHED ? ", 1" : "");
       *name = buf;
       return 0;
     }
@@ -138,8 +145,8 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
     p.lo = a.interior_begin; p.hi = a.interior_end;
     const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len +
                                                                    (a.planes2 + a.seg_len - 1) / a.seg_len));
-    constexpr int threads = (B::NI + 63) / 64 * 64;
-    hipLaunchKernelGGL((lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1>), dim3(grid), dim3(threads), 0,
+    constexpr int threads = SCHED ? RoleWaves<B::NI, B::NO>::THREADS : (B::NI + 63) / 64 * 64;
+    hipLaunchKernelGGL((lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1, SCHED>), dim3(grid), dim3(threads), 0,
                        a.stream, p, a.seg_len);
     return (int)hipGetLastError();
   } else {
@@ -147,11 +154,24 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
+#if LT_PART == 3
+// the BGK sweeps of this unit with separate producer and consumer waves, where they won their A/B (DESIGN.md section 7)
+int twice_roles(const StepArgs &a, bool name_only, const char **name) {
+  constexpr int W = kTwiceW, R = kTwiceR;
+  if (a.layout == 0) return launch_twice<0, 1, W, R, 0, 1>(a, name_only, name);
+  return launch_twice<1, 1, W, R, 0, 1>(a, name_only, name);
+}
+#else
 // the unmasked 3-D two-step launches of this unit
 int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
   const int coll = a.coll;
   constexpr int W = kTwiceW, R = kTwiceR;
   if constexpr (R > 0) {
+#if LT_HAS_ROLES
+    // the plain BGK sweep: inst3_<tag>.hip; shift policy 6 runs the one-role schedule (A/B)
+    if (coll == 1 && a.shift != 6 && (a.layout == 0 || !(a.pack_lo || a.pack_hi || a.signal)))
+      return LT_CAT(roles_, LT_TAG)(a, name_only, name);
+#endif
     if (a.layout == 0 && coll == 0) return launch_twice<0, 0, W, R>(a, name_only, name);
     if (a.layout == 0 && coll == 1) return launch_twice<0, 1, W, R>(a, name_only, name);
 #if LT_IS_3D
@@ -169,9 +189,10 @@ int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
   }
   return kNoKernel;
 }
+#endif  // LT_PART == 3, else
 #endif  // LT_PART != 1
 
-#if LT_PART != 2
+#if LT_PART < 2
 // Two fused steps per launch for plans with boundaries (twostep_masked.hpp, lbm2m_kernel): whole periodic
 // grid, reference layout.  api.hip admits the plan (masked_two_step_ok); here: the grid tiles, the field is
 // below 4 GiB (32-bit buffer offsets; BGK in the reference layout: a population is, and fields beyond 4 GiB run
@@ -578,13 +599,17 @@ int aux_impl(const AuxArgs &a) {
   return (int)hipGetLastError();
 }
 
-#endif  // LT_PART != 2
+#endif  // LT_PART < 2
 
 }  // namespace
 
 #if LT_PART == 2
 int LT_CAT(twice_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
   return twice_unmasked(a, name_only, name);
+}
+#elif LT_PART == 3
+int LT_CAT(roles_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
+  return twice_roles(a, name_only, name);
 }
 #else
 int LT_CAT(step_, LT_TAG)(const StepArgs &a) { return dispatch(a, false, nullptr); }
@@ -600,6 +625,6 @@ int LT_CAT(aux_, LT_TAG)(const AuxArgs &a) {
 #endif
   return aux_impl<0>(a);
 }
-#endif  // LT_PART == 2
+#endif  // LT_PART
 
 }  // namespace lt

@@ -27,7 +27,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t
 echo "== rocprofv3 kernel trace of the slab rehearsal"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_slab -- python3 $GRAFT_REPO_ROOT/bench.py --slab --steps 100 --batches 3 --driver two-step --no-cpu-baseline > $OUT/trace_slab_bench.json 2> $OUT/trace_slab.err; echo "slab trace exit $?"
 python3 $GRAFT_REPO_ROOT/tools/slab_timeline.py $OUT/trace_slab $OUT/slab_timeline.json > /dev/null; echo "timeline exit $?"
-for W in cfg2 cfg4 cfg4bgk obst19 cfg5 slab slab5; do
+for W in cfg2_one_role cfg2 cfg4 cfg4bgk obst19 cfg5 slab slab5; do
   echo "== $W: kernel trace"
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/w_$W/trace -- python3 $GRAFT_REPO_ROOT/tools/profile_workload.py $W 200 > $OUT/w_$W.json 2> $OUT/w_$W.err; echo "rc $?"
   for C in FETCH_SIZE WRITE_SIZE; do

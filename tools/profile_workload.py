@@ -1,6 +1,7 @@
 """One BASELINE workload through lt.Simulation for the rocprofv3 passes of tools/gpu_round3.sh (kernel trace and
 PMC counters need a process that runs ONE workload: the counters are summed per kernel name).
-usage: profile_workload.py cfg2|cfg4|cfg4bgk|obst19|cfg5 [steps]"""
+usage: profile_workload.py cfg2|cfg2_one_role|cfg4|cfg4bgk|obst19|cfg5|slab|slab5 [steps]
+cfg2_one_role: cfg2 with the one-role schedule of the two-step sweep (lt_plan_set_shift_policy 6)."""
 import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,12 +10,14 @@ import lettuce_amd as lt
 which = sys.argv[1]
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 25
 dev = torch.device("cuda:0")
-if which == "cfg2":
+if which in ("cfg2", "cfg2_one_role"):
     ctx = lt.Context(dev, torch.float32, True)
     edge = int(os.environ.get("LT_PROFILE_EDGE", "256"))          # other sizes: tools/pmc_tlb.sh
     shape = [int(v) for v in os.environ["LT_PROFILE_RES"].split(",")] if os.environ.get("LT_PROFILE_RES") else [edge] * 3
     flow = lt.TaylorGreenVortex(ctx, shape, 1600, 0.1, lt.D3Q19())
     sim = lt.Simulation(flow, lt.BGKCollision(flow.units.relaxation_parameter_lu), [])
+    if which == "cfg2_one_role":
+        sim._native.plan.set_shift_policy(6)
     # a cube keeps the name bench.py looks its traffic row up by (bench.traffic_from_profile)
     q, esize, key = 19, 4, "tgv3d_d3q19_bgk_f32_" + (str(shape[0]) if len(set(shape)) == 1 else "x".join(map(str, shape)))
 elif which in ("cfg4", "cfg4bgk", "obst19"):
