@@ -59,8 +59,9 @@ enum lt_status {
 enum lt_stencil { LT_D2Q9 = 0, LT_D3Q19 = 1, LT_D3Q27 = 2, LT_D1Q3 = 3, LT_D3Q15 = 4 };
 /* AT_DISPATCH_FLOATING_TYPES, lettuce/cuda_native/_template.py:357 */
 enum lt_dtype { LT_F32 = 0, LT_F64 = 1 };
-/* lettuce/ext/_collision/no_collision.py:9-17, bgk_collision.py:12-35, kbc_collision.py:11-166 */
-enum lt_collision { LT_COLLISION_NONE = 0, LT_COLLISION_BGK = 1, LT_COLLISION_KBC = 2 };
+/* lettuce/ext/_collision/no_collision.py:9-17, bgk_collision.py:12-35, kbc_collision.py:11-166,
+ * smagorinsky_collision.py:7-36 (every stencil; the constant: lt_plan_set_smagorinsky) */
+enum lt_collision { LT_COLLISION_NONE = 0, LT_COLLISION_BGK = 1, LT_COLLISION_KBC = 2, LT_COLLISION_SMAGORINSKY = 3 };
 /* lettuce/ext/_boundary/bounce_back_boundary.py:10-32, equilibrium_boundary_pu.py:13-46,
  * anti_bounce_back_outlet.py:13-109 */
 enum lt_boundary_kind {
@@ -398,6 +399,13 @@ int lt_plan_set_many_step(lt_plan *plan, int32_t mode);
  * mode -1 = automatic, 0 = never, 1 = whenever supported.  planes_per_workgroup: segment length of
  * the sweep along the slowest axis (0 = automatic). */
 int lt_plan_set_two_step(lt_plan *plan, int32_t mode, int32_t planes_per_workgroup);
+/* The constant C of a plan with LT_COLLISION_SMAGORINSKY (nu_t = C^2 S:S after two fixed-point iterations,
+ * smagorinsky_collision.py:27-34); 0.17, the reference's default, until set.  Read at every launch, so it may change
+ * between calls like tau.  LT_ERR_INVALID (plan unchanged) for a negative or non-finite value and on a plan of
+ * another collision.  Two steps per launch exist for D3Q19 fp32 on periodic plans without masks: lt_run's automatic
+ * mode takes them in the streaming regime as it does for BGK, lt_plan_set_two_step(plan, 1, ...) wherever the grid
+ * tiles; every other plan keeps the one-step kernel (lt_plan_two_step_admitted tells why). */
+int lt_plan_set_smagorinsky(lt_plan *plan, double constant);
 /* Population stride.  By default a population buffer is dense: population q starts q * nodes elements after
  * population 0 (the reference's [q, *res] tensor, lettuce/_flow.py:90).  With the q populations a power of two
  * apart (256^3 fp32: exactly 64 MiB) the q read and q write streams of a node meet in the same memory channels;

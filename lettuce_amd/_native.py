@@ -29,7 +29,7 @@ LT_MAX_Q = 27
 
 STENCIL_IDS = {"D2Q9": 0, "D3Q19": 1, "D3Q27": 2, "D1Q3": 3, "D3Q15": 4}
 DTYPE_IDS = {torch.float32: 0, torch.float64: 1}
-COLLISION_IDS = {"none": 0, "bgk": 1, "kbc": 2}
+COLLISION_IDS = {"none": 0, "bgk": 1, "kbc": 2, "smagorinsky": 3}
 BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3}
 LAYOUT_REFERENCE, LAYOUT_SLAB = 0, 1
 
@@ -98,6 +98,7 @@ SYMBOLS = {
     "lt_plan_set_residency": (ctypes.c_int, [_vp, _i32]),
     "lt_stream_collide_twice": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "lt_plan_set_two_step": (ctypes.c_int, [_vp, _i32, _i32]),
+    "lt_plan_set_smagorinsky": (ctypes.c_int, [_vp, _dbl]),
     "lt_stream_collide_twice_planes": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp]),
     "lt_stream_collide_twice_planes_packed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp, _vp, _vp]),
     "lt_stream_collide_twice_edges": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i32, _vp, _vp, _vp]),
@@ -716,6 +717,10 @@ class Plan:
         self._check(self.lib.lt_stream_collide_many(self._handle, _ptr(f), _ptr(out), float(tau), int(n_steps),
                                                     _stream_handle()))
         return out
+
+    def set_smagorinsky(self, constant: float = 0.17):
+        """the constant of a plan with the Smagorinsky collision; read at every launch, like tau"""
+        self._check(self.lib.lt_plan_set_smagorinsky(self._handle, float(constant)))
 
     def set_two_step(self, mode: int = -1, planes_per_workgroup: int = 0):
         """lt_run pairs fused steps into two-step launches: -1 automatic, 0 never, 1 when supported"""

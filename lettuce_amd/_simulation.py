@@ -192,9 +192,15 @@ class _NativeStepper:
         self._sync_masks()
         self._sync_boundaries()
         tau = float(self.collision.tau(flow))
+        key = tau               # what a batch must share with the one before it to carry on from its state
+        if self.collision.constant is not None:
+            # Smagorinsky: the constant is re-read per batch like tau and handed to the plan (no new plan)
+            constant = float(self.collision.constant(flow))
+            self.plan.set_smagorinsky(constant)
+            key = (tau, constant)
         if self.plan.resident_enabled()[0]:
             try:
-                return self._batch_resident(k, tau)
+                return self._batch_resident(k, tau, key)
             except NativeEngineError as exc:
                 # the engine's own padded buffers could not be allocated (two more population fields, raw
                 # hipMalloc; torch's cache was emptied and the allocation tried again).  "Automatic" then carries on
@@ -208,12 +214,12 @@ class _NativeStepper:
         pending = flow._pending is not None and self._lazy is not None
         if pending:
             fstar, scratch, token = self._lazy
-            pending = token == (_version(fstar), _version(scratch), tau) and self._carry == "lazy"
+            pending = token == (_version(fstar), _version(scratch), key) and self._carry == "lazy"
         if pending:
             a, b, from_fstar = fstar, scratch, True
         else:
             f, nxt = self._state_buffers()                    # reading flow.f completes a pending batch
-            carry = not changed and self._carry == (_version(f), _version(nxt), tau)
+            carry = not changed and self._carry == (_version(f), _version(nxt), key)
             a, b, from_fstar = (nxt, f, True) if carry else (f, nxt, False)
         if self.fused_events is not None:
             self.plan.set_fused_events(*self.fused_events)    # recorded by lt_run around its fused launches
@@ -224,14 +230,14 @@ class _NativeStepper:
             self.plan.set_deferred_stream(False)
             if self.fused_events is not None:
                 self.plan.set_fused_events(None, None)
-        self._lazy = (fstar, scratch, (_version(fstar), _version(scratch), tau))
+        self._lazy = (fstar, scratch, (_version(fstar), _version(scratch), key))
         self._carry = "lazy"
         flow._f, flow._f_next = None, None                    # nobody may see the buffers until the pass is done
 
         def finish():
             result = self.plan.stream(fstar, scratch)
             self._lazy = None
-            self._carry = (_version(result), _version(fstar), tau)
+            self._carry = (_version(result), _version(fstar), key)
             return result, fstar
 
         def drop():                                           # flow.f was assigned while the pass was pending
@@ -240,7 +246,7 @@ class _NativeStepper:
         finish.drop = drop
         flow._pending = finish
 
-    def _batch_resident(self, k: int, tau: float):
+    def _batch_resident(self, k: int, tau: float, key):
         """The same batch with the post-collision populations in the ENGINE's padded ping-pong buffers
         (``lt_resident_*``): ``flow.f`` / ``flow.f_next`` stay the reference's plain ``[q, *res]`` tensors
         (lettuce/_flow.py:90,124-134) and are written only by the pass that presents the populations when somebody
@@ -250,11 +256,11 @@ class _NativeStepper:
         if self.fused_events is not None:
             plan.set_fused_events(*self.fused_events)
         try:
-            if flow._pending is not None and self._carry == ("resident-pending", tau):
+            if flow._pending is not None and self._carry == ("resident-pending", key):
                 plan.resident_advance(tau, k)
             else:
                 f, nxt = self._state_buffers()                # reading flow.f completes a pending batch
-                if self._carry == ("resident", _version(f), tau):
+                if self._carry == ("resident", _version(f), key):
                     plan.resident_advance(tau, k)             # what was shown is still what the engine holds
                 else:
                     plan.resident_load(f, tau)
@@ -263,14 +269,14 @@ class _NativeStepper:
         finally:
             if self.fused_events is not None:
                 plan.set_fused_events(None, None)
-        self._carry = ("resident-pending", tau)
+        self._carry = ("resident-pending", key)
         flow._f, flow._f_next = None, None                    # nobody may see the buffers until the pass is done
 
         def finish():
             f, nxt, _ = self._lazy
             result = plan.resident_store(nxt)                 # the buffer shown last keeps its content
             self._lazy = None
-            self._carry = ("resident", _version(result), tau)
+            self._carry = ("resident", _version(result), key)
             return result, f
 
         def drop():                                           # flow.f was assigned while the pass was pending

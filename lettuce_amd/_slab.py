@@ -389,7 +389,7 @@ class SlabSimulation:
 
     ``flow`` is built on ``slab.extended_resolution`` with ``slab=slab`` (so that its initial
     condition and its boundary masks equal the global ones on this rank's planes); ``collision``
-    is a BGK / KBC / NoCollision object.  Boundaries may be bounce-back, equilibrium (uniform or with
+    is a BGK / KBC / Smagorinsky / NoCollision object.  Boundaries may be bounce-back, equilibrium (uniform or with
     per-node velocity / pressure given on the extended slab) and an anti-bounce-back outlet along any axis
     (along z it lives on the rank that holds the first / last plane of the global grid, together with the
     plane next to it).  ``engine`` defaults to the HIP engine; tests inject a
@@ -435,6 +435,7 @@ class SlabSimulation:
         self.up, self.down = _crossing_sets(flow.stencil)
         desc = collision.native_generator()
         self._tau = desc.tau
+        self._constant = desc.constant      # Smagorinsky: re-read per batch like tau (else None)
         # boundaries: same ordering and masks as Simulation (built on the extended slab, then cut
         # to this rank's planes + one ghost plane per side and laid out z-slowest)
         from ._simulation import build_masks
@@ -467,6 +468,8 @@ class SlabSimulation:
                 engine.ghosts = g
             engine.set_boundaries(entries, ncm, nsm, flow.units)      # test stand-ins
         self.engine = engine
+        if self._constant is not None and not hasattr(engine, "set_smagorinsky"):
+            raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
         # [q, nx, ny, nzl + 2g] incl. the ghost planes -> [q, nzl + 2g, ny, nx]
         core = flow.f[..., h - g:h + nzl + g]
         # The slab tensors are this driver's own (the reference never sees them), so the populations need not be
@@ -713,6 +716,8 @@ class SlabSimulation:
         """n whole steps: (collide, exchange,) n - 1 or -- carrying on from the batch before -- n fused steps; the
         streaming pass that completes the last one runs when ``f`` is read (as Flow.f does on one GPU)."""
         tau = float(self._tau(self.flow))
+        if self._constant is not None:
+            self.engine.set_smagorinsky(float(self._constant(self.flow)))
         cur, nxt, carried = self._start_batch(tau)
         for _ in range(n if carried else n - 1):
             self._fused_step(cur, nxt, tau)

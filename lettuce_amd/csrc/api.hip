@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 
 #include "dispatch.hpp"
@@ -130,6 +131,7 @@ struct lt_plan {
   int tune = -1;             // cache policy: -1 = automatic
   int residency = -1;        // workgroups per CU of the big launches: -1 = automatic, 0 = no cap
   int n_cu = 0;              // compute units of the plan's device
+  double smagorinsky = 0.17; // Smagorinsky constant (lt_plan_set_smagorinsky); the reference's default
   int two_step = -1;         // lt_run: pair the fused steps (lbm2_kernel): -1 = automatic, 0 / 1
   int seg_len = 0;           // planes per workgroup of the two-step kernel, 0 = automatic
   int many = -1;             // lt_run: several steps per launch on small 2-D grids: -1 = automatic, 0 / 1
@@ -182,7 +184,7 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau; int masked, tune, shift, residency; } gkey = {};
+  struct { void *a, *b; double tau, smagorinsky; int masked, tune, shift, residency; } gkey = {};
 };
 
 namespace {
@@ -511,6 +513,8 @@ int masked_two_step_axis(const lt_plan *p) {
 }
 bool masked_two_step_ok(const lt_plan *p) { return masked_two_step_axis(p) >= 0; }
 bool canary_ok(lt_plan *p);
+const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
+                                      "edge, packed or signalling launches): slabs keep the one-step kernels";
 
 int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long pb, long long pe,
          void *stream, long long stride = 1, void *pack_lo = nullptr, void *pack_hi = nullptr) {
@@ -532,6 +536,8 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
       return fail(LT_ERR_INVALID, "two-step range [%lld, %lld) must stay in [2, %d)", pb, pe, p->n2 - 2);
     if (!p->desc.ghost_planes && (pb != 0 || pe != p->n2))
       return fail(LT_ERR_INVALID, "periodic plan: the two-step launch covers all planes");
+    if (p->desc.ghost_planes && p->desc.collision == LT_COLLISION_SMAGORINSKY)
+      return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kSmagorinskySlabs);
     if (p->masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0)))
       return fail(LT_ERR_UNSUPPORTED, "two steps per launch with boundaries: at most one anti-bounce-back outlet, at the "
                                       "last plane of the slowest memory axis (periodic plans only) or at an end of "
@@ -550,6 +556,7 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   a.p_begin = (int)pb; a.planes = (int)((pe - pb + stride - 1) / stride); a.p_stride = (int)stride;
   a.wrap2 = p->desc.ghost_planes ? 0 : 1;
   a.tau = tau > 0.0 ? tau : 1.0;
+  a.smagorinsky = p->smagorinsky;
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
   a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = mode;
   a.masked = p->masked;
@@ -611,7 +618,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
         hipEventCreateWithFlags(&p->gev_out, hipEventDisableTiming) != hipSuccess)
       return -fail(LT_ERR_HIP, "cannot create the graph stream/events");
   }
-  const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau &&
+  const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.smagorinsky == p->smagorinsky &&
                     p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
                     p->gkey.shift == p->shift;
   if (!same) {
@@ -631,7 +638,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->masked, p->tune, p->shift, p->residency};
+    p->gkey = {cur, other, tau, p->smagorinsky, p->masked, p->tune, p->shift, p->residency};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -673,6 +680,10 @@ bool two_step_possible(lt_plan *p, const char **why) {
            "exactly that outlet's";
     return false;
   }
+  if (p->desc.ghost_planes && p->desc.collision == LT_COLLISION_SMAGORINSKY) {
+    *why = kSmagorinskySlabs;
+    return false;
+  }
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
   a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = lt::kFusedTwice;
@@ -701,6 +712,8 @@ bool two_step_wanted(lt_plan *p) {
   // its multiply-adds differently in the two inlining contexts): never automatic, so that the result of n steps
   // does not depend on how the caller splits them into batches
   if (p->desc.collision == LT_COLLISION_KBC) return false;
+  // (Smagorinsky, D3Q19 fp32: bit-identical to two one-step launches and 0.279-0.309 against 0.409-0.475 ms per
+  // update at 256^3, every sample below every sample of the one-step pair: automatic like BGK)
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
   return bytes > (128ll << 20);
 }
@@ -1024,7 +1037,7 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
     return fail(LT_ERR_INVALID, "ABI version %d, library is %d", d->abi_version, LT_ABI_VERSION);
   if (d->stencil < 0 || d->stencil > 4) return fail(LT_ERR_UNSUPPORTED, "stencil %d", d->stencil);
   if (d->dtype < 0 || d->dtype > 1) return fail(LT_ERR_UNSUPPORTED, "dtype %d (fp32/fp64 only)", d->dtype);
-  if (d->collision < 0 || d->collision > 2) return fail(LT_ERR_UNSUPPORTED, "collision %d", d->collision);
+  if (d->collision < 0 || d->collision > LT_COLLISION_SMAGORINSKY) return fail(LT_ERR_UNSUPPORTED, "collision %d", d->collision);
   const Unit unit = kUnits[d->stencil][d->dtype];
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   if (d->collision == LT_COLLISION_KBC && d->stencil != LT_D2Q9 && d->stencil != LT_D3Q27)
@@ -1673,6 +1686,16 @@ int lt_plan_set_many_step(lt_plan *p, int32_t mode) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "many-step mode %d", mode);
   p->many = mode;
+  return LT_OK;
+}
+
+int lt_plan_set_smagorinsky(lt_plan *p, double constant) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (p->desc.collision != LT_COLLISION_SMAGORINSKY)
+    return fail(LT_ERR_INVALID, "the plan's collision is %d, not Smagorinsky", p->desc.collision);
+  if (!(constant >= 0.0) || !std::isfinite(constant))
+    return fail(LT_ERR_INVALID, "Smagorinsky constant %g (finite and >= 0)", constant);
+  p->smagorinsky = constant;
   return LT_OK;
 }
 

@@ -18,6 +18,7 @@ struct StepArgs {
   int p_begin2, planes2;  // kFusedTwice: optional second range of output planes
   int wrap2;
   double tau;
+  double smagorinsky;    // Smagorinsky constant (collision 3); the units square it
   const unsigned char *node;
   const unsigned *nsm_bits;
   const void *bt;        // BoundaryTable<T>* (device)
@@ -80,6 +81,15 @@ LT_DECLARE_TWICE(d3q27_f32)
 LT_DECLARE_TWICE(d3q27_f64)
 // ... and those with separate producer and consumer waves, instantiated by inst3_<tag>.hip
 int roles_d3q19_f32(const StepArgs &, bool name_only, const char **name);
+
+// ... and the one-step Smagorinsky kernels of the 3-D units, instantiated by inst4_<tag>.hip
+#define LT_DECLARE_SMAG(tag) int smag_##tag(const StepArgs &, bool name_only, const char **name);
+LT_DECLARE_SMAG(d3q15_f32)
+LT_DECLARE_SMAG(d3q15_f64)
+LT_DECLARE_SMAG(d3q19_f32)
+LT_DECLARE_SMAG(d3q19_f64)
+LT_DECLARE_SMAG(d3q27_f32)
+LT_DECLARE_SMAG(d3q27_f64)
 
 LT_DECLARE_UNIT(d1q3_f32)
 LT_DECLARE_UNIT(d1q3_f64)

@@ -63,6 +63,7 @@ struct KParams {
   unsigned nvec_total;       // threads doing work: nv0 * n1 * planes
   T tau_inv;                 // BGK: 1/tau
   T beta, inv_beta;          // KBC: 1/(2 tau), 1/beta
+  T tau, smag_c2;            // Smagorinsky: tau and the squared constant
   const unsigned char *node; // [N] boundary index | 0x80 if any no-streaming bit (or null)
   const unsigned *nsm_bits;  // [N] bit q set: population q keeps its value (or null)
   const BoundaryTable<T> *bt;
@@ -474,6 +475,74 @@ __device__ __forceinline__ void collide_kbc(T (&f)[S::Q][VEC], T beta, T inv_bet
   });
 }
 
+// Smagorinsky LES on top of BGK (lettuce/ext/_collision/smagorinsky_collision.py:19-36): the relaxation time of a
+// node grows with the second moments of its non-equilibrium part,
+//   Pi_ab = sum_q e_qa e_qb (f_q - feq_q),  S_shear = Pi / (2 rho cs^2),  nu = (tau - 1/2) / 3,
+//   twice:  S = S_shear / tau_eff;  nu_t = C^2 (S : S);  tau_eff = 3 (nu + nu_t) + 1/2     (from tau_eff = tau),
+// then f - (1 / tau_eff) (f - feq).  The contraction runs over all d x d components, so the off-diagonal ones count
+// twice, and nu_t has no square root: the reference's model, kept as it is.  rho, u and feq are BGK's, bit for bit.
+// The six distinct moments are raw sums over the opposite pairs (equal e_a e_b, as in kbc_s); S : S is formed as
+// (Pi / D : Pi / D) / tau_eff^2 with one division by D = 2 rho cs^2 and one reciprocal per iteration, where the
+// reference divides the d x d components each time: same value up to rounding, so -- like KBC -- this collision is
+// compared with the reference at rounding level.  No contraction by the compiler (every kernel it is inlined into
+// returns the same bits); the two multiply-adds of the iteration are written as fma_t.
+// The Q differences f - feq stay in registers for the relaxation (the two-step kernel of D3Q19 fp32 fits its
+// 168 VGPRs with them, without scratch: DESIGN.md section 4).
+template <typename T, class S, int LAYOUT, int VEC, int k>
+__device__ __forceinline__ void collide_smagorinsky(T (&f)[S::Q][VEC], T tau, T c2) {
+#pragma clang fp contract(off)
+  T rho, j[3], u[3];
+  moments<T, S, LAYOUT, VEC, k>(f, rho, j);
+  u[0] = j[0] / rho; u[1] = j[1] / rho; u[2] = j[2] / rho;
+  const T uxu = square_norm<S, LAYOUT>(u);
+  T x[S::Q];
+  T pair[S::Q];                                   // [q], q < opposite(q): x_q + x_opposite
+  for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+    constexpr int q = decltype(qc)::value;
+    constexpr int o = S::OPP[q];
+    const T d = f[q][k] - feq;
+    x[q] = d;
+    if constexpr (q < o) pair[q] = d;             // (for_each_feq hands out q, then its opposite)
+    else if constexpr (q > o) pair[o] = pair[o] + d;
+  });
+  T xx = T(0), yy = T(0), zz = T(0), xy = T(0), xz = T(0), yz = T(0);
+  static_for<S::Q>([&](auto qc) {
+    constexpr int q = decltype(qc)::value;
+    if constexpr (q < S::OPP[q]) {
+      constexpr int ex = S::E[q][0], ey = S::E[q][1], ez = S::E[q][2];
+      const T v = pair[q];
+      if constexpr (ex != 0) xx += v;
+      if constexpr (ey != 0) yy += v;
+      if constexpr (ez != 0) zz += v;
+      if constexpr (ex * ey > 0) xy += v; else if constexpr (ex * ey < 0) xy -= v;
+      if constexpr (ex * ez > 0) xz += v; else if constexpr (ex * ez < 0) xz -= v;
+      if constexpr (ey * ez > 0) yz += v; else if constexpr (ey * ez < 0) yz -= v;
+    }
+  });
+  const T inv_d = T(1) / (T(2) * rho * T(kCs2));
+  xx = xx * inv_d;
+  T ss = xx * xx;                                 // S_shear : S_shear
+  if constexpr (S::D > 1) {
+    yy = yy * inv_d; xy = xy * inv_d;
+    ss = ss + yy * yy + T(2) * (xy * xy);
+  }
+  if constexpr (S::D > 2) {
+    zz = zz * inv_d; xz = xz * inv_d; yz = yz * inv_d;
+    ss = ss + zz * zz + T(2) * (xz * xz) + T(2) * (yz * yz);
+  }
+  const T nu = (tau - T(0.5)) / T(3);
+  T r = T(1) / tau;                               // 1 / tau_eff
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const T nu_eff = fma_t(c2, ss * (r * r), nu);
+    r = T(1) / fma_t(nu_eff, T(3), T(0.5));
+  }
+  static_for<S::Q>([&](auto qc) {
+    constexpr int q = decltype(qc)::value;
+    f[q][k] = f[q][k] - r * x[q];
+  });
+}
+
 // ---- boundaries -------------------------------------------------------------------------
 // BounceBackBoundary: f <- f[opposite] (lettuce/ext/_boundary/bounce_back_boundary.py:17-18)
 template <typename T, class S, int VEC, int k>
@@ -586,6 +655,7 @@ __device__ __forceinline__ void neighbour_moments(const KParams<T> &p, int c0, i
       if (b == 0) {
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(g, p.tau_inv);
         if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(g, p.beta, p.inv_beta);
+        if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(g, p.tau, p.smag_c2);
       }
       for (int t = 1; t < slot; ++t) {
         const int kind = p.bt->kind[t];
@@ -735,6 +805,7 @@ __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
       if (b == 0) {
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(f, p.tau_inv);
         if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(f, p.beta, p.inv_beta);
+        if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(f, p.tau, p.smag_c2);
       }
       if constexpr (MASKED)
         apply_boundaries<T, S, LAYOUT, STREAM, 1, 0, COLL, ABBD>(p, b, c0, c1, c2, own, f, lane_slot, lane_rho, lane_j);
@@ -844,7 +915,8 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
   constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
   constexpr int NU = B::template count<LAYOUT, 1>(), NC = B::template count<LAYOUT, 0>(),
                 ND = B::template count<LAYOUT, -1>();
-  static_assert(COLL == 0 || COLL == 1, "two-step kernel: streaming only or BGK");
+  static_assert(COLL == 0 || COLL == 1 || COLL == 3, "two-step kernel: streaming only, BGK or Smagorinsky");
+  static_assert(COLL != 3 || (SCHED == 0 && MODE == 0), "Smagorinsky: the plain one-role sweep only");
   __shared__ T lds_u[4][NU][NI];
   __shared__ T lds_c[3][NC][NI];
   __shared__ T lds_d[2][ND][NI];
@@ -1059,6 +1131,8 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
     if (in_a) {
       if constexpr (COLL == 1)
         static_for<NPT>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau_inv); });
+      if constexpr (COLL == 3)
+        static_for<NPT>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau, p.smag_c2); });
       static_for<S::Q>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
@@ -1091,6 +1165,8 @@ lbm2_kernel(const KParams<T> p, const int seg_len) {
     if (in_b) {
       if constexpr (COLL == 1)
         static_for<NPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau_inv); });
+      if constexpr (COLL == 3)
+        static_for<NPB>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau, p.smag_c2); });
     }
   };
   // packing: this workgroup writes halo messages (PACK kernels; a launch that covers a whole slab runs the

@@ -17,6 +17,8 @@
 // 3 = the two-step launches with separate producer and consumer waves (the kernel's SCHED = 1) of a unit that has
 // them (LT_HAS_ROLES, inst3_<tag>.hip): again an object of its own, because that schedule wants another scheduler
 // setting than the one-role kernels beside it (Makefile)
+// 4 = the one-step kernels of the Smagorinsky collision of a 3-D unit (inst4_<tag>.hip): an object of its own so that
+// the build takes no longer than before (the D3Q27 fp32 unit with its KBC kernels is the longest job)
 #ifndef LT_PART
 #define LT_PART 0
 #endif
@@ -41,7 +43,7 @@ constexpr int kTwiceW = 256 / (int)sizeof(T);
 constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
                         : (sizeof(T) == 4 && kTwicePerNode * (kTwiceW + 2) * 6 <= 160 * 1024 ? 4 : 0);
 
-#if LT_PART < 2
+#if LT_PART < 2 || LT_PART == 4
 
 // one node per thread: the kernels' VEC = 1, SHIFT = 0
 template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
@@ -78,6 +80,8 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   const double beta = 1. / (2 * a.tau);          // kbc_collision.py:97-99
   p.beta = (T)beta;
   p.inv_beta = (T)(1. / beta);
+  p.tau = (T)a.tau;
+  p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
   p.node = a.node;
   p.nsm_bits = a.nsm_bits;
   p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
@@ -95,16 +99,76 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   return (int)hipGetLastError();
 }
 
-#endif  // LT_PART < 2
+// Product kernels: one node per thread (VEC = 1).  Measured on MI355X (profiles/r01_variant_sweep*):
+// for this 2q-stream kernel 8 waves/SIMD of scalar accesses beat 16-byte accesses at 3-4
+// waves/SIMD by 8-13 %, and nontemporal stores (+3-4 %) and loads (+1.6 %) help once the
+// populations exceed the caches (TUNE 3).  TUNE 0 (cached accesses) is kept for grids that fit in
+// L2 / Infinity Cache.
+#define LT_TRY(LAYOUT, COLL, MODE, MASKED)                                                       \
+  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked == MASKED) {            \
+    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 0>(a, name_only, name); \
+    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 3>(a, name_only, name); \
+  }
+
+// slab boundary-plane launch with fused halo packing (fused mode, slab layout)
+#define LT_TRY_PACK(COLL, MASKED)                                                               \
+  if (a.layout == 1 && coll == COLL && a.mode == kFused && a.masked == MASKED &&                 \
+      a.pack_lo != nullptr && a.abb_depth == 0)                                                                      \
+    return launch<1, COLL, kFused, (MASKED != 0), 0, true>(a, name_only, name);
+
+// plans with two anti-bounce-back outlets (kernels.hpp, neighbour_moments DEPTH 1): masked kernels that
+// apply boundaries, i.e. fused and collide-only
+#define LT_TRY_TWO_OUTLETS(LAYOUT, COLL, MODE)                                                  \
+  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 1) \
+    return launch<LAYOUT, COLL, MODE, true, 0, false, 1>(a, name_only, name);
+
+// outlets on all three axes of a 3-D flow (their planes meet in corners: DEPTH 2), reference layout
+#define LT_TRY_THREE_AXES(COLL, MODE)                                                           \
+  if (a.layout == 0 && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 2) \
+    return launch<0, COLL, MODE, true, 0, false, 2>(a, name_only, name);
+
+#define LT_COLLISION_SET(LAYOUT, COLL, MASKED) \
+  LT_TRY(LAYOUT, COLL, kFused, MASKED)         \
+  LT_TRY(LAYOUT, COLL, kCollideOnly, MASKED)
 
 #if LT_PART != 1
+// The one-step kernels of the Smagorinsky collision (COLL 3): every variant BGK has.  The 3-D units build them in
+// an object of their own (LT_PART 4, inst4_<tag>.hip), beside the rest.
+int one_step_smagorinsky(const StepArgs &a, bool name_only, const char **name) {
+  const int coll = a.coll;
+  if (coll != 3 || (a.mode != kFused && a.mode != kCollideOnly)) return kNoKernel;
+#if LT_IS_3D
+  LT_TRY_THREE_AXES(3, kFused) LT_TRY_THREE_AXES(3, kCollideOnly)
+#endif
+  if (a.abb_depth > 1) return kNoKernel;
+  LT_TRY_TWO_OUTLETS(0, 3, kFused) LT_TRY_TWO_OUTLETS(0, 3, kCollideOnly)
+#if LT_IS_3D
+  LT_TRY_TWO_OUTLETS(1, 3, kFused) LT_TRY_TWO_OUTLETS(1, 3, kCollideOnly)
+#endif
+  LT_COLLISION_SET(0, 3, 0)
+  LT_COLLISION_SET(0, 3, 1)
+#if LT_IS_3D
+  LT_TRY_PACK(3, 0)
+  LT_TRY_PACK(3, 1)
+  LT_COLLISION_SET(1, 3, 0)
+  LT_COLLISION_SET(1, 3, 1)
+#endif
+  return kNoKernel;
+}
+#endif  // LT_PART != 1
+
+#endif  // LT_PART < 2 || LT_PART == 4
+
+#if LT_PART == 2 || LT_PART == 3 || LT_PART == 0
 // Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
 // returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
 // one node per thread and per block: the kernel's NPT = NPB = 1
 // SCHED 1: separate producer and consumer waves (twostep_roles.hpp)
+// Smagorinsky (COLL 3): the plain one-role sweep of D3Q19 fp32
 template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
 int launch_twice(const StepArgs &a, bool name_only, const char **name) {
-  if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1)) {
+  if constexpr (S::D == 3 && T0 > 0 &&
+                (COLL == 0 || COLL == 1 || (COLL == 3 && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
     using B = TwoStep<T, S, T0, T1>;
     if (name_only) {
       static char buf[96];
@@ -132,6 +196,8 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
     p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
     p.No = a.stride_out > 0 ? a.stride_out : p.N;
     p.tau_inv = (T)(1.0 / a.tau);
+    p.tau = (T)a.tau;
+    p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);
     p.nb = a.shift == 3 ? 1 : (a.shift == 4 ? 2 : 0);   // A/B: 1 = no XCD-aware renumbering of the workgroups, 2 = per segment layer
     p.pack_lo = static_cast<T *>(a.pack_lo);
     p.pack_hi = static_cast<T *>(a.pack_hi);
@@ -174,7 +240,10 @@ int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
 #endif
     if (a.layout == 0 && coll == 0) return launch_twice<0, 0, W, R>(a, name_only, name);
     if (a.layout == 0 && coll == 1) return launch_twice<0, 1, W, R>(a, name_only, name);
+    if (a.layout == 0 && coll == 3) return launch_twice<0, 3, W, R>(a, name_only, name);
 #if LT_IS_3D
+    // Smagorinsky has the plain sweep only: no edge launch with packing, no signalling launch
+    if (coll == 3 && (a.pack_lo || a.pack_hi || a.signal)) return kNoKernel;
     if (a.layout == 1 && (a.pack_lo || a.pack_hi)) {     // slab edge launch with fused halo packing
       if (coll == 0) return launch_twice<1, 0, W, R, 1>(a, name_only, name);
       if (coll == 1) return launch_twice<1, 1, W, R, 1>(a, name_only, name);
@@ -185,12 +254,13 @@ int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
     }
     if (a.layout == 1 && coll == 0) return launch_twice<1, 0, W, R>(a, name_only, name);
     if (a.layout == 1 && coll == 1) return launch_twice<1, 1, W, R>(a, name_only, name);
+    if (a.layout == 1 && coll == 3) return launch_twice<1, 3, W, R>(a, name_only, name);
 #endif
   }
   return kNoKernel;
 }
 #endif  // LT_PART == 3, else
-#endif  // LT_PART != 1
+#endif  // LT_PART 0, 2, 3
 
 #if LT_PART < 2
 // Two fused steps per launch for plans with boundaries (twostep_masked.hpp, lbm2m_kernel): whole periodic
@@ -365,38 +435,6 @@ int launch_many(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
-// Product kernels: one node per thread (VEC = 1).  Measured on MI355X (profiles/r01_variant_sweep*):
-// for this 2q-stream kernel 8 waves/SIMD of scalar accesses beat 16-byte accesses at 3-4
-// waves/SIMD by 8-13 %, and nontemporal stores (+3-4 %) and loads (+1.6 %) help once the
-// populations exceed the caches (TUNE 3).  TUNE 0 (cached accesses) is kept for grids that fit in
-// L2 / Infinity Cache.
-#define LT_TRY(LAYOUT, COLL, MODE, MASKED)                                                       \
-  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked == MASKED) {            \
-    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 0>(a, name_only, name); \
-    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 3>(a, name_only, name); \
-  }
-
-// slab boundary-plane launch with fused halo packing (fused mode, slab layout)
-#define LT_TRY_PACK(COLL, MASKED)                                                               \
-  if (a.layout == 1 && coll == COLL && a.mode == kFused && a.masked == MASKED &&                 \
-      a.pack_lo != nullptr && a.abb_depth == 0)                                                                      \
-    return launch<1, COLL, kFused, (MASKED != 0), 0, true>(a, name_only, name);
-
-// plans with two anti-bounce-back outlets (kernels.hpp, neighbour_moments DEPTH 1): masked kernels that
-// apply boundaries, i.e. fused and collide-only
-#define LT_TRY_TWO_OUTLETS(LAYOUT, COLL, MODE)                                                  \
-  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 1) \
-    return launch<LAYOUT, COLL, MODE, true, 0, false, 1>(a, name_only, name);
-
-// outlets on all three axes of a 3-D flow (their planes meet in corners: DEPTH 2), reference layout
-#define LT_TRY_THREE_AXES(COLL, MODE)                                                           \
-  if (a.layout == 0 && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 2) \
-    return launch<0, COLL, MODE, true, 0, false, 2>(a, name_only, name);
-
-#define LT_COLLISION_SET(LAYOUT, COLL, MASKED) \
-  LT_TRY(LAYOUT, COLL, kFused, MASKED)         \
-  LT_TRY(LAYOUT, COLL, kCollideOnly, MASKED)
-
 int dispatch(const StepArgs &a, bool name_only, const char **name) {
   const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
   if (a.mode == kFusedMany) {
@@ -453,6 +491,13 @@ int dispatch(const StepArgs &a, bool name_only, const char **name) {
 #endif
     }
     return kNoKernel;
+  }
+  if (coll == 3) {
+#if LT_PART == 1
+    return LT_CAT(smag_, LT_TAG)(a, name_only, name);       // inst4_<tag>.hip
+#else
+    return one_step_smagorinsky(a, name_only, name);
+#endif
   }
 #if LT_IS_3D
   LT_TRY_THREE_AXES(0, kFused) LT_TRY_THREE_AXES(0, kCollideOnly)
@@ -610,6 +655,10 @@ int LT_CAT(twice_, LT_TAG)(const StepArgs &a, bool name_only, const char **name)
 #elif LT_PART == 3
 int LT_CAT(roles_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
   return twice_roles(a, name_only, name);
+}
+#elif LT_PART == 4
+int LT_CAT(smag_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
+  return one_step_smagorinsky(a, name_only, name);
 }
 #else
 int LT_CAT(step_, LT_TAG)(const StepArgs &a) { return dispatch(a, false, nullptr); }

@@ -1,10 +1,10 @@
-"""Collision operators on the hot path: BGK, KBC (D2Q9 / D3Q27) and NoCollision.
+"""Collision operators on the hot path: BGK, KBC (D2Q9 / D3Q27), Smagorinsky (every lattice) and NoCollision.
 
 Each ``__call__`` is a pure whole-field function ``flow -> tensor`` usable outside a
 ``Simulation`` (the reference's tests call ``collision(flow)`` directly).  On a native context
 and for the flow's grid-shaped state it is one launch of the engine's collide kernel;
-otherwise the reference's torch expressions are evaluated.  TRT / MRT / regularised /
-Smagorinsky collisions and forcing schemes are out of scope.
+otherwise the reference's torch expressions are evaluated.  TRT / MRT / regularised
+collisions and forcing schemes on the engine are out of scope.
 """
 import warnings
 from typing import AnyStr, Optional
@@ -15,11 +15,13 @@ from .._simulation import Collision
 from ..native_desc import NativeCollision
 from ..util import LettuceException
 
-__all__ = ["BGKCollision", "KBCCollision", "KBCCollision2D", "KBCCollision3D", "NoCollision"]
+__all__ = ["BGKCollision", "KBCCollision", "KBCCollision2D", "KBCCollision3D", "NoCollision",
+           "SmagorinskyCollision"]
 
 
-def _engine_collide(flow, kind, tau):
-    """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped."""
+def _engine_collide(flow, kind, tau, constant=None):
+    """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``constant``: the
+    Smagorinsky constant, a per-launch setting of the kind's one plan (handed over before every collide)."""
     if flow._engine_plan(flow.f) is None:
         return None
     plans = flow.__dict__.setdefault("_collision_plans", {})
@@ -27,6 +29,8 @@ def _engine_collide(flow, kind, tau):
         from .._native import Plan
         plans[kind] = Plan(type(flow.stencil).__name__, flow.context.dtype, kind, flow.resolution,
                            device=flow.f.device)
+    if constant is not None:
+        plans[kind].set_smagorinsky(constant)
     return plans[kind].collide(flow.f, torch.empty_like(flow.f), tau)
 
 
@@ -168,6 +172,58 @@ class KBCCollision3D(KBCCollision):
     def __init__(self, tau: float = None):
         warnings.warn("KBCCollision3D is is deprecated! Use KBCCollision instead!")
         super().__init__()
+
+
+class SmagorinskyCollision(Collision):
+    """Smagorinsky large-eddy model on top of BGK (lettuce/ext/_collision/smagorinsky_collision.py:7-42): the
+    relaxation time of a node grows with the second moments of its non-equilibrium populations, through two
+    fixed-point iterations.  The reference's algorithm is kept as it is, including that S:S enters the eddy
+    viscosity without a square root and that the contraction counts the off-diagonal components twice.
+
+    ``tau_eff`` is ``tau`` until the torch path has run, then the per-node field of its last call (as in the
+    reference); the engine's kernel keeps it in registers and does not set it."""
+
+    def __init__(self, tau, smagorinsky_constant=0.17, force: Optional["Force"] = None):
+        self.force = force
+        self.tau = tau
+        self.iterations = 2
+        self.tau_eff = tau
+        self.constant = smagorinsky_constant
+
+    def __call__(self, flow: "Flow") -> torch.Tensor:
+        if self.native_available():
+            out = _engine_collide(flow, "smagorinsky", self.tau, self.constant)
+            if out is not None:
+                return out
+        rho = flow.rho()
+        u_eq = 0 if self.force is None else self.force.u_eq(flow)
+        u = flow.u() + u_eq
+        feq = flow.equilibrium(flow, rho, u)
+        f_neq = flow.f - feq
+        if f_neq.is_cuda:       # no BLAS on device tensors (see _flow.local_contract)
+            from .._flow import local_contract
+            e, d = flow.torch_stencil.e, flow.stencil.d
+            ee = torch.einsum("qa,qb->abq", e, e).reshape(d * d, -1)
+            s_shear = local_contract(ee, f_neq).reshape([d, d] + list(f_neq.shape[1:]))
+        else:
+            s_shear = flow.shear_tensor(f_neq)
+        s_shear /= (2.0 * rho * flow.stencil.cs ** 2)
+        self.tau_eff = self.tau
+        nu = (self.tau - 0.5) / 3.0
+        for _ in range(self.iterations):
+            s = s_shear / self.tau_eff
+            s = (s * s).sum(dim=(0, 1)) if s.is_cuda else flow.einsum("ab,ab->", [s, s])
+            nu_t = self.constant ** 2 * s
+            nu_eff = nu + nu_t
+            self.tau_eff = nu_eff * 3.0 + 0.5
+        si = 0 if self.force is None else self.force.source_term(u)
+        return flow.f - 1.0 / self.tau_eff * (flow.f - feq) + si
+
+    def native_available(self) -> bool:
+        return self.force is None and self.iterations == 2
+
+    def native_generator(self) -> "NativeCollision":
+        return NativeCollision("smagorinsky", tau=lambda flow: self.tau, constant=lambda flow: self.constant)
 
 
 class NoCollision(Collision):

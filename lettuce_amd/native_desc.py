@@ -19,7 +19,7 @@ class NativeEquilibrium:
 
 @dataclass
 class NativeCollision:
-    kind: str                                  # 'none' | 'bgk' | 'kbc'
+    kind: str                                  # 'none' | 'bgk' | 'kbc' | 'smagorinsky'
     # relaxation time used for the next batch of steps; evaluated per call because the
     # reference re-reads collision.tau on every invocation
     # (lettuce/cuda_native/ext/_collision/bgk_collision.py:30)
@@ -27,6 +27,9 @@ class NativeCollision:
     # "exact": the reference's floating-point operations one for one (the default; bit-identical periodic BGK flows),
     # the only arithmetic the engine has ("fast" lost its A/B: DESIGN.md section 4)
     arithmetic: str = "exact"
+    # 'smagorinsky': the constant, evaluated per batch like tau (the reference reads collision.constant on every
+    # call, lettuce/ext/_collision/smagorinsky_collision.py:32); None for the other kinds
+    constant: Optional[Callable[["Flow"], float]] = None
 
 
 @dataclass
