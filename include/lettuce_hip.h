@@ -290,7 +290,9 @@ int lt_kinetic_energy(lt_plan *plan, const void *f_dev, double *out_dev, void *s
 int lt_mass(lt_plan *plan, const void *f_dev, double *out_dev, void *stream);
 
 /* *out_dev = max over nodes of |u| in lattice units (MaximumVelocity observable,
- * lettuce/ext/_reporter/observable_reporter.py:27-31; the pu scaling stays on the host). */
+ * lettuce/ext/_reporter/observable_reporter.py:27-31; the pu scaling stays on the host).  The maximum
+ * propagates NaN as torch.max does: if |u| of any node is NaN (a diverged run) the result is NaN, not the
+ * largest finite value.  Ghost planes are excluded. */
 int lt_max_velocity(lt_plan *plan, const void *f_dev, double *out_dev, void *stream);
 
 /* Non-equilibrium initialisation (lettuce/_flow.py:309-336, Krueger et al. 2017): f_dev [q][N] =
@@ -300,7 +302,9 @@ int lt_max_velocity(lt_plan *plan, const void *f_dev, double *out_dev, void *str
  * DEFAULT dtype (an fp32-rounded cs^2 even in an fp64 run, _flow.py:328-330).  rho_dev [N] and u_dev
  * [d][N] (lattice units, logical component order) are the moments of the equilibrium populations, as
  * Flow.rho() / Flow.u() give them; one launch, nothing else is materialised (the reference builds
- * [d][d][N] gradients, Pi1 and two [q][N] fields).  Reference layout, periodic along every axis. */
+ * [d][d][N] gradients, Pi1 and two [q][N] fields).  Reference layout, periodic along every axis: the
+ * shifted indices wrap modulo the extent like torch.roll, for every extent >= 1 (with an extent of 1 or 2 the
+ * six taps alias the same one or two nodes). */
 int lt_init_fneq(lt_plan *plan, const void *rho_dev, const void *u_dev, double tau, double identity_cs2,
                  void *f_dev, void *stream);
 
@@ -310,7 +314,8 @@ int lt_init_fneq(lt_plan *plan, const void *rho_dev, const void *u_dev, double t
  * per node in the working dtype as the reference's whole-field expression and accumulated in fp64
  * with a fixed reduction order; the factor dx^d stays on the host.  Two launches: u [d][N] into
  * u_scratch_dev (d * N scalars of the plan's dtype, caller-owned), then the stencil reduction over
- * it.  2-D / 3-D, reference layout, periodic domains only (as the reference). */
+ * it.  2-D / 3-D, reference layout, periodic domains only (as the reference).  The shifted indices wrap
+ * modulo the extent like torch.roll, for every extent >= 1. */
 int lt_enstrophy(lt_plan *plan, const void *f_dev, void *u_scratch_dev, double u_scale, double inv_dx,
                  double *out_dev, void *stream);
 
@@ -327,7 +332,8 @@ int lt_mass_interior(lt_plan *plan, const void *f_dev, const uint8_t *no_mass_ma
  *                     units) <- u of the plan's nz + 2 g planes, written at planes [3 - g, 3 + nz + g); the caller
  *                     then fills planes [0, 3) and [nz + 3, nz + 6) with the neighbours' planes (6th-order
  *                     differences reach three planes: a velocity halo exchange, host side);
- *  lt_slab_enstrophy  *out_dev = sum over the rank's own nodes of |curl(u_scale * u)|^2, as lt_enstrophy;
+ *  lt_slab_enstrophy  *out_dev = sum over the rank's own nodes of |curl(u_scale * u)|^2, as lt_enstrophy (x and y
+ *                     wrap modulo nx / ny >= 1; nothing wraps along z, where the neighbours' planes are read);
  *  lt_slab_mass_interior  *out_dev = the rank's share of lt_mass_interior: own planes only, y and the GLOBAL z index
  *                     (z_begin + local plane, of nz_global) off their first / last value; no_mass_mask_dev is uint8 per
  *                     node of the plan (ghost planes included, as f) or null.

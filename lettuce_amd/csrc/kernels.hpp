@@ -1585,6 +1585,13 @@ __global__ void __launch_bounds__(kThreads) equilibrium_kernel(const T *__restri
   });
 }
 
+// periodic index of a shifted coordinate: a modulo n in [0, n) for every extent n >= 1 and any shift, as
+// torch.roll wraps (an extent of 1 or 2 is smaller than the stencil's reach of 3)
+__device__ __forceinline__ int wrap_index(int a, int n) {
+  a %= n;
+  return a < 0 ? a + n : a;
+}
+
 // f = feq(rho, u) - w_q Pi1:Q_q  -- initialize_f_neq (lettuce/_flow.py:309-336), reference layout,
 // periodic.  S[a][b] = d u_a / d x_b: torch_gradient's 6th-order central differences (dx = 1), term
 // order of the reference's expression; Pi1 = ((1.0 tau) rho) S / cs^2; Q_q,ab = e_qa e_qb - eye_cs2 d_ab.
@@ -1609,9 +1616,9 @@ __global__ void __launch_bounds__(kThreads) fneq_kernel(const T *__restrict__ rh
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       int a0 = c0, a1 = c1, a2 = c2;
-      if (m == 0) { a0 = c0 - sh[k]; a0 = a0 < 0 ? a0 + n0 : (a0 >= n0 ? a0 - n0 : a0); }
-      if (m == 1) { a1 = c1 - sh[k]; a1 = a1 < 0 ? a1 + n1 : (a1 >= n1 ? a1 - n1 : a1); }
-      if (m == 2) { a2 = c2 - sh[k]; a2 = a2 < 0 ? a2 + n2 : (a2 >= n2 ? a2 - n2 : a2); }
+      if (m == 0) { a0 = c0 - sh[k]; a0 = wrap_index(a0, n0); }
+      if (m == 1) { a1 = c1 - sh[k]; a1 = wrap_index(a1, n1); }
+      if (m == 2) { a2 = c2 - sh[k]; a2 = wrap_index(a2, n2); }
       at[k] = ((long long)a2 * n1 + a1) * n0 + a0;
     }
 #pragma unroll
@@ -1651,7 +1658,11 @@ __global__ void __launch_bounds__(kThreads) fneq_kernel(const T *__restrict__ rh
   });
 }
 
-// wavefront (64-lane) + workgroup reduction of a double (sum, or max when MAX); result valid in
+// maximum that propagates NaN like torch.max: a NaN on either side wins and then stays (`m > acc` alone is false
+// for a NaN m, which would drop it); without a NaN the larger value, as before
+__device__ __forceinline__ double nan_max(double m, double acc) { return (m > acc || m != m) ? m : acc; }
+
+// wavefront (64-lane) + workgroup reduction of a double (sum, or max when MAX: NaN-propagating); result valid in
 // thread 0
 template <bool MAX = false>
 __device__ __forceinline__ double block_sum(double v) {
@@ -1659,7 +1670,7 @@ __device__ __forceinline__ double block_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const double o = __shfl_down(v, off);
-    v = MAX ? (o > v ? o : v) : v + o;
+    v = MAX ? nan_max(o, v) : v + o;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) part[wave] = v;
@@ -1667,7 +1678,7 @@ __device__ __forceinline__ double block_sum(double v) {
   double s = 0.0;
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) s = MAX ? (part[w] > s ? part[w] : s) : s + part[w];
+    for (int w = 0; w < kThreads / 64; ++w) s = MAX ? nan_max(part[w], s) : s + part[w];
   }
   return s;
 }
@@ -1697,7 +1708,7 @@ __global__ void __launch_bounds__(kThreads) reduce_kernel(const T *__restrict__ 
     } else {
       const T ux = j[0] / rho, uy = j[1] / rho, uz = j[2] / rho;
       const double m = (double)sqrt(ux * ux + uy * uy + uz * uz);
-      acc = m > acc ? m : acc;
+      acc = nan_max(m, acc);
     }
   }
   const double s = block_sum<MODE == 2>(acc);
@@ -1732,9 +1743,9 @@ __global__ void __launch_bounds__(kThreads) enstrophy_kernel(const T *__restrict
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         int a0 = c0, a1 = c1, a2 = c2;
-        if (m == 0) { a0 = c0 - sh[k]; a0 = a0 < 0 ? a0 + n0 : (a0 >= n0 ? a0 - n0 : a0); }
-        if (m == 1) { a1 = c1 - sh[k]; a1 = a1 < 0 ? a1 + n1 : (a1 >= n1 ? a1 - n1 : a1); }
-        if (m == 2) { a2 = c2 - sh[k]; if (!SLAB) a2 = a2 < 0 ? a2 + n2 : (a2 >= n2 ? a2 - n2 : a2); }
+        if (m == 0) { a0 = c0 - sh[k]; a0 = wrap_index(a0, n0); }
+        if (m == 1) { a1 = c1 - sh[k]; a1 = wrap_index(a1, n1); }
+        if (m == 2) { a2 = c2 - sh[k]; if (!SLAB) a2 = wrap_index(a2, n2); }
         const T v = w[k] * (uc[((long long)a2 * n1 + a1) * n0 + a0] * scale);
         r = k == 0 ? v : r + v;
       }
@@ -1804,7 +1815,7 @@ template <bool MAX>
 static __global__ void __launch_bounds__(kThreads) finish_sum_kernel(const double *__restrict__ partial,
                                                               int n, double *__restrict__ out) {
   double acc = 0.0;
-  for (int i = threadIdx.x; i < n; i += kThreads) acc = MAX ? (partial[i] > acc ? partial[i] : acc) : acc + partial[i];
+  for (int i = threadIdx.x; i < n; i += kThreads) acc = MAX ? nan_max(partial[i], acc) : acc + partial[i];
   const double s = block_sum<MAX>(acc);
   if (threadIdx.x == 0) *out = s;
 }

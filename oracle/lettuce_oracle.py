@@ -525,10 +525,16 @@ def initialize_from_pu(p, u, lat: Lattice, units: Units, dtype, fneq=True):
     f = quadratic_equilibrium(rho0, u0, e, w)
     if not fneq:
         return f
-    rho = density(f)
-    uu = velocity(f, e)
+    return f_neq_initialisation(density(f), velocity(f, e), units.tau, lat, dtype)
+
+
+def f_neq_initialisation(rho, uu, tau, lat: Lattice, dtype):
+    """initialize_f_neq (lettuce/_flow.py:309-336) from the moments ``rho`` [1, *res] and ``uu`` [d, *res] of the
+    equilibrium populations: feq(rho, uu) - w_q Pi1:Q_q.  Periodic for every extent >= 1: torch.roll wraps modulo the
+    extent, so with an extent of 1 or 2 the six taps alias the same one or two nodes."""
+    e, w = lattice_tensors(lat, dtype)
     S = torch.cat([periodic_gradient6(uu[a])[None, ...] for a in range(lat.d)])
-    pi1 = 1.0 * units.tau * rho * S / CS ** 2
+    pi1 = 1.0 * tau * rho * S / CS ** 2
     # the reference builds the identity with torch's default dtype (float32), so the
     # cs^2 on the diagonal is rounded to fp32 even in an fp64 run (_flow.py:328-330)
     Q = (torch.einsum("ia,ib->iab", e, e) - torch.eye(lat.d) * CS ** 2)

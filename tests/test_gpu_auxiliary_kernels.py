@@ -1,0 +1,483 @@
+"""The auxiliary kernels of the HIP engine -- moments, equilibrium, f_neq initialisation, the fixed-grid reductions,
+enstrophy, interior mass, the halo pack / unpack kernels -- at their edges: extents below the reach of the 6th-order
+differences, grids beyond one trip of the reduction's grid-stride loop, a maximum or a NaN in the first node, in the
+ragged tail and in the last node, slab plans with poisoned ghost planes and padding, every plane and direction of the
+halo messages.
+
+The reference of every test is the oracle (or plain numpy / torch indexing) evaluated in float64 on the CPU; for fp32
+on the same fp32-rounded inputs.  It is never another engine path.
+"""
+import functools
+import math
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import TORCH_DT
+from oracle import lettuce_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+ATOL = {"f64": 1e-12, "f32": 1e-5}
+# the reference builds the identity of Q in torch's default dtype: an fp32-rounded cs^2 (_flow.py passes the same)
+EYE_CS2 = float(torch.tensor(orc.CS ** 2, dtype=torch.float32))
+
+
+def dev(x, dtype=None):
+    t = torch.as_tensor(x)
+    return t.to(device="cuda", dtype=dtype or t.dtype).contiguous()
+
+
+def assert_close(got, want, dt):
+    tol = ATOL[dt] * max(1.0, float(np.abs(want).max()))
+    np.testing.assert_allclose(got, want, rtol=0, atol=tol)
+
+
+def _seed(*key):
+    return zlib.crc32(repr(key).encode())
+
+
+@functools.lru_cache(maxsize=None)
+def _field(lat, res, dt):
+    """(populations in the working dtype, the same values in float64), reference layout [q, *res]: an anisotropic,
+    non-symmetric state -- mean velocity (0.04, -0.03, 0.02), 2 % velocity and 5 % density noise, equilibrium times
+    5 % noise per population (as test_whole_field_operators_against_the_oracle).  Shared; never written to."""
+    L = orc.LATTICES[lat]
+    res = list(res)
+    g = torch.Generator().manual_seed(_seed(lat, res))
+    e, w = orc.lattice_tensors(L, torch.float64)
+    u0 = torch.tensor([0.04, -0.03, 0.02][:L.d], dtype=torch.float64).reshape([-1] + [1] * L.d)
+    u_in = u0 + 0.02 * torch.rand([L.d] + res, generator=g, dtype=torch.float64)
+    rho_in = 1 + 0.05 * torch.rand(res, generator=g, dtype=torch.float64)
+    f64 = orc.quadratic_equilibrium(rho_in, u_in, e, w) * (1 + 0.05 * torch.rand([L.q] + res, generator=g, dtype=torch.float64))
+    f_host = f64.to(TORCH_DT[dt])
+    return f_host, f_host.double()
+
+
+def _speed(ref, e):
+    u = orc.velocity(ref, e)
+    return torch.sqrt((u ** 2).sum(dim=0))
+
+
+def _plan(lat, dt, res, boundaries=(), **kw):
+    from lettuce_amd._native import Plan
+    return Plan(lat, TORCH_DT[dt], "bgk", list(res), list(boundaries), **kw)
+
+
+# --------------------------------------------------------------------------- a. f_neq initialisation
+FNEQ = [("D2Q9", (2, 9)), ("D2Q9", (9, 1)), ("D2Q9", (3, 4)), ("D2Q9", (6, 5)), ("D2Q9", (12, 9)),
+        ("D3Q19", (2, 7, 5)), ("D3Q19", (5, 1, 2)), ("D3Q19", (3, 4, 6)), ("D3Q19", (8, 7, 10)),
+        ("D3Q27", (6, 6, 6)), ("D3Q15", (1, 1, 7))]
+FNEQ_TAU = (0.51, 1.7)
+# Largest distance, over the cases and relaxation times above, between the oracle's expression evaluated in fp32 and in
+# float64 on the same fp32 inputs, as a fraction of max|f| (measured on the CPU: fneq_fp32_distance() below)
+FNEQ_F32_DISTANCE = 1.574e-7     # at D3Q27 6 x 6 x 6, tau = 0.51; the kernel's bound is 4 x this = 6.3e-7 max|f|
+
+
+def _fneq_inputs(lat, res):
+    """rho = 1 + 0.05 rand [*res], u = 0.05 rand [d, *res], float64"""
+    L = orc.LATTICES[lat]
+    g = torch.Generator().manual_seed(_seed("fneq", lat, list(res)))
+    rho = 1 + 0.05 * torch.rand(list(res), generator=g, dtype=torch.float64)
+    u = 0.05 * torch.rand([L.d] + list(res), generator=g, dtype=torch.float64)
+    return rho, u
+
+
+def fneq_fp32_distance():
+    """how FNEQ_F32_DISTANCE was measured (CPU only): max over FNEQ x FNEQ_TAU of max|f_fp32 - f_fp64| / max|f_fp64|"""
+    worst = 0.0
+    for lat, res in FNEQ:
+        L = orc.LATTICES[lat]
+        rho, u = _fneq_inputs(lat, res)
+        rho32, u32 = rho.float(), u.float()
+        for tau in FNEQ_TAU:
+            lo = orc.f_neq_initialisation(rho32[None], u32, tau, L, torch.float32).double()
+            hi = orc.f_neq_initialisation(rho32.double()[None], u32.double(), tau, L, torch.float64)
+            worst = max(worst, float((lo - hi).abs().max() / hi.abs().max()))
+    return worst
+
+
+@pytest.mark.parametrize("tau", FNEQ_TAU)
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat,res", FNEQ, ids=[f"{a}-{'x'.join(map(str, r))}" for a, r in FNEQ])
+def test_fneq_initialisation_at_small_and_aliasing_extents(lat, res, dt, tau):
+    """Plan.init_fneq against the oracle's initialize_f_neq expression (periodic_gradient6: torch.roll) in float64 on
+    the same rho, u -- extents 1 and 2 (every tap wraps, some twice), 3 to 6 (the six taps alias each other), ragged
+    larger ones; a density that varies by 5 %; both relaxation-time regimes; fp64 AND fp32.
+
+    fp64: 16 * 2^-53 * max|f|, the bound of the existing fp64 test.
+    fp32: the oracle's expression evaluated in fp32 differs from its float64 evaluation on the same fp32 inputs by at
+    most FNEQ_F32_DISTANCE = 1.574e-7 max|f| over exactly these cases (measured on the CPU, fneq_fp32_distance(): the
+    largest is D3Q27 6 x 6 x 6 at tau = 0.51; per case 5.6e-8 .. 1.6e-7); the kernel sums in another order and gets 4
+    times that, 6.3e-7 max|f| -- below the project's 1e-5 * max|f|, which caps it."""
+    L = orc.LATTICES[lat]
+    T = TORCH_DT[dt]
+    rho, u = _fneq_inputs(lat, res)
+    rho_t, u_t = rho.to(T), u.to(T)
+    want = orc.f_neq_initialisation(rho_t.double()[None], u_t.double(), tau, L, torch.float64)
+    plan = _plan(lat, dt, res)
+    got = plan.init_fneq(dev(rho_t), dev(u_t), tau, EYE_CS2).cpu().double()
+    scale = float(want.abs().max())
+    err = float((got - want).abs().max())
+    bound = (16 * 2.0 ** -53 if dt == "f64" else min(4 * FNEQ_F32_DISTANCE, ATOL["f32"])) * scale
+    print(f"init_fneq {lat} {list(res)} {dt} tau={tau}: max|df| = {err:.3e} = {err / scale:.3e} max|f|, bound {bound:.3e}")
+    assert list(got.shape) == [L.q] + list(res)
+    assert err <= bound
+
+
+# --------------------------------------------------------------------------- b. enstrophy
+ENS = [("D2Q9", (2, 9)), ("D2Q9", (9, 1)), ("D2Q9", (6, 5)), ("D2Q9", (515, 511)),
+       ("D3Q19", (2, 7, 5)), ("D3Q19", (3, 4, 6)), ("D3Q19", (67, 63, 65)), ("D3Q15", (5, 6, 7)), ("D3Q27", (6, 6, 6))]
+U_SCALE, DX = 7.3, 0.37
+# Units whose velocity scale (characteristic_velocity_pu / u_char_lu) is U_SCALE and whose dx is DX
+ENS_UNITS = orc.Units(1.0, 1.0, characteristic_length_lu=1, characteristic_length_pu=DX,
+                      characteristic_velocity_pu=U_SCALE * orc.CS)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat,res", ENS, ids=[f"{a}-{'x'.join(map(str, r))}" for a, r in ENS])
+def test_enstrophy_on_anisotropic_fields(lat, res, dt):
+    """Plan.enstrophy_sum against the oracle's Enstrophy expression in float64 on the same populations: an anisotropic
+    random field (no symmetry cancels a swapped component or axis), D3Q15 and D3Q27 as well, extents 1 and 2, and
+    grids of more than 1024 x 256 nodes, where the fixed grid of the reduction takes a second, ragged trip
+    (515 x 511 = 263 165 and 67 x 63 x 65 = 274 365 nodes)."""
+    L = orc.LATTICES[lat]
+    f_host, ref = _field(lat, res, dt)
+    assert ENS_UNITS.length_to_pu(1.0) == DX
+    want = float(orc.enstrophy_pu(ref, L, ENS_UNITS)) / DX ** L.d
+    assert want > 1e-6                                   # a resolved sum, not rounding noise
+    plan = _plan(lat, dt, res)
+    got = float(plan.enstrophy_sum(dev(f_host), U_SCALE, 1.0 / DX))
+    print(f"enstrophy {lat} {list(res)} {dt}: got {got!r}, want {want!r}, rel {abs(got - want) / want:.3e}")
+    assert got == pytest.approx(want, rel=1e-9 if dt == "f64" else 2e-5)
+
+
+@pytest.mark.parametrize("res", [(2, 5, 8), (7, 1, 6)], ids=["2x5x8", "7x1x6"])
+def test_slab_enstrophy_with_nx_or_ny_below_the_reach_of_the_differences(res):
+    """lt_slab_velocity + lt_slab_enstrophy through SlabSimulation on one rank (its own neighbour), fp64: x and y wrap
+    within the rank, with an extent of 2 and of 1; z comes from the neighbours' planes.  Against the oracle's
+    Enstrophy on the whole field."""
+    import lettuce_amd as lt
+    res = list(res)
+    L = orc.LATTICES["D3Q19"]
+    ctx = lt.Context("cuda:0", torch.float64, use_native=True)
+    slab = lt.ZSlab(res, 0, 1)
+    flow = lt.TaylorGreenVortex(ctx, slab.extended_resolution, 400, 0.1, lt.D3Q19(), slab=slab)
+    sim = lt.SlabSimulation(flow, lt.BGKCollision(flow.units.relaxation_parameter_lu), slab)
+    f_host, ref = _field("D3Q19", tuple(res), "f64")
+    sim.f[:, sim.lo:sim.hi] = dev(f_host).permute(0, 3, 2, 1)         # [q, nz, ny, nx]; the ghost planes are not read
+    want = float(orc.enstrophy_pu(ref, L, orc.tgv_units(res, 400, 0.1)))
+    assert want > 1e-6
+    got = sim.enstrophy_pu()
+    print(f"slab enstrophy {res}: got {got!r}, want {want!r}, rel {abs(got - want) / want:.3e}")
+    assert got == pytest.approx(want, rel=1e-9)
+
+
+# --------------------------------------------------------------------------- c. reductions
+RED = [("D2Q9", (515, 511)), ("D3Q19", (67, 63, 65)), ("D1Q3", (3,))]
+BIG = RED[:2]
+NODES = {"first": lambda n: 0, "second_trip": lambda n: 262144, "last": lambda n: n - 1}
+PLANT_U = {2: (0.18, -0.24), 3: (0.2, -0.2, 0.1)}                # |u| = 0.3
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat,res", RED, ids=[f"{a}-{'x'.join(map(str, r))}" for a, r in RED])
+def test_reductions_against_float64_sums(lat, res, dt):
+    """kinetic_energy_lu, mass and max_velocity_lu against float64 sums of the oracle's per-node values: beyond one
+    trip of the 1024 x 256 grid with a ragged tail, and on three nodes (1021 idle blocks)."""
+    L = orc.LATTICES[lat]
+    e, _ = orc.lattice_tensors(L, torch.float64)
+    f_host, ref = _field(lat, res, dt)
+    plan = _plan(lat, dt, res)
+    f = dev(f_host)
+    ke, want = float(plan.kinetic_energy_lu(f)), float(orc.incompressible_energy(ref, e).sum())
+    print(f"kinetic energy {lat} {dt}: rel {abs(ke - want) / want:.3e}")
+    assert ke == pytest.approx(want, rel=1e-12 if dt == "f64" else 2e-6)
+    mass, want = float(plan.mass(f)), float(ref.sum())
+    print(f"mass {lat} {dt}: rel {abs(mass - want) / want:.3e}")
+    assert mass == pytest.approx(want, rel=1e-12 if dt == "f64" else 1e-6)
+    umax, want = float(plan.max_velocity_lu(f)), float(_speed(ref, e).max())
+    print(f"max |u| {lat} {dt}: rel {abs(umax - want) / want:.3e}")
+    assert umax == pytest.approx(want, rel=1e-12 if dt == "f64" else 1e-6)
+
+
+@pytest.mark.parametrize("where", list(NODES))
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat,res", BIG, ids=[a for a, _ in BIG])
+def test_maximum_velocity_found_in_the_first_node_the_second_trip_and_the_last_node(lat, res, dt, where):
+    """One node carries the equilibrium of |u| = 0.3, the rest of the field stays far below: flat node 0, node 262 144
+    (the first of the second trip of the grid-stride loop) and the last node (the ragged tail).  The device maximum
+    is that node's |u|, computed in float64 from the stored populations."""
+    L = orc.LATTICES[lat]
+    e, w = orc.lattice_tensors(L, torch.float64)
+    f_host, _ = _field(lat, res, dt)
+    f = f_host.clone()
+    flat = f.reshape(L.q, -1)
+    node = NODES[where](flat.shape[1])
+    feq = orc.quadratic_equilibrium(torch.tensor(1.0, dtype=torch.float64),
+                                    torch.tensor(PLANT_U[L.d], dtype=torch.float64), e, w)
+    flat[:, node] = feq.to(f.dtype)
+    speed = _speed(f.double(), e).reshape(-1)
+    assert int(speed.argmax()) == node and float(speed[node]) == pytest.approx(0.3, rel=1e-5)
+    others = torch.cat([speed[:node], speed[node + 1:]])
+    assert float(others.max()) < 0.15
+    got = float(_plan(lat, dt, res).max_velocity_lu(dev(f)))
+    assert got == pytest.approx(float(speed[node]), rel=1e-12 if dt == "f64" else 1e-6)
+
+
+@pytest.mark.parametrize("where", list(NODES))
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat,res", BIG, ids=[a for a, _ in BIG])
+def test_a_nan_anywhere_makes_every_reduction_nan(lat, res, dt, where):
+    """One population of one node is NaN (a diverged run): the maximum |u| is NaN like the reference's
+    torch.norm(u, dim=0).max() -- `m > acc` alone would drop it and report a finite maximum -- and so are the sums."""
+    L = orc.LATTICES[lat]
+    e, _ = orc.lattice_tensors(L, torch.float64)
+    f_host, _ = _field(lat, res, dt)
+    f = f_host.clone()
+    flat = f.reshape(L.q, -1)
+    flat[3, NODES[where](flat.shape[1])] = float("nan")
+    assert math.isnan(float(_speed(f.double(), e).max()))             # what the reference reports
+    plan = _plan(lat, dt, res)
+    fd = dev(f)
+    assert math.isnan(float(plan.max_velocity_lu(fd)))
+    assert math.isnan(float(plan.kinetic_energy_lu(fd)))
+    assert math.isnan(float(plan.mass(fd)))
+
+
+def _stride_for(nodes, dtype):
+    """the next multiple of 256 bytes above `nodes` elements"""
+    unit = 256 // torch.empty((), dtype=dtype).element_size()
+    return (nodes // unit + 1) * unit
+
+
+def _slab_storage(plan, padded, fill):
+    """(flat buffer, [q, n2, n1, n0] view of it) filled with `fill`; with `padded` the plan gets a population stride of
+    the next multiple of 256 bytes and the view skips the padding, which stays reachable through the flat buffer"""
+    q, n2, n1, n0 = plan.f_shape
+    nodes = n2 * n1 * n0
+    stride = nodes
+    if padded:
+        stride = _stride_for(nodes, plan.dtype)
+        plan.set_population_stride(stride)
+    flat = torch.full([q * stride], fill, dtype=plan.dtype, device="cuda")
+    return flat, flat.as_strided([q, n2, n1, n0], (stride, n1 * n0, n0, 1))
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["dense", "padded"])
+@pytest.mark.parametrize("ghosts", [1, 2])
+def test_slab_reductions_exclude_poisoned_ghost_planes_and_padding(ghosts, padded):
+    """"Ghost planes are excluded" (lettuce_hip.h): a slab plan whose ghost planes and padding hold NaN gives the
+    float64 result over its interior planes, for the three reductions and for lt_slab_mass_interior."""
+    from lettuce_amd._native import LAYOUT_SLAB
+    res, dt = (10, 6, 4), "f32"
+    L = orc.LATTICES["D3Q19"]
+    e, _ = orc.lattice_tensors(L, torch.float64)
+    f_host, ref = _field("D3Q19", res, dt)
+    plan = _plan("D3Q19", dt, res, layout=LAYOUT_SLAB, ghost_planes=ghosts)
+    flat, f = _slab_storage(plan, padded, float("nan"))
+    f[:, ghosts:ghosts + res[2]] = dev(f_host).permute(0, 3, 2, 1)
+    assert int(torch.isnan(flat).sum()) == flat.numel() - ref.numel()
+    assert float(plan.kinetic_energy_lu(f)) == pytest.approx(float(orc.incompressible_energy(ref, e).sum()), rel=2e-6)
+    assert float(plan.mass(f)) == pytest.approx(float(ref.sum()), rel=1e-6)
+    assert float(plan.max_velocity_lu(f)) == pytest.approx(float(_speed(ref, e).max()), rel=1e-6)
+    # both sides sum the same fp32 values in float64
+    want = float(orc.mass_observable(ref))
+    assert want > 1.0
+    assert float(plan.slab_mass_interior(f, 0, res[2])) == pytest.approx(want, rel=1e-12)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat,res", [("D2Q9", (2, 9)), ("D3Q19", (5, 2, 6))], ids=["D2Q9-2x9", "D3Q19-5x2x6"])
+def test_interior_mass_of_a_grid_without_interior(lat, res, dt):
+    """An extent of 2 along one of the two fastest axes leaves no interior node (f[..., 1:-1, 1:-1] is empty): exactly
+    0 without a mask, minus the masked nodes' populations with one (both sides sum the same values in float64)."""
+    f_host, ref = _field(lat, res, dt)
+    plan = _plan(lat, dt, res)
+    f = dev(f_host)
+    assert float(plan.mass_interior(f)) == 0.0
+    mask = torch.rand(list(res), generator=torch.Generator().manual_seed(5)) < 0.3
+    assert 0 < int(mask.sum()) < mask.numel()
+    want = float(orc.mass_observable(ref, mask))
+    assert want < -0.5
+    assert float(plan.mass_interior(f, mask.cuda())) == pytest.approx(want, rel=1e-12)
+
+
+# --------------------------------------------------------------------------- d. moments and equilibrium on slab plans
+@pytest.mark.parametrize("res,ghosts", [((10, 6, 4), 1), ((9, 5, 3), 2)], ids=["10x6x4-g1", "9x5x3-g2"])
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("lat", ["D3Q19", "D3Q27"])
+def test_macroscopic_and_equilibrium_on_slab_layout_plans(lat, dt, res, ghosts):
+    """On a slab-layout plan the memory axes are (z, y, x), the kernels' component maps permute, and N covers the
+    ghost planes: rho and u (component a in LOGICAL order) and the equilibrium against the oracle on the permuted
+    field, all planes -- the anisotropic mean velocity makes a swapped component a 1e-2 error.  The moments also from
+    populations with a stride."""
+    from lettuce_amd._native import LAYOUT_SLAB
+    L = orc.LATTICES[lat]
+    T = TORCH_DT[dt]
+    e, w = orc.lattice_tensors(L, torch.float64)
+    nx, ny, nz = res
+    f_host, ref = _field(lat, (nx, ny, nz + 2 * ghosts), dt)         # reference layout, the ghost planes included
+    to_slab = lambda t: t.permute(0, 3, 2, 1).contiguous()           # noqa: E731  [c, x, y, z] -> [c, z, y, x]
+    rho_ref, u_ref = orc.density(ref), orc.velocity(ref, e)
+    plan = _plan(lat, dt, res, layout=LAYOUT_SLAB, ghost_planes=ghosts)
+    assert plan.f_shape == [L.q, nz + 2 * ghosts, ny, nx]
+    f = dev(to_slab(f_host))
+    rho, u = plan.macroscopic(f)
+    assert_close(rho.cpu().numpy()[None], to_slab(rho_ref).numpy(), dt)
+    assert_close(u.cpu().numpy(), to_slab(u_ref).numpy(), dt)
+    rho_t, u_t = rho_ref.to(T), u_ref.to(T)
+    feq = plan.equilibrium(dev(to_slab(rho_t))[0], dev(to_slab(u_t)))
+    assert_close(feq.cpu().numpy(), to_slab(orc.quadratic_equilibrium(rho_t.double(), u_t.double(), e, w)).numpy(), dt)
+    # a population stride: NaN padding between the populations
+    flat, fp = _slab_storage(plan, True, float("nan"))
+    fp.copy_(f)
+    rho, u = plan.macroscopic(fp)
+    assert_close(rho.cpu().numpy()[None], to_slab(rho_ref).numpy(), dt)
+    assert_close(u.cpu().numpy(), to_slab(u_ref).numpy(), dt)
+
+
+# --------------------------------------------------------------------------- e. halo pack / unpack
+SENTINEL = -7.0
+
+
+def _tags(plan):
+    """f[q, node] = q * N + node: exact in fp32 below 2^24"""
+    q, n2, n1, n0 = plan.f_shape
+    n = q * n2 * n1 * n0
+    assert n < 2 ** 24
+    return torch.arange(n, dtype=torch.float64).reshape(plan.f_shape).to(plan.dtype)
+
+
+def _crossings(plan, lat):
+    e = np.array(orc.LATTICES[lat].e)
+    sets = {d: [int(q) for q in np.nonzero(e[:, 2] == d)[0]] for d in (1, -1, 0)}
+    for d, want in sets.items():
+        assert plan.crossing(d) == want, d
+    return sets
+
+
+def _message(blocks, plan):
+    """`blocks` planes of distinct positive values, exact in fp32"""
+    _, _, n1, n0 = plan.f_shape
+    return (1 + torch.arange(blocks * n1 * n0, dtype=torch.float64)).reshape(blocks, n1, n0).to(plan.dtype)
+
+
+PACK = [(lat, res, dt, padded) for lat in ("D3Q15", "D3Q19", "D3Q27") for res in ((10, 6, 4), (40, 13, 3))
+        for dt in ("f32", "f64") for padded in (False, True)]
+PACK_IDS = [f"{lat}-{'x'.join(map(str, res))}-{dt}-{'padded' if p else 'dense'}" for lat, res, dt, p in PACK]
+
+
+@pytest.mark.parametrize("lat,res,dt,padded", PACK, ids=PACK_IDS)
+def test_plane_pack_and_unpack_against_plain_indexing(lat, res, dt, padded):
+    """lt_slab_crossing / lt_slab_pack / lt_slab_unpack, bit for bit: the crossing sets are those of the lattice
+    table; for every plane and both directions the message is f[crossing(dir), plane]; unpacking changes exactly
+    those entries of a sentinel-filled field -- ghost planes and padding included in the comparison.  60 nodes per
+    plane (less than a block) and 520 (three blocks, the last one ragged)."""
+    from lettuce_amd._native import LAYOUT_SLAB
+    plan = _plan(lat, dt, res, layout=LAYOUT_SLAB, ghost_planes=1)
+    sets = _crossings(plan, lat)
+    q, n2, n1, n0 = plan.f_shape
+    tags = _tags(plan)
+    flat, f = _slab_storage(plan, padded, SENTINEL)
+    f.copy_(tags)
+    before = flat.clone()
+    n = len(sets[1])
+    assert len(sets[-1]) == n
+    out = torch.full([n2, 2, n, n1, n0], SENTINEL, dtype=plan.dtype, device="cuda")
+    for plane in range(n2):
+        for k, direction in enumerate((1, -1)):
+            plan.pack(f, plane, direction, out[plane, k])
+    out = out.cpu()
+    assert torch.equal(flat, before)                                  # packing reads only
+    for plane in range(n2):
+        for k, direction in enumerate((1, -1)):
+            assert torch.equal(out[plane, k], tags[sets[direction], plane]), (plane, direction)
+    msg = _message(n, plan)
+    msg_dev = dev(msg)
+    for plane in range(n2):
+        for direction in (1, -1):
+            flat, f = _slab_storage(plan, padded, SENTINEL)
+            plan.unpack(f, plane, direction, msg_dev)
+            want_flat = torch.full_like(flat, SENTINEL, device="cpu")
+            want = want_flat.as_strided(f.shape, f.stride())
+            want[sets[direction], plane] = msg
+            assert torch.equal(flat.cpu(), want_flat), (plane, direction)
+
+
+def _two_step_layout(plan, sets, side, packing, masked=False):
+    """[(populations, plane)] per group of the two-step halo message, from the description in lettuce_hip.h: packing
+    for the neighbour beyond `side` reads this rank's two interior planes next to that cut -- in-plane populations of
+    the near plane, the populations that leave through the cut of the near plane and of the plane behind it;
+    unpacking fills the two ghost planes beyond `side` with the populations that enter.  Plans with masks: a fourth
+    group, the populations of the near plane that move away from the cut."""
+    n2, g = plan.f_shape[1], 2
+    if packing:
+        near, far = (g, g + 1) if side < 0 else (n2 - g - 1, n2 - g - 2)
+        direction = side
+    else:
+        near, far = (g - 1, g - 2) if side < 0 else (n2 - g, n2 - g + 1)
+        direction = -side
+    groups = [(sets[0], near), (sets[direction], near), (sets[direction], far)]
+    if masked:
+        groups.append((sets[-direction], near))
+    return groups
+
+
+def _check_two_step_messages(plan, lat, padded, masked):
+    sets = _crossings(plan, lat)
+    q, n2, n1, n0 = plan.f_shape
+    blocks = len(sets[0]) + (3 if masked else 2) * len(sets[1])
+    assert plan.two_step_message_blocks() == blocks
+    tags = _tags(plan)
+    flat, f = _slab_storage(plan, padded, SENTINEL)
+    f.copy_(tags)
+    before = flat.clone()
+    for side in (-1, 1):
+        buf = torch.full([blocks, n1, n0], SENTINEL, dtype=plan.dtype, device="cuda")
+        plan.pack_two_step(f, side, buf)
+        want = torch.cat([tags[qs, plane] for qs, plane in _two_step_layout(plan, sets, side, True, masked)])
+        assert torch.equal(buf.cpu(), want), side
+    assert torch.equal(flat, before)
+    msg = _message(blocks, plan)
+    msg_dev = dev(msg)
+    for side in (-1, 1):
+        flat, f = _slab_storage(plan, padded, SENTINEL)
+        plan.unpack_two_step(f, side, msg_dev)
+        want_flat = torch.full_like(flat, SENTINEL, device="cpu")
+        want = want_flat.as_strided(f.shape, f.stride())
+        at = 0
+        for qs, plane in _two_step_layout(plan, sets, side, False, masked):
+            want[qs, plane] = msg[at:at + len(qs)]
+            at += len(qs)
+        assert at == blocks
+        assert torch.equal(flat.cpu(), want_flat), side
+    return blocks
+
+
+@pytest.mark.parametrize("lat,res,dt,padded", PACK, ids=PACK_IDS)
+def test_two_step_pack_and_unpack_against_the_documented_message(lat, res, dt, padded):
+    """lt_slab_pack_two_step / lt_slab_unpack_two_step -- the reference the fused-packing launches are compared with
+    -- bit for bit against the message lettuce_hip.h documents, built by plain indexing; unpacking writes the
+    documented ghost entries and nothing else (interior planes, the other ghost planes and the padding compared)."""
+    from lettuce_amd._native import LAYOUT_SLAB
+    plan = _plan(lat, dt, res, layout=LAYOUT_SLAB, ghost_planes=2)
+    blocks = _check_two_step_messages(plan, lat, padded, masked=False)
+    assert blocks == orc.LATTICES[lat].q                              # 9 + 5 + 5, 9 + 9 + 9, 5 + 5 + 5
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["dense", "padded"])
+def test_two_step_messages_of_a_plan_with_masks_carry_the_away_populations(padded):
+    """A plan with masks (one bounce-back boundary, a few solid nodes; 64 x 8 x 6 so that the masked two-step kernel
+    admits it) sends 24 blocks for D3Q19: the fourth group is the near plane's populations that move away from the
+    cut."""
+    from lettuce_amd._native import LAYOUT_SLAB
+    plan = _plan("D3Q19", "f32", (64, 8, 6), [{"kind": "bounce_back"}], layout=LAYOUT_SLAB, ghost_planes=2)
+    ncm = torch.zeros(plan.f_shape[1:], dtype=torch.uint8)
+    for z, y, x in ((4, 3, 10), (5, 2, 33), (6, 5, 20), (6, 5, 21)):
+        ncm[z, y, x] = 1
+    plan.set_masks(ncm.cuda(), None)
+    assert plan.two_step_admitted() is None
+    assert _check_two_step_messages(plan, "D3Q19", padded, masked=True) == 24

@@ -510,3 +510,33 @@ def test_only_reporters_that_opt_in_are_batched():
     assert sim._steps_to_next_report(100) == 1
     EveryStep.batchable = True
     assert sim._steps_to_next_report(100) == 5
+
+
+@pytest.mark.parametrize("stencil,res", [(lt.D2Q9, [2, 9]), (lt.D2Q9, [1, 8]), (lt.D3Q27, [2, 1, 4])])
+def test_small_extent_fneq_and_enstrophy_of_the_mirror_agree_with_the_oracle(stencil, res):
+    """Extents 1 and 2 are smaller than the reach of the 6th-order differences (three nodes): every tap wraps, some
+    more than once.  The mirror's non-native initialize_f_neq and Enstrophy (torch_gradient) and the oracle's
+    restatement (periodic_gradient6) are two independent statements of what torch.roll gives there -- the HIP kernels
+    are held against the oracle, the oracle against the mirror here.  fp64, an anisotropic random state."""
+    from oracle import lettuce_oracle as orc
+    from lettuce_amd._flow import initialize_f_neq
+    L = orc.LATTICES[stencil.__name__]
+    g = torch.Generator().manual_seed(23)
+    e, w = orc.lattice_tensors(L, torch.float64)
+    u0 = torch.tensor([0.04, -0.03, 0.02][:L.d], dtype=torch.float64).reshape([-1] + [1] * L.d)
+    u_in = u0 + 0.02 * torch.rand([L.d] + res, generator=g, dtype=torch.float64)
+    rho_in = 1 + 0.05 * torch.rand([1] + res, generator=g, dtype=torch.float64)
+    f_eq = orc.quadratic_equilibrium(rho_in, u_in, e, w)
+    flow = lt.TaylorGreenVortex(ctx(), res, 100, 0.05, stencil(), initialize_fneq=False)
+    flow.f = f_eq.clone()
+    units = orc.tgv_units(res, 100, 0.05)
+    want = orc.f_neq_initialisation(orc.density(f_eq), orc.velocity(f_eq, e), units.tau, L, torch.float64)
+    got = initialize_f_neq(flow)
+    assert float((want - f_eq).abs().max()) > 1e-6            # the non-equilibrium part is not rounding noise
+    np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=0, atol=16 * 2.0 ** -53 * float(want.abs().max()))
+    # Enstrophy on a state with a resolved non-equilibrium part
+    f = f_eq * (1 + 0.05 * torch.rand([L.q] + res, generator=g, dtype=torch.float64))
+    flow.f = f.clone()
+    want_e = float(orc.enstrophy_pu(f, L, units))
+    assert want_e > 1e-6
+    assert float(lt.Enstrophy(flow)()) == pytest.approx(want_e, rel=1e-12)
