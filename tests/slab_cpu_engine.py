@@ -131,6 +131,55 @@ class OracleSlabEngine:
         self.pack_two_step(out, -1, pack_lower)
         self.pack_two_step(out, +1, pack_upper)
 
+    def stream_collide_twice_planes_packed(self, f, out, tau, b, e, pack_lower=None, pack_upper=None):
+        """lt_stream_collide_twice_planes_packed: the launch over [b, e) also writes the message(s) of its cut(s)"""
+        self.stream_collide_twice_planes(f, out, tau, b, e)
+        if pack_lower is not None:
+            assert b == 2
+            self.pack_two_step(out, -1, pack_lower)
+        if pack_upper is not None:
+            assert e == f.shape[1] - 2
+            self.pack_two_step(out, +1, pack_upper)
+
+    def stream_collide_twice_edges(self, f, out, tau, edge, pack_lower=None, pack_upper=None):
+        """lt_stream_collide_twice_edges: both edges in one launch, with both messages or with neither"""
+        assert (pack_lower is None) == (pack_upper is None)
+        lo, hi = 2, f.shape[1] - 2
+        self.stream_collide_twice_planes_packed(f, out, tau, lo, lo + edge, pack_lower=pack_lower)
+        self.stream_collide_twice_planes_packed(f, out, tau, hi - edge, hi, pack_upper=pack_upper)
+
+    def stream_collide_twice_slab(self, f, out, tau):
+        """lt_stream_collide_twice_slab: all interior planes; the edges are done when the call returns"""
+        self.stream_collide_twice_planes(f, out, tau, 2, f.shape[1] - 2)
+
+    def wait_edges(self):
+        pass
+
+    def wait_timed_out(self):
+        return False
+
+    # ---- one-step slabs: the pair launch and the crossing populations -----------------------------
+    def crossing(self, direction):
+        return self._sets(direction)[1] if direction else self._sets(0)[0]
+
+    def pack(self, f, plane, direction, buf):
+        buf.copy_(f[self.crossing(direction), plane])
+
+    def unpack(self, f, plane, direction, buf):
+        f[self.crossing(direction), plane] = buf
+
+    def stream_collide_plane_pair(self, f, out, tau, first, second):
+        self.stream_collide_planes(f, out, tau, first, first + 1)
+        if second != first:
+            self.stream_collide_planes(f, out, tau, second, second + 1)
+
+    def stream_collide_plane_pair_packed(self, f, out, tau, first, second, pack_first, pack_second):
+        """lt_stream_collide_plane_pair_packed: the downward populations of plane `first` and the upward ones of
+        plane `second` leave with the launch"""
+        self.stream_collide_plane_pair(f, out, tau, first, second)
+        self.pack(out, first, -1, pack_first)
+        self.pack(out, second, +1, pack_second)
+
     def _sets(self, direction):
         ez = [v[2] for v in self.lat.e]
         return ([q for q in range(self.lat.q) if ez[q] == 0],

@@ -407,3 +407,53 @@ def test_obstacle_on_slabs_with_two_updates_per_launch(tmp_path, world, name, la
         np.testing.assert_array_equal(got[f"TwoStepSlabSimulation_{n}"], got[f"SlabSimulation_{n}"])
         np.testing.assert_allclose(got[f"TwoStepSlabSimulation_{n}"], g[f"f{n}"], rtol=0,
                                    atol=1e-5 * float(np.abs(g[f"f{n}"]).max()))
+
+
+def _perturbed_worker(rank, world, port, lattice, dtype_name, res, steps, tau, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.cuda.set_device(0)
+    import lettuce_amd as lt
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_paths_vs_oracle import perturbed_state
+    dtype = getattr(torch, dtype_name)
+    ctx = lt.Context("cuda:0", dtype, use_native=True)
+    slab = lt.ZSlab(res)
+    flow = lt.TaylorGreenVortex(ctx, slab.extended_resolution, 400, 0.1, getattr(lt, lattice)(), slab=slab)
+    # this rank's planes of the global state, extended by the slab's halo planes (periodic)
+    f0 = perturbed_state(lattice, res, dtype, 21)
+    flow.f = f0[..., slab.z_indices()].cuda().contiguous()
+    sim = lt.TwoStepSlabSimulation(flow, lt.BGKCollision(tau), slab)
+    direct = sim._direct_ok()
+    sim(steps)
+    f1 = sim.gather_f()
+    if rank == 0:
+        np.savez(os.path.join(out_dir, "out.npz"), f1=f1.cpu().numpy(), direct=direct)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+PERTURBED = [(2, "D3Q27", "float32", [64, 8, 12], 7), (2, "D3Q15", "float64", [32, 16, 12], 7),
+             (3, "D3Q19", "float64", [32, 16, 15], 5)]
+
+
+@pytest.mark.parametrize("world,lattice,dtype_name,res,steps", PERTURBED,
+                         ids=[f"{c[0]}ranks-{c[1]}-{c[2]}" for c in PERTURBED])
+def test_two_step_slab_driver_on_every_lattice_from_a_state_without_symmetries(tmp_path, world, lattice, dtype_name,
+                                                                               res, steps):
+    """TwoStepSlabSimulation between different ranks on D3Q27 fp32, D3Q15 fp64 and D3Q19 fp64 (messages of 9 + 9 + 9,
+    5 + 5 + 5 and 9 + 5 + 5 blocks), in its default direct schedule, an odd number of steps from a perturbed state
+    (random density, mean flow, 5 % noise per population) against the oracle of the global domain in float64."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_paths_vs_oracle import TAU, assert_close, oracle, perturbed_state
+    port = 29200 + (os.getpid() % 500) + 10 * world + int(lattice[3:])
+    mp.spawn(_perturbed_worker, args=(world, port, lattice, dtype_name, res, steps, TAU, str(tmp_path)), nprocs=world,
+             join=True)
+    got = np.load(tmp_path / "out.npz")
+    assert bool(got["direct"])
+    sim = oracle(lattice, perturbed_state(lattice, res, getattr(torch, dtype_name), 21), "bgk")
+    want = sim.step(steps).numpy()
+    dt = "f32" if dtype_name == "float32" else "f64"
+    print(f"{lattice} {dtype_name} {world} ranks: max |driver - oracle| {float(np.abs(got['f1'] - want).max()):.3e}")
+    assert_close(got["f1"], want, dt, steps, False)
