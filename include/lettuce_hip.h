@@ -412,6 +412,25 @@ int lt_plan_set_two_step(lt_plan *plan, int32_t mode, int32_t planes_per_workgro
  * mode takes them in the streaming regime as it does for BGK, lt_plan_set_two_step(plan, 1, ...) wherever the grid
  * tiles; every other plan keeps the one-step kernel (lt_plan_two_step_admitted tells why). */
 int lt_plan_set_smagorinsky(lt_plan *plan, double constant);
+/* A uniform body force on a plan with LT_COLLISION_BGK or LT_COLLISION_SMAGORINSKY.  acceleration: `dims` values in
+ * lattice units, logical order x, y, z.  A colliding node (no_collision_mask == 0) then does
+ *   u*   = j / rho + (ueq_scale * a) / rho
+ *   f'_q = f_q - (1 / tau_eff) (f_q - feq_q(rho, u*))
+ *          + source_scale * w_q * sum_c [ (e_qc - u*_c) / cs^2 + (e_q . u*) e_qc / cs^4 ] a_c
+ * with tau_eff = tau for BGK (bgk_collision.py:17-22) and, for Smagorinsky, the relaxation time formed from
+ * f - feq(rho, u*) (smagorinsky_collision.py:19-36); boundary nodes are untouched.  Guo's scheme (lettuce/ext/_force/
+ * guo.py:14-31) is ueq_scale = 0.5, source_scale = 1 - 1 / (2 force.tau); Shan-Chen's (shan_chen.py:14-25) is
+ * ueq_scale = force.tau, source_scale = 0.  Read at every launch, so it may change between calls like tau.
+ * acceleration == NULL removes the force: the plan then launches exactly what a plan that never had one launches.  A
+ * zero vector is still a forced plan (its own kernels, same result up to rounding).  LT_ERR_INVALID for a non-finite
+ * value, LT_ERR_UNSUPPORTED on a plan whose collision is none or KBC; a refused call leaves the plan unchanged.
+ * Every one-step variant exists with the force (all lattices, dtypes, layouts, mask variants, the plane launches of a
+ * slab with one ghost plane); two steps per launch exist for BGK on D3Q19 fp32, periodic plans without masks, and are
+ * taken with lt_plan_set_two_step(plan, 1, ...) only -- never by the automatic mode.  On every other plan lt_run,
+ * lt_continue and lt_resident_advance keep the one-step kernel; the explicit multi-step entry points and
+ * lt_plan_two_step_admitted return LT_ERR_UNSUPPORTED with a reason that names the force. */
+int lt_plan_set_force(lt_plan *plan, const double *acceleration /* dims values, or NULL */, double ueq_scale,
+                      double source_scale);
 /* Population stride.  By default a population buffer is dense: population q starts q * nodes elements after
  * population 0 (the reference's [q, *res] tensor, lettuce/_flow.py:90).  With the q populations a power of two
  * apart (256^3 fp32: exactly 64 MiB) the q read and q write streams of a node meet in the same memory channels;

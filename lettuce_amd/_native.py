@@ -99,6 +99,7 @@ SYMBOLS = {
     "lt_stream_collide_twice": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "lt_plan_set_two_step": (ctypes.c_int, [_vp, _i32, _i32]),
     "lt_plan_set_smagorinsky": (ctypes.c_int, [_vp, _dbl]),
+    "lt_plan_set_force": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _dbl, _dbl]),
     "lt_stream_collide_twice_planes": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp]),
     "lt_stream_collide_twice_planes_packed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp, _vp, _vp]),
     "lt_stream_collide_twice_edges": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i32, _vp, _vp, _vp]),
@@ -721,6 +722,19 @@ class Plan:
     def set_smagorinsky(self, constant: float = 0.17):
         """the constant of a plan with the Smagorinsky collision; read at every launch, like tau"""
         self._check(self.lib.lt_plan_set_smagorinsky(self._handle, float(constant)))
+
+    def set_force(self, acceleration=None, ueq_scale: float = 0.5, source_scale: float = 0.0):
+        """A uniform body force on a BGK / Smagorinsky plan, read at every launch like tau: ``acceleration`` in lattice
+        units, one value per axis (x, y, z); None removes the force.  Guo: ``ueq_scale`` 0.5, ``source_scale``
+        1 - 1 / (2 tau); Shan-Chen: ``ueq_scale`` tau, ``source_scale`` 0 (include/lettuce_hip.h)."""
+        if acceleration is None:
+            self._check(self.lib.lt_plan_set_force(self._handle, None, float(ueq_scale), float(source_scale)))
+            return
+        values = [float(a) for a in acceleration]
+        if len(values) != len(self.resolution):
+            raise NativeEngineError(f"acceleration has {len(values)} components, the lattice {len(self.resolution)}")
+        array = (ctypes.c_double * len(values))(*values)
+        self._check(self.lib.lt_plan_set_force(self._handle, array, float(ueq_scale), float(source_scale)))
 
     def set_two_step(self, mode: int = -1, planes_per_workgroup: int = 0):
         """lt_run pairs fused steps into two-step launches: -1 automatic, 0 never, 1 when supported"""

@@ -198,6 +198,11 @@ class _NativeStepper:
             constant = float(self.collision.constant(flow))
             self.plan.set_smagorinsky(constant)
             key = (tau, constant)
+        if self.collision.force is not None:
+            # a body force: acceleration and scales are re-read per batch too; a changed force starts from flow.f
+            force = self.collision.force.plan_args()
+            self.plan.set_force(*force)
+            key = (key, force)
         if self.plan.resident_enabled()[0]:
             try:
                 return self._batch_resident(k, tau, key)

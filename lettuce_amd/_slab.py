@@ -433,9 +433,12 @@ class SlabSimulation:
         self.nzl = nzl
         self.lo, self.hi = g, g + nzl               # interior planes [lo, hi) of the slab tensor
         self.up, self.down = _crossing_sets(flow.stencil)
+        if not collision.native_available() and getattr(collision, "force", None) is not None:
+            raise LettuceException(f"collision '{type(collision).__name__}' with this force has no engine kernel")
         desc = collision.native_generator()
         self._tau = desc.tau
         self._constant = desc.constant      # Smagorinsky: re-read per batch like tau (else None)
+        self._force = desc.force            # body force: re-read per batch as well (else None)
         # boundaries: same ordering and masks as Simulation (built on the extended slab, then cut
         # to this rank's planes + one ghost plane per side and laid out z-slowest)
         from ._simulation import build_masks
@@ -470,6 +473,10 @@ class SlabSimulation:
         self.engine = engine
         if self._constant is not None and not hasattr(engine, "set_smagorinsky"):
             raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
+        if self._force is not None:
+            if not hasattr(engine, "set_force"):
+                raise LettuceException(f"engine {type(engine).__name__} has no body force")
+            engine.set_force(*self._force.plan_args())     # now: the two-step driver asks the engine below
         # [q, nx, ny, nzl + 2g] incl. the ghost planes -> [q, nzl + 2g, ny, nx]
         core = flow.f[..., h - g:h + nzl + g]
         # The slab tensors are this driver's own (the reference never sees them), so the populations need not be
@@ -718,6 +725,8 @@ class SlabSimulation:
         tau = float(self._tau(self.flow))
         if self._constant is not None:
             self.engine.set_smagorinsky(float(self._constant(self.flow)))
+        if self._force is not None:
+            self.engine.set_force(*self._force.plan_args())
         cur, nxt, carried = self._start_batch(tau)
         for _ in range(n if carried else n - 1):
             self._fused_step(cur, nxt, tau)

@@ -132,6 +132,15 @@ struct lt_plan {
   int residency = -1;        // workgroups per CU of the big launches: -1 = automatic, 0 = no cap
   int n_cu = 0;              // compute units of the plan's device
   double smagorinsky = 0.17; // Smagorinsky constant (lt_plan_set_smagorinsky); the reference's default
+  // uniform body force (lt_plan_set_force): read at every launch like tau.  forced: the kernels with COLL = 4 + collision
+  struct Force {
+    bool on = false;
+    double a[3] = {0.0, 0.0, 0.0}, ueq_scale = 0.0, source_scale = 0.0;
+    bool operator==(const Force &o) const {
+      return on == o.on && a[0] == o.a[0] && a[1] == o.a[1] && a[2] == o.a[2] && ueq_scale == o.ueq_scale &&
+             source_scale == o.source_scale;
+    }
+  } force;
   int two_step = -1;         // lt_run: pair the fused steps (lbm2_kernel): -1 = automatic, 0 / 1
   int seg_len = 0;           // planes per workgroup of the two-step kernel, 0 = automatic
   int many = -1;             // lt_run: several steps per launch on small 2-D grids: -1 = automatic, 0 / 1
@@ -184,7 +193,7 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau, smagorinsky; int masked, tune, shift, residency; } gkey = {};
+  struct { void *a, *b; double tau, smagorinsky; int masked, tune, shift, residency; Force force; } gkey = {};
 };
 
 namespace {
@@ -513,6 +522,27 @@ int masked_two_step_axis(const lt_plan *p) {
 }
 bool masked_two_step_ok(const lt_plan *p) { return masked_two_step_axis(p) >= 0; }
 bool canary_ok(lt_plan *p);
+// the kernels' COLL of the plan: its collision, + 4 with a body force
+int kernel_coll(const lt_plan *p) { return p->desc.collision | (p->force.on ? 4 : 0); }
+const char *const kForceMultiStep = "a body force (lt_plan_set_force) has the one-step kernels and the plain two-step sweep "
+                                    "of periodic D3Q19 fp32 plans without masks only: no many-step, 2-D, masked, role-wave "
+                                    "or slab two-step kernel takes it";
+const char *const kForceSmagorinskyTwice = "Smagorinsky with a body force (lt_plan_set_force) does not fit the two-step "
+                                           "sweep's occupancy step without scratch: it keeps the one-step kernel";
+// why a plan with a body force has no launch of several steps in `mode` (nullptr: it may have one)
+const char *force_refuses(const lt_plan *p, int mode) {
+  if (!p->force.on) return nullptr;
+  if (mode == lt::kFusedMany) return kForceMultiStep;
+  if (mode == lt::kFusedTwice) {
+    if (p->unit.d != 3 || p->masked || p->desc.ghost_planes || p->desc.stencil != LT_D3Q19 || p->desc.dtype != LT_F32)
+      return kForceMultiStep;
+    lt::StepArgs a;
+    memset(&a, 0, sizeof a);
+    a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = lt::kFusedTwice;
+    if (!p->unit.name(a)) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
+  }
+  return nullptr;
+}
 const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
                                       "edge, packed or signalling launches): slabs keep the one-step kernels";
 
@@ -526,6 +556,8 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   if (p->desc.ghost_planes && (pb < 1 || pe > p->n2 - 1) && mode != lt::kCollideOnly && pe > pb)
     return fail(LT_ERR_INVALID, "streaming from ghost planes: range [%lld, %lld) must stay in [1, %d)",
                 pb, pe, p->n2 - 1);
+  if (const char *why = force_refuses(p, mode))
+    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
   if (mode == lt::kFusedMany && (p->desc.ghost_planes || (p->masked && p->n_abb > 1)))
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: no slabs, at most one anti-bounce-back outlet");
   if (mode == lt::kFusedTwice) {
@@ -557,8 +589,10 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   a.wrap2 = p->desc.ghost_planes ? 0 : 1;
   a.tau = tau > 0.0 ? tau : 1.0;
   a.smagorinsky = p->smagorinsky;
+  a.accel[0] = p->force.a[0]; a.accel[1] = p->force.a[1]; a.accel[2] = p->force.a[2];
+  a.ueq_scale = p->force.ueq_scale; a.source_scale = p->force.source_scale;
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
-  a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = mode;
+  a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = mode;
   a.masked = p->masked;
   a.abb_depth = p->abb_depth;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
@@ -619,6 +653,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
       return -fail(LT_ERR_HIP, "cannot create the graph stream/events");
   }
   const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.smagorinsky == p->smagorinsky &&
+                    p->gkey.force == p->force &&
                     p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
                     p->gkey.shift == p->shift;
   if (!same) {
@@ -638,7 +673,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->smagorinsky, p->masked, p->tune, p->shift, p->residency};
+    p->gkey = {cur, other, tau, p->smagorinsky, p->masked, p->tune, p->shift, p->residency, p->force};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -659,6 +694,10 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
 bool two_step_possible(lt_plan *p, const char **why) {
   const char *dummy;
   if (!why) why = &dummy;
+  if (const char *refused = force_refuses(p, lt::kFusedTwice)) {
+    *why = refused;
+    return false;
+  }
   const TwoStepTile tile = two_step_tile(p);
   if (tile.rows == 0 || p->n0 % tile.width != 0 || p->n1 % tile.rows != 0) {
     *why = "the grid does not tile (contiguous extent % 64 (fp32) / 32 (fp64), middle extent % 8 or 4)";
@@ -686,7 +725,7 @@ bool two_step_possible(lt_plan *p, const char **why) {
   }
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = lt::kFusedTwice;
+  a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = lt::kFusedTwice;
   a.masked = p->masked;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? tile.width : 0;
@@ -712,6 +751,9 @@ bool two_step_wanted(lt_plan *p) {
   // its multiply-adds differently in the two inlining contexts): never automatic, so that the result of n steps
   // does not depend on how the caller splits them into batches
   if (p->desc.collision == LT_COLLISION_KBC) return false;
+  // a body force: never automatic (the forced two-step sweep has not been measured against two one-step launches,
+  // DESIGN.md section 7); lt_plan_set_two_step(plan, 1, ...) takes it
+  if (p->force.on) return false;
   // (Smagorinsky, D3Q19 fp32: bit-identical to two one-step launches and 0.279-0.309 against 0.409-0.475 ms per
   // update at 256^3, every sample below every sample of the one-step pair: automatic like BGK)
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
@@ -845,7 +887,7 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->mas
 // 2-D kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
 // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
-  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2) return false;
+  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on) return false;
   if (p->masked && p->n_abb > 1) return false;
   if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
   lt::StepArgs a;
@@ -1340,7 +1382,7 @@ const char *lt_plan_kernel_name(lt_plan *p) {
   if (!p) return "";
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = p->desc.collision;
+  a.layout = p->desc.layout; a.coll = kernel_coll(p);
   // what the fused section launches: lt_run's pairs, or a two-step slab driver on a plan with two
   // ghost planes
   a.mode = (two_step_wanted(p) || p->desc.ghost_planes == 2) ? lt::kFusedTwice : lt::kFused;
@@ -1696,6 +1738,25 @@ int lt_plan_set_smagorinsky(lt_plan *p, double constant) {
   if (!(constant >= 0.0) || !std::isfinite(constant))
     return fail(LT_ERR_INVALID, "Smagorinsky constant %g (finite and >= 0)", constant);
   p->smagorinsky = constant;
+  return LT_OK;
+}
+
+int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, double source_scale) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (p->desc.collision != LT_COLLISION_BGK && p->desc.collision != LT_COLLISION_SMAGORINSKY)
+    return fail(LT_ERR_UNSUPPORTED, "a body force exists for the BGK and Smagorinsky collisions; the plan's collision "
+                                    "is %d", p->desc.collision);
+  lt_plan::Force f;
+  if (acceleration) {
+    f.on = true;
+    for (int c = 0; c < p->unit.d; ++c) f.a[c] = acceleration[c];
+    f.ueq_scale = ueq_scale; f.source_scale = source_scale;
+    if (!std::isfinite(f.a[0]) || !std::isfinite(f.a[1]) || !std::isfinite(f.a[2]) || !std::isfinite(ueq_scale) ||
+        !std::isfinite(source_scale))
+      return fail(LT_ERR_INVALID, "body force: acceleration (%g, %g, %g), scales %g and %g must be finite", f.a[0],
+                  f.a[1], f.a[2], ueq_scale, source_scale);
+  }
+  p->force = f;
   return LT_OK;
 }
 

@@ -19,11 +19,14 @@ struct StepArgs {
   int wrap2;
   double tau;
   double smagorinsky;    // Smagorinsky constant (collision 3); the units square it
+  // body force (coll & 4, lt_plan_set_force): acceleration in the logical order x, y, z (the units permute it to the
+  // memory axes of the layout) and the two scales of the scheme
+  double accel[3], ueq_scale, source_scale;
   const unsigned char *node;
   const unsigned *nsm_bits;
   const void *bt;        // BoundaryTable<T>* (device)
   int nb;
-  int layout, coll, mode, masked, shift, tune;
+  int layout, coll, mode, masked, shift, tune;   // coll: lt_collision, + 4 with a body force (the kernels' COLL)
   int strip;             // kFusedTwice on 2-D lattices: columns per workgroup (512 / 256 / 128 / 64)
   int abb_axis;          // kFusedTwice with masks: memory axis of the plan's outlet (2 without one)
   int n_abb;             // anti-bounce-back outlets of the plan
@@ -90,6 +93,19 @@ LT_DECLARE_SMAG(d3q19_f32)
 LT_DECLARE_SMAG(d3q19_f64)
 LT_DECLARE_SMAG(d3q27_f32)
 LT_DECLARE_SMAG(d3q27_f64)
+
+// ... and the kernels with a body force of every unit, instantiated by inst5_<tag>.hip
+#define LT_DECLARE_FORCED(tag) int forced_##tag(const StepArgs &, bool name_only, const char **name);
+LT_DECLARE_FORCED(d1q3_f32)
+LT_DECLARE_FORCED(d1q3_f64)
+LT_DECLARE_FORCED(d2q9_f32)
+LT_DECLARE_FORCED(d2q9_f64)
+LT_DECLARE_FORCED(d3q15_f32)
+LT_DECLARE_FORCED(d3q15_f64)
+LT_DECLARE_FORCED(d3q19_f32)
+LT_DECLARE_FORCED(d3q19_f64)
+LT_DECLARE_FORCED(d3q27_f32)
+LT_DECLARE_FORCED(d3q27_f64)
 
 LT_DECLARE_UNIT(d1q3_f32)
 LT_DECLARE_UNIT(d1q3_f64)

@@ -91,6 +91,16 @@ struct KParams {
   int lo, hi;                // first interior plane, one past the last interior plane
 };
 
+// The parameters of a kernel with a body force (COLL & 4): KParams and, behind it, the uniform acceleration.  A type of
+// its own, taken by overloads of the kernels, so that the argument block of every unforced kernel -- and with it that
+// kernel's code -- stays what it was.
+template <typename T>
+struct KParamsF : KParams<T> {
+  T accel[3];                // acceleration along the MEMORY axes a0, a1, a2 (the units permute it; 0 beyond the lattice's d)
+  T shift[3];                // ueq_scale * accel (Guo 1/2, Shan-Chen force.tau): u* = j / rho + shift / rho
+  T source_scale;            // Guo: 1 - 1 / (2 force.tau), Shan-Chen: 0
+};
+
 // ---- constants the reference builds from cs = 1/np.sqrt(3.0) (lettuce/_stencil.py:17) ----
 // cs**2 evaluates to 0.33333333333333337 in double; keep that value, not 1/3.
 constexpr double kCs = 0.57735026918962584;   // 1/sqrt(3) rounded to double
@@ -543,6 +553,105 @@ __device__ __forceinline__ void collide_smagorinsky(T (&f)[S::Q][VEC], T tau, T 
   });
 }
 
+// BGK (BASE 1) or Smagorinsky (BASE 3) with a uniform body force (lettuce/ext/_collision/bgk_collision.py:17-22,
+// smagorinsky_collision.py:19-36, lettuce/ext/_force/guo.py:14-31, shan_chen.py:14-25):
+//   u*   = j / rho + (ueq_scale a) / rho
+//   f'_q = f_q - (1 / tau_eff) (f_q - feq_q(rho, u*))
+//          + source_scale w_q sum_c [ (e_qc - u*_c) / cs^2 + (e_q . u*) e_qc / cs^4 ] a_c
+// with tau_eff = tau (BGK) or the Smagorinsky relaxation time formed from f - feq(rho, u*) exactly as
+// collide_smagorinsky forms it from f - feq(rho, u).  The sum over c is evaluated as
+//   sum_c e_qc (a_c h_q) - (u* . a) / cs^2,   h_q = 1 / cs^2 + (e_q . u*) / cs^4,
+// with u* . a formed once per node.  Every product has a per-node factor: a product of two launch constants (e_q . a,
+// ueq_scale a -- the units form the latter) would be hoisted out of the two-step kernel's sweep into vector registers,
+// one per population, and the sweep has none to spare.  Compared with the reference at rounding level.  No
+// contraction by the compiler (every kernel this is inlined into returns the same bits); the multiply-adds of the
+// source term are written as fma_t.
+template <typename T, class S, int LAYOUT, int VEC, int k, int BASE>
+__device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF<T> &p) {
+#pragma clang fp contract(off)
+  static_assert(BASE == 1 || BASE == 3, "a body force exists for BGK and Smagorinsky");
+  using M = MemMap<S, LAYOUT>;
+  T rho, j[3], u[3];
+  moments<T, S, LAYOUT, VEC, k>(f, rho, j);
+  static_for<3>([&](auto mc) {
+    constexpr int m = decltype(mc)::value;
+    u[m] = j[m] / rho + p.shift[m] / rho;
+  });
+  const T uxu = square_norm<S, LAYOUT>(u);
+  // u* . a over the logical axes
+  T ua = u[M::memory(0)] * p.accel[M::memory(0)];
+  if constexpr (S::D > 1) ua = ua + u[M::memory(1)] * p.accel[M::memory(1)];
+  if constexpr (S::D > 2) ua = ua + u[M::memory(2)] * p.accel[M::memory(2)];
+  constexpr T inv_cs2 = (T)(1.0 / kCs2), inv_cs4 = (T)(1.0 / kCs4);
+  const T ua_cs2 = ua * inv_cs2;
+  // relaxed = f_q - (1 / tau_eff) (f_q - feq_q)  ->  relaxed + source_q
+  auto with_source = [&](auto qc, T relaxed) {
+    constexpr int q = decltype(qc)::value;
+    const T h = fma_t(dot_e<S, LAYOUT, q>(u), inv_cs4, inv_cs2);
+    T t = -ua_cs2;
+    static_for<S::D>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      constexpr int e = S::E[q][c];
+      if constexpr (e > 0) t = fma_t(p.accel[M::memory(c)], h, t);
+      else if constexpr (e < 0) t = fma_t(-p.accel[M::memory(c)], h, t);
+    });
+    return fma_t(p.source_scale, T(S::W[q]) * t, relaxed);
+  };
+  if constexpr (BASE == 1) {
+    for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+      constexpr int q = decltype(qc)::value;
+      f[q][k] = with_source(qc, f[q][k] - p.tau_inv * (f[q][k] - feq));
+    });
+  } else {
+    T x[S::Q];
+    T pair[S::Q];                                 // [q], q < opposite(q): x_q + x_opposite
+    for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+      constexpr int q = decltype(qc)::value;
+      constexpr int o = S::OPP[q];
+      const T d = f[q][k] - feq;
+      x[q] = d;
+      if constexpr (q < o) pair[q] = d;
+      else if constexpr (q > o) pair[o] = pair[o] + d;
+    });
+    T xx = T(0), yy = T(0), zz = T(0), xy = T(0), xz = T(0), yz = T(0);
+    static_for<S::Q>([&](auto qc) {
+      constexpr int q = decltype(qc)::value;
+      if constexpr (q < S::OPP[q]) {
+        constexpr int ex = S::E[q][0], ey = S::E[q][1], ez = S::E[q][2];
+        const T v = pair[q];
+        if constexpr (ex != 0) xx += v;
+        if constexpr (ey != 0) yy += v;
+        if constexpr (ez != 0) zz += v;
+        if constexpr (ex * ey > 0) xy += v; else if constexpr (ex * ey < 0) xy -= v;
+        if constexpr (ex * ez > 0) xz += v; else if constexpr (ex * ez < 0) xz -= v;
+        if constexpr (ey * ez > 0) yz += v; else if constexpr (ey * ez < 0) yz -= v;
+      }
+    });
+    const T inv_d = T(1) / (T(2) * rho * T(kCs2));
+    xx = xx * inv_d;
+    T ss = xx * xx;                               // S_shear : S_shear
+    if constexpr (S::D > 1) {
+      yy = yy * inv_d; xy = xy * inv_d;
+      ss = ss + yy * yy + T(2) * (xy * xy);
+    }
+    if constexpr (S::D > 2) {
+      zz = zz * inv_d; xz = xz * inv_d; yz = yz * inv_d;
+      ss = ss + zz * zz + T(2) * (xz * xz) + T(2) * (yz * yz);
+    }
+    const T nu = (p.tau - T(0.5)) / T(3);
+    T r = T(1) / p.tau;                           // 1 / tau_eff
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const T nu_eff = fma_t(p.smag_c2, ss * (r * r), nu);
+      r = T(1) / fma_t(nu_eff, T(3), T(0.5));
+    }
+    static_for<S::Q>([&](auto qc) {
+      constexpr int q = decltype(qc)::value;
+      f[q][k] = with_source(qc, f[q][k] - r * x[q]);
+    });
+  }
+}
+
 // ---- boundaries -------------------------------------------------------------------------
 // BounceBackBoundary: f <- f[opposite] (lettuce/ext/_boundary/bounce_back_boundary.py:17-18)
 template <typename T, class S, int VEC, int k>
@@ -629,8 +738,8 @@ __device__ __forceinline__ void abb_apply(const KParams<T> &p, int slot, T rn, c
 // rewritten some of this node's populations, so the node's state is rebuilt in full -- pull, collision,
 // boundaries below `slot` in order, the lower outlet with ITS neighbour's moments at DEPTH - 1 -- instead
 // of being read off the conserved moments.  DEPTH = 0 is the kernel of plans with one outlet.
-template <typename T, class S, int LAYOUT, bool STREAM, bool MASKED, int COLL = 0, int DEPTH = 0>
-__device__ __forceinline__ void neighbour_moments(const KParams<T> &p, int c0, int c1, int c2, int slot,
+template <typename T, class S, int LAYOUT, bool STREAM, bool MASKED, int COLL = 0, int DEPTH = 0, class P = KParams<T>>
+__device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, int c2, int slot,
                                                   T &rho, T (&j)[3]) {
   const Coord c = make_coord(p, c0, c1, c2);
   T g[S::Q][1];
@@ -656,6 +765,7 @@ __device__ __forceinline__ void neighbour_moments(const KParams<T> &p, int c0, i
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(g, p.tau_inv);
         if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(g, p.beta, p.inv_beta);
         if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(g, p.tau, p.smag_c2);
+        if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(g, p);
       }
       for (int t = 1; t < slot; ++t) {
         const int kind = p.bt->kind[t];
@@ -683,12 +793,18 @@ __device__ __forceinline__ void neighbour_moments(const KParams<T> &p, int c0, i
       return;
     }
   }
+  // a body force adds momentum in the collision (a per step with BGK; with Smagorinsky an amount that depends on the
+  // node's tau_eff): the moments are those of the collided populations
+  if constexpr ((COLL & 4) != 0) {
+    if (b == 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(g, p);
+  }
   moments<T, S, LAYOUT, 1, 0>(g, rho, j);
   lower_boundaries_on_moments<T, S, LAYOUT>(p, b, slot, own, rho, j);
 }
 
-template <typename T, class S, int LAYOUT, bool STREAM, bool MASKED, int VEC, int k, int COLL = 0, int ABBD = 0>
-__device__ __forceinline__ void abb_outlet(const KParams<T> &p, int slot, int c0k, int c1,
+template <typename T, class S, int LAYOUT, bool STREAM, bool MASKED, int VEC, int k, int COLL = 0, int ABBD = 0,
+          class P = KParams<T>>
+__device__ __forceinline__ void abb_outlet(const P &p, int slot, int c0k, int c1,
                                            int c2, T (&f)[S::Q][VEC]) {
   const int ax = p.bt->mem_axis[slot], nbr = p.bt->nbr[slot];
   T rn, jn[3];
@@ -701,8 +817,8 @@ __device__ __forceinline__ void abb_outlet(const KParams<T> &p, int slot, int c0
 // no_collision_mask, (c0k, c1, c2) its memory coordinates, ownk its index within a population.
 // lane_slot != 0: (lane_rho, lane_j) are the moments of the node next to this one along a0 as outlet `lane_slot`
 // sees them, handed over by the neighbouring lane (lbm_body) instead of being gathered again.
-template <typename T, class S, int LAYOUT, bool STREAM, int VEC, int k, int COLL = 0, int ABBD = 0>
-__device__ __forceinline__ void apply_boundaries(const KParams<T> &p, int b, int c0k, int c1, int c2,
+template <typename T, class S, int LAYOUT, bool STREAM, int VEC, int k, int COLL = 0, int ABBD = 0, class P = KParams<T>>
+__device__ __forceinline__ void apply_boundaries(const P &p, int b, int c0k, int c1, int c2,
                                                  unsigned ownk, T (&f)[S::Q][VEC], int lane_slot = 0,
                                                  T lane_rho = T(1), const T *lane_j = nullptr) {
   for (int slot = 1; slot <= p.nb; ++slot) {
@@ -750,8 +866,8 @@ constexpr int crossing_rank() {
 
 // ABBD: plans with ABBD + 1 anti-bounce-back outlets (neighbour_moments, DEPTH)
 template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
-          int TUNE = 0, bool PACK = false, int ABBD = 0>
-__device__ __forceinline__ void lbm_body(const KParams<T> &p) {
+          int TUNE = 0, bool PACK = false, int ABBD = 0, class P = KParams<T>>
+__device__ __forceinline__ void lbm_body(const P &p) {
   const unsigned v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= p.nvec_total) return;
   {
@@ -780,7 +896,8 @@ __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
   // their latency in every wave that ends a row: 0.48 -> 0.60 ms at 512 x 512 x 64 with the Obstacle's outlet)
   int lane_slot = 0;
   T lane_rho = T(1), lane_j[3] = {T(0), T(0), T(0)};
-  if constexpr (COLLIDE && MASKED && ABBD == 0) {
+  // (not with a body force: the neighbour's collision changes its momentum -- neighbour_moments collides it)
+  if constexpr (COLLIDE && MASKED && ABBD == 0 && (COLL & 4) == 0) {
     if (p.abb0_slot != 0) {
       const int slot = p.abb0_slot, plane = p.bt->plane[slot];
       const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -806,6 +923,7 @@ __device__ __forceinline__ void lbm_body(const KParams<T> &p) {
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(f, p.tau_inv);
         if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(f, p.beta, p.inv_beta);
         if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(f, p.tau, p.smag_c2);
+        if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(f, p);
       }
       if constexpr (MASKED)
         apply_boundaries<T, S, LAYOUT, STREAM, 1, 0, COLL, ABBD>(p, b, c0, c1, c2, own, f, lane_slot, lane_rho, lane_j);
@@ -842,6 +960,15 @@ template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, 
           int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParams<T> p) {
   static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
+}
+
+// ... with a body force (COLL = 4 + the collision): the same body on KParamsF
+template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
+          int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+__global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsF<T> p) {
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  static_assert(COLL == 5 || COLL == 7, "a body force exists for BGK (5) and Smagorinsky (7)");
   lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 
@@ -906,445 +1033,20 @@ template <typename T, class S, int LAYOUT, int COLL, int T0_, int T1, int NPT = 
 __global__ void __launch_bounds__((SCHED == 0 ? (TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64
                                               : RoleWaves<TwoStep<T, S, T0_, T1>::NI, TwoStep<T, S, T0_, T1>::NO>::THREADS))
 lbm2_kernel(const KParams<T> p, const int seg_len) {
-  constexpr bool PACK = MODE == 1;
-  static_assert(MODE == 0 || LAYOUT == 1, "edge / signalling launches exist in the slab layout");
-  static_assert(NPT == 1 && NPB == 1, "one intermediate and one output node per thread");
-  static_assert(SCHED == 0 || (SCHED == 1 && MODE == 0), "separate producer and consumer waves: the plain sweep");
-  using B = TwoStep<T, S, T0_, T1>;
-  using M = MemMap<S, LAYOUT>;
-  constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
-  constexpr int NU = B::template count<LAYOUT, 1>(), NC = B::template count<LAYOUT, 0>(),
-                ND = B::template count<LAYOUT, -1>();
-  static_assert(COLL == 0 || COLL == 1 || COLL == 3, "two-step kernel: streaming only, BGK or Smagorinsky");
-  static_assert(COLL != 3 || (SCHED == 0 && MODE == 0), "Smagorinsky: the plain one-role sweep only");
-  __shared__ T lds_u[4][NU][NI];
-  __shared__ T lds_c[3][NC][NI];
-  __shared__ T lds_d[2][ND][NI];
+  static_assert((COLL & 4) == 0, "kernels with a body force take KParamsF");
+#include "twostep_sweep.inc"
+}
 
-  const int tid = threadIdx.x;
-  const int tiles0 = p.n0 / T0, tiles1 = p.n1 / T1;
-  // Workgroups go to the 8 XCDs round-robin (block b -> XCD b % 8) and every XCD has its own L2.
-  // Renumber so that an XCD owns a compact patch of neighbouring tiles: the halo rows two tiles
-  // share are then fetched into one L2 once instead of into two L2s.
-  int b = blockIdx.x;
-  const int segs_a = (p.p_end - p.p_begin + seg_len - 1) / seg_len;
-  if (MODE == 2) {
-    // edges first (the hardware starts workgroups in index order): upper edge = the one segment of the second
-    // range, then the first segment of the first range, then the rest with the XCD-aware numbering
-    // (XCD-aware within each layer of tiles)
-    const int tiles = tiles0 * tiles1;
-    const int layer = b / tiles, t = b - layer * tiles;
-    const int tile = tiles % 8 == 0 ? (t % 8) * (tiles / 8) + t / 8 : t;
-    b = (layer == 0 ? segs_a : layer - 1) * tiles + tile;
-  } else if (p.nb == 0 && (tiles0 * tiles1) % 8 == 0) {
-    // every XCD gets an eighth of EVERY segment layer -- a compact patch of tiles -- rather than an eighth of
-    // the grid: slab launches cut their plane range into segments of unequal length (64 planes as 62 + 2: four
-    // XCDs had all the long workgroups, 1.00 instead of 0.55 ms), and with equal segments it is as good or
-    // better (256^3: 0.511 / 0.537 / 0.532 against 0.512 / 0.572 / 0.579 ms with 128 / 64 / 32 planes)
-    const int tiles = tiles0 * tiles1;
-    const int layer = b / tiles, t = b - layer * tiles;
-    b = layer * tiles + (t % 8) * (tiles / 8) + t / 8;
-  } else if (p.nb != 1 && gridDim.x % 8 == 0) {
-    b = (b % 8) * (gridDim.x / 8) + b / 8;           // A/B (nb = 2), or tiles that do not divide by 8
-  }
-  const int t0 = (b % tiles0) * T0; b /= tiles0;
-  const int t1 = (b % tiles1) * T1; b /= tiles1;
-  // first output plane of this workgroup: segments of the first range, then of the second one
-  const bool second = b >= segs_a;
-  const int range_end = second ? p.p_end2 : p.p_end;
-  const int s = second ? p.p_begin2 + (b - segs_a) * seg_len : p.p_begin + b * seg_len;
-
-  const bool in_a = tid < NI, in_b = tid < NO;
-  // Addresses: the plane part is uniform (scalar registers, recomputed per plane), the in-plane
-  // part is a per-thread constant -- nine byte offsets for the nine (e0, e1) pairs of the lattice.
-  unsigned voff[NPT][3][3];                          // [k][e1 + 1][e0 + 1], bytes within a plane
-  unsigned out_off[NPB];
-  int a_at[NPT];                                     // LDS index of the intermediate node
-  int b_at[NPB];                                     // LDS index of the output node incl. halo offset
-  static_for<NPT>([&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    // phase A: node (i0, i1) of the halo'd tile, global coordinates (g0, g1).  The T0 inner columns
-    // of a row go to T0 consecutive threads (a wave reads one aligned 256-byte row segment per
-    // population), the two halo columns of all rows to the last threads.
-    const int ia = tid + k * NI;
-    constexpr int inner = T0 * B::H1;
-    const int i1 = ia < inner ? ia / T0 : (ia - inner) >> 1;
-    const int i0 = ia < inner ? 1 + (ia - i1 * T0) : (((ia - inner) & 1) ? H0 - 1 : 0);
-    a_at[k] = i1 * H0 + i0;
-    int g0 = t0 + i0 - 1; g0 = g0 < 0 ? g0 + p.n0 : (g0 >= p.n0 ? g0 - p.n0 : g0);
-    int g1 = t1 + i1 - 1; g1 = g1 < 0 ? g1 + p.n1 : (g1 >= p.n1 ? g1 - p.n1 : g1);
-    const int g0m = g0 == 0 ? p.n0 - 1 : g0 - 1, g0p = g0 == p.n0 - 1 ? 0 : g0 + 1;
-    const int g1m = g1 == 0 ? p.n1 - 1 : g1 - 1, g1p = g1 == p.n1 - 1 ? 0 : g1 + 1;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int y = a == 0 ? g1p : (a == 1 ? g1 : g1m);     // source = node - e
-        const int x = c == 0 ? g0p : (c == 1 ? g0 : g0m);
-        voff[k][a][c] = ((unsigned)y * (unsigned)p.n0 + (unsigned)x) * (unsigned)sizeof(T);
-      }
-  });
-  static_for<NPB>([&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    // phase B: output node (j0, j1) of the tile
-    const int ib = tid + k * NO;
-    const int j1 = ib / T0, j0 = ib - j1 * T0;
-    out_off[k] = ((unsigned)(t1 + j1) * (unsigned)p.n0 + (unsigned)(t0 + j0)) * (unsigned)sizeof(T);
-    b_at[k] = (j1 + 1) * H0 + (j0 + 1);
-  });
-  const unsigned plane_nodes = (unsigned)p.n1 * (unsigned)p.n0;
-
-  if constexpr (SCHED == 1) {
-    // Producer waves run phase A only, consumer waves phase B only (twostep_roles.hpp: the skeleton both run, the
-    // wave layout).  A SIMD then holds waves in different phases -- a consumer colliding while the producers wait
-    // for their loads, producers colliding while the consumer waits for LDS -- instead of three waves that wait at
-    // the same moments.  Per node the arithmetic and its order are those of SCHED 0.
-    using R = RoleWaves<NI, NO>;
-    constexpr int CPB = R::CPB, CT = NO / CPB;
-    const int last = s + seg_len < range_end ? s + seg_len : range_end;
-    auto sync = [&]() { lds_barrier(); };
-    if (__builtin_amdgcn_readfirstlane(tid >> 6) < R::PW) {
-      // Every lane loads (those without an intermediate node read the plane's first node): under `if (in_a)` the
-      // other lanes' registers are undefined, the compiler zeroes them AFTER the loads and that write waits for them.
-      if (!in_a) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) voff[0][a][c] = 0u;
-      }
-      T set0[S::Q][1], set1[S::Q][1];
-      auto load = [&](int plane, auto set) {
-        T (&dst)[S::Q][1] = decltype(set)::value == 0 ? set0 : set1;
-        int g2 = plane, g2m = plane - 1, g2p = plane + 1;
-        if (p.wrap2) {
-          g2 = plane < 0 ? plane + p.n2 : (plane >= p.n2 ? plane - p.n2 : plane);
-          g2m = g2 == 0 ? p.n2 - 1 : g2 - 1;
-          g2p = g2 == p.n2 - 1 ? 0 : g2 + 1;
-        }
-        static_for<S::Q>([&](auto qc) {
-          constexpr int q = decltype(qc)::value;
-          constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2);
-          const int z = e2 == 0 ? g2 : (e2 > 0 ? g2m : g2p);
-          const T *base = p.in + ((long long)q * p.Ni + (long long)((unsigned)z * plane_nodes));
-          dst[q][0] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + voff[0][e1 + 1][e0 + 1]);
-        });
-        // (the register-minimising scheduler sinks the loads behind the collide of the other set otherwise)
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      auto fill = [&](int r, int r3, auto set) {
-        T (&src)[S::Q][1] = decltype(set)::value == 0 ? set0 : set1;
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
-        if (in_a) {
-          static_for<S::Q>([&](auto qc) {
-            constexpr int q = decltype(qc)::value;
-            constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-            if constexpr (e2 > 0) lds_u[r & 3][rank][a_at[0]] = src[q][0];
-            else if constexpr (e2 == 0) lds_c[r3][rank][a_at[0]] = src[q][0];
-            else lds_d[r & 1][rank][a_at[0]] = src[q][0];
-          });
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      role_sweep(s, last, load, fill, sync, [](int, int) {}, [](int) {});
-    } else {
-      // consumer thread c of CT owns the output nodes c, c + CT, ... of the tile: a wave reads whole rows
-      const int c = tid - R::PW * 64;
-      unsigned c_off[CPB];
-      int c_at[CPB];
-      static_for<CPB>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const int ib = c + k * CT;
-        const int j1 = ib / T0, j0 = ib - j1 * T0;
-        c_off[k] = ((unsigned)(t1 + j1) * (unsigned)p.n0 + (unsigned)(t0 + j0)) * (unsigned)sizeof(T);
-        c_at[k] = (j1 + 1) * H0 + (j0 + 1);
-      });
-      T f[S::Q][CPB];
-      auto drain = [&](int r, int r3) {
-        static_for<S::Q>([&](auto qc) {
-          constexpr int q = decltype(qc)::value;
-          constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-          static_for<CPB>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            const int at = c_at[k] - e1 * H0 - e0;
-            if constexpr (e2 > 0) f[q][k] = lds_u[(r - 1) & 3][rank][at];
-            else if constexpr (e2 == 0) f[q][k] = lds_c[r3][rank][at];
-            else f[q][k] = lds_d[(r + 1) & 1][rank][at];
-          });
-        });
-      };
-      auto emit = [&](int k2) {
-        if constexpr (COLL == 1)
-          static_for<CPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, CPB, decltype(kc)::value>(f, p.tau_inv); });
-        static_for<S::Q>([&](auto qc) {
-          constexpr int q = decltype(qc)::value;
-          T *base = p.out + ((long long)q * p.No + (long long)((unsigned)k2 * plane_nodes));
-          static_for<CPB>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            __builtin_nontemporal_store(f[q][k], reinterpret_cast<T *>(reinterpret_cast<char *>(base) + c_off[k]));
-          });
-        });
-      };
-      role_sweep(s, last, [](int, auto) {}, [](int, int, auto) {}, sync, drain, emit);
-    }
-    return;
-  }
-  T pre[S::Q][NPT];
-  auto load_a = [&](int plane) {
-    // periodic along a2, or a slab whose ghost planes (two per side) hold the neighbours' data
-    int g2 = plane, g2m = plane - 1, g2p = plane + 1;
-    if (p.wrap2) {
-      g2 = plane < 0 ? plane + p.n2 : (plane >= p.n2 ? plane - p.n2 : plane);
-      g2m = g2 == 0 ? p.n2 - 1 : g2 - 1;
-      g2p = g2 == p.n2 - 1 ? 0 : g2 + 1;
-    }
-    if (in_a) {
-      static_for<S::Q>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2);
-        const int z = e2 == 0 ? g2 : (e2 > 0 ? g2m : g2p);
-        // 32-bit scalar multiply (a plane's first node index fits: N < 2^31), 64-bit scalar add
-        const T *base = p.in + ((long long)q * p.Ni + (long long)((unsigned)z * plane_nodes));
-        if constexpr (MODE == 1) {
-          // Planes beyond a cut: the neighbour's populations as they arrived (halo2_kernel's message: in-plane
-          // populations of its plane next to the cut | the crossing ones of that plane | the crossing ones of the
-          // plane behind it).  The plane index is uniform, so this is scalar work; the populations moving away
-          // from a cut are never pulled across it.
-          constexpr int rank = crossing_rank<S, LAYOUT, q>();
-          if constexpr (e2 >= 0) {
-            if (p.ghost_lo != nullptr && z < p.lo)
-              base = p.ghost_lo + (size_t)(e2 == 0 ? rank : (z == p.lo - 1 ? NC + rank : NC + NU + rank)) * plane_nodes;
-          }
-          if constexpr (e2 <= 0) {
-            if (p.ghost_hi != nullptr && z >= p.hi)
-              base = p.ghost_hi + (size_t)(e2 == 0 ? rank : (z == p.hi ? NC + rank : NC + ND + rank)) * plane_nodes;
-          }
-        }
-        static_for<NPT>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          pre[q][k] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + voff[k][e1 + 1][e0 + 1]);
-        });
-      });
-    }
-  };
-  // r = index of the plane relative to s - 1; r3 = r % 3
-  auto compute_a = [&](int r, int r3) {
-    if (in_a) {
-      if constexpr (COLL == 1)
-        static_for<NPT>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau_inv); });
-      if constexpr (COLL == 3)
-        static_for<NPT>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau, p.smag_c2); });
-      static_for<S::Q>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-        static_for<NPT>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          if constexpr (e2 > 0) lds_u[r & 3][rank][a_at[k]] = pre[q][k];
-          else if constexpr (e2 == 0) lds_c[r3][rank][a_at[k]] = pre[q][k];
-          else lds_d[r & 1][rank][a_at[k]] = pre[q][k];
-        });
-      });
-    }
-  };
-  T f[S::Q][NPB];
-  auto read_b = [&](int r, int r3) {                 // output plane with relative index r
-    if (in_b) {
-      static_for<S::Q>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-        static_for<NPB>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          const int at = b_at[k] - e1 * H0 - e0;
-          if constexpr (e2 > 0) f[q][k] = lds_u[(r - 1) & 3][rank][at];
-          else if constexpr (e2 == 0) f[q][k] = lds_c[r3][rank][at];
-          else f[q][k] = lds_d[(r + 1) & 1][rank][at];
-        });
-      });
-    }
-  };
-  auto collide_b = [&]() {
-    if (in_b) {
-      if constexpr (COLL == 1)
-        static_for<NPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau_inv); });
-      if constexpr (COLL == 3)
-        static_for<NPB>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau, p.smag_c2); });
-    }
-  };
-  // packing: this workgroup writes halo messages (PACK kernels; a launch that covers a whole slab runs the
-  // sweep of its other workgroups without that code -- with it in the loop they took twice as long)
-  // how: 0 = nontemporal stores; 1 = also the halo messages (PACK kernels); 2 = stores that are performed at
-  // device scope (write-through: another XCD's kernel may read them while this launch still runs)
-  auto store_b = [&](int k2, auto how) {
-    constexpr int HOW = decltype(how)::value;
-    constexpr bool PACKING = HOW == 1;
-    if (in_b) {
-      static_for<S::Q>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        T *base = p.out + ((long long)q * p.No + (long long)((unsigned)k2 * plane_nodes));
-        static_for<NPB>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          T *at = reinterpret_cast<T *>(reinterpret_cast<char *>(base) + out_off[k]);
-          if constexpr (HOW == 2) {
-            using Bits = std::conditional_t<sizeof(T) == 4, unsigned, unsigned long long>;
-            __hip_atomic_store(reinterpret_cast<Bits *>(at), __builtin_bit_cast(Bits, f[q][k]), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-          } else {
-            __builtin_nontemporal_store(f[q][k], at);
-          }
-        });
-        // Slab edge launches (PACK) also write the two-step halo message (layout of halo2_kernel: in-plane
-        // populations of the plane next to the cut | its crossing populations | the crossing
-        // populations of the plane behind it), possibly straight into the neighbour's memory.
-        constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-        if constexpr (PACKING) {
-        if (p.pack_lo != nullptr && e2 <= 0) {
-          const int d = k2 - p.pack_lo_plane;                    // 0: near plane, 1: far plane
-          if (d == 0 || (d == 1 && e2 < 0)) {
-            const int slot = e2 == 0 ? rank : (d == 0 ? NC + rank : NC + ND + rank);
-            T *msg = p.pack_lo + (size_t)slot * plane_nodes;
-            static_for<NPB>([&](auto kc) {
-              constexpr int k = decltype(kc)::value;
-              *reinterpret_cast<T *>(reinterpret_cast<char *>(msg) + out_off[k]) = f[q][k];
-            });
-          }
-        }
-        if (p.pack_hi != nullptr && e2 >= 0) {
-          const int d = p.pack_hi_plane - k2;
-          if (d == 0 || (d == 1 && e2 > 0)) {
-            const int slot = e2 == 0 ? rank : (d == 0 ? NC + rank : NC + NU + rank);
-            T *msg = p.pack_hi + (size_t)slot * plane_nodes;
-            static_for<NPB>([&](auto kc) {
-              constexpr int k = decltype(kc)::value;
-              *reinterpret_cast<T *>(reinterpret_cast<char *>(msg) + out_off[k]) = f[q][k];
-            });
-          }
-        }
-        }
-      });
-    }
-  };
-
-  // intermediate planes s-1 .. s+seg_len are needed (relative indices 0 .. seg_len+1)
-  const int last = s + seg_len < range_end ? s + seg_len : range_end;
-  if constexpr (PACK) {
-    if (last - s == 2) {
-      // Slab edge launch: two output planes per workgroup, i.e. four intermediate planes and no sweep to amortise a
-      // serial prologue over, with all 256 workgroups of a round in lock-step (memory idle while they collide, compute
-      // units idle while they load).  Straight-line schedule on two register sets with the loads of plane j + 1 in
-      // flight behind the collide of plane j -- what the steady state of the sweep does.  Every thread loads (the 44
-      // of 704 without an intermediate node read the plane's first node): a load under `if (in_a)` leaves the other
-      // lanes' registers undefined, the compiler zeroes them AFTER the loads and that write waits for the loads.
-      if (!in_a) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) voff[0][a][c] = 0u;
-      }
-      auto load_into = [&](int plane, T (&dst)[S::Q][1]) {
-        const int g2 = plane, g2m = plane - 1, g2p = plane + 1;      // slab layout: no wrap along a2
-        static_for<S::Q>([&](auto qc) {
-          constexpr int q = decltype(qc)::value;
-          constexpr int e0 = M::e(q, 0), e1 = M::e(q, 1), e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-          const int z = e2 == 0 ? g2 : (e2 > 0 ? g2m : g2p);
-          const T *base = p.in + ((long long)q * p.Ni + (long long)((unsigned)z * plane_nodes));
-          if constexpr (e2 >= 0) {
-            if (p.ghost_lo != nullptr && z < p.lo)
-              base = p.ghost_lo + (size_t)(e2 == 0 ? rank : (z == p.lo - 1 ? NC + rank : NC + NU + rank)) * plane_nodes;
-          }
-          if constexpr (e2 <= 0) {
-            if (p.ghost_hi != nullptr && z >= p.hi)
-              base = p.ghost_hi + (size_t)(e2 == 0 ? rank : (z == p.hi ? NC + rank : NC + ND + rank)) * plane_nodes;
-          }
-          dst[q][0] = *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + voff[0][e1 + 1][e0 + 1]);
-        });
-      };
-      // KEEP: which populations of the plane anybody reads -- bit 0: those moving up (the output plane above pulls
-      // them), bit 1: in-plane, bit 2: moving down.  The first intermediate plane only feeds the output plane above
-      // it, the last one only the plane below: 38 of the 76 post-collision populations of the four planes are needed,
-      // the others are neither stored nor (dead code to the compiler) computed.
-      auto collide_into_lds = [&](T (&src)[S::Q][1], int r, int r3, auto keep) {
-        constexpr int KEEP = decltype(keep)::value;
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
-        if (in_a) {
-          static_for<S::Q>([&](auto qc) {
-            constexpr int q = decltype(qc)::value;
-            constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
-            if constexpr (e2 > 0) { if constexpr (KEEP & 1) lds_u[r & 3][rank][a_at[0]] = src[q][0]; }
-            else if constexpr (e2 == 0) { if constexpr (KEEP & 2) lds_c[r3][rank][a_at[0]] = src[q][0]; }
-            else { if constexpr (KEEP & 4) lds_d[r & 1][rank][a_at[0]] = src[q][0]; }
-          });
-        }
-      };
-      using Up = std::integral_constant<int, 1>;
-      using UpIn = std::integral_constant<int, 3>;
-      using InDown = std::integral_constant<int, 6>;
-      using Down = std::integral_constant<int, 4>;
-      // (sched_barrier: the register-minimising scheduler of this unit sinks the loads behind the collide otherwise)
-      T pre2[S::Q][1];
-      load_into(s - 1, pre); load_into(s, pre2);
-      __builtin_amdgcn_sched_barrier(0);
-      collide_into_lds(pre, 0, 0, Up{});
-      __builtin_amdgcn_sched_barrier(0);
-      load_into(s + 1, pre);
-      __builtin_amdgcn_sched_barrier(0);
-      collide_into_lds(pre2, 1, 1, UpIn{});
-      __builtin_amdgcn_sched_barrier(0);
-      load_into(s + 2, pre2);
-      __builtin_amdgcn_sched_barrier(0);
-      collide_into_lds(pre, 2, 2, InDown{});
-      lds_barrier();
-      read_b(1, 1);
-      collide_into_lds(pre2, 3, 0, Down{});
-      collide_b();
-      store_b(s, std::integral_constant<int, 1>{});
-      lds_barrier();
-      read_b(2, 2);
-      collide_b();
-      store_b(s + 1, std::integral_constant<int, 1>{});
-      return;
-    }
-  }
-  load_a(s - 1); compute_a(0, 0);
-  load_a(s);     compute_a(1, 1);
-  load_a(s + 1); compute_a(2, 2);
-  if (s + 2 <= last) load_a(s + 2);
-  int r = 1, r3 = 1;                                  // output plane k has relative index k - s + 1
-  auto interval = [&](int k, auto how) {
-    lds_barrier();                                    // planes up to k + 1 complete; reads of k - 1 done
-    read_b(r, r3);                                    // 19 LDS reads in flight ...
-    if (k + 2 <= last) {
-      compute_a(r + 2, r3 == 0 ? 2 : r3 - 1);         // ... behind the collide of plane k + 2; (r + 2) % 3
-      if (k + 3 <= last) load_a(k + 3);
-    }
-    collide_b();
-    store_b(k, how);
-    ++r;
-    r3 = r3 == 2 ? 0 : r3 + 1;
-  };
-  int k = s;
-  using Plain = std::integral_constant<int, 0>;
-  if constexpr (PACK) {
-    // edge launches: every workgroup also writes the halo messages.  (This copy of the loop is slow -- 12 spilled
-    // registers, message stores -- and even its presence slows the other copy: a launch over the whole slab
-    // with packing first segments took 1.0 instead of 0.6 ms, so that launch does not pack.)
-    for (; k < last; ++k) interval(k, std::integral_constant<int, 1>{});
-  } else if constexpr (MODE == 2) {
-    if (second || b == 0) {
-      // Launch over the whole slab: the planes next to a cut are this workgroup's last two (upper edge) or first
-      // two (lower edge).  They are stored at device scope, and once the stores have been performed the
-      // workgroup counts itself done.  No release fence: at device scope that is a write-back of the XCD's
-      // whole L2 -- 1024 of them made the launch take 0.99 instead of 0.66 ms.
-      const int until = second ? last : (s + 2 < last ? s + 2 : last);
-      for (; k < until; ++k) interval(k, std::integral_constant<int, 2>{});
-      // every wave waits until ITS edge-plane stores have been acknowledged (they are write-through stores at
-      // device scope, so the acknowledgement means "performed in memory"): a workgroup-scope release alone emits
-      // no vmcnt wait on gfx950, and the counter below must not become visible before the planes are
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-      if (tid == 0) __hip_atomic_fetch_add(p.signal, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  for (; k < last; ++k) interval(k, Plain{});
+// ... with a body force (COLL = 4 + the collision): the plain one-role sweep on KParamsF.  The sweep is one text
+// (twostep_sweep.inc) in both kernels rather than a function both call: inlined from a function the unforced kernels
+// came out with another register allocation (156 -> 162 VGPRs for the BGK sweep of D3Q19 fp32), and they are to stay
+// instruction for instruction what they were.
+template <typename T, class S, int LAYOUT, int COLL, int T0_, int T1, int NPT = 1, int MODE = 0,
+          int NPB = NPT, int SCHED = 0>
+__global__ void __launch_bounds__((TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64)
+lbm2_kernel(const KParamsF<T> p, const int seg_len) {
+  static_assert(COLL == 5 || COLL == 7, "a body force exists for BGK (5) and Smagorinsky (7)");
+#include "twostep_sweep.inc"
 }
 
 // One wave on the communication stream: returns when *counter has reached `target` (the edge workgroups of

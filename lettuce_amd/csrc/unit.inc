@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <type_traits>
 
 #include "dispatch.hpp"
 #include "kernels.hpp"
@@ -19,6 +20,9 @@
 // setting than the one-role kernels beside it (Makefile)
 // 4 = the one-step kernels of the Smagorinsky collision of a 3-D unit (inst4_<tag>.hip): an object of its own so that
 // the build takes no longer than before (the D3Q27 fp32 unit with its KBC kernels is the longest job)
+// 5 = the kernels with a body force (the kernels' COLL = 5: BGK, 7: Smagorinsky) of every unit (inst5_<tag>.hip): every
+// one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep -- objects of their own, so
+// that the objects of the unforced kernels are what they were
 #ifndef LT_PART
 #define LT_PART 0
 #endif
@@ -43,14 +47,29 @@ constexpr int kTwiceW = 256 / (int)sizeof(T);
 constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
                         : (sizeof(T) == 4 && kTwicePerNode * (kTwiceW + 2) * 6 <= 160 * 1024 ? 4 : 0);
 
-#if LT_PART < 2 || LT_PART == 4
+// uniform body force (lt_plan_set_force): the acceleration permuted from the logical order x, y, z to the memory axes
+// of the layout, as the kernels read the velocity
+template <int LAYOUT>
+void set_force(KParamsF<T> &p, const StepArgs &a) {
+  using M = MemMap<S, LAYOUT>;
+  p.accel[0] = p.accel[1] = p.accel[2] = T(0);
+  p.shift[0] = p.shift[1] = p.shift[2] = T(0);
+  for (int c = 0; c < S::D; ++c) {
+    p.accel[M::memory(c)] = (T)a.accel[c];
+    p.shift[M::memory(c)] = (T)a.ueq_scale * (T)a.accel[c];     // guo.py:27-29: the product in the tensor's precision
+  }
+  p.source_scale = (T)a.source_scale;
+}
+
+#if LT_PART < 2 || LT_PART == 4 || LT_PART == 5
 
 // one node per thread: the kernels' VEC = 1, SHIFT = 0
 template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
 int launch(const StepArgs &a, bool name_only, const char **name) {
   constexpr bool STREAM = MODE != kCollideOnly, COLLIDE = MODE != kStreamOnly;
   constexpr bool OCC4 = (COLL == 2 && MASKED && sizeof(T) == 4 && S::Q == 27 && ABBD == 0);
-  void (*kern)(const KParams<T>);
+  using P = std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>;
+  void (*kern)(const P);
   if constexpr (OCC4)
     kern = lbm_kernel_occ4<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK>;
   else
@@ -64,7 +83,7 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
     *name = buf;
     return 0;
   }
-  KParams<T> p;
+  P p;
   p.in = static_cast<const T *>(a.in);
   p.out = static_cast<T *>(a.out);
   p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
@@ -82,6 +101,7 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   p.inv_beta = (T)(1. / beta);
   p.tau = (T)a.tau;
   p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
+  if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
   p.node = a.node;
   p.nsm_bits = a.nsm_bits;
   p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
@@ -131,7 +151,7 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
   LT_TRY(LAYOUT, COLL, kFused, MASKED)         \
   LT_TRY(LAYOUT, COLL, kCollideOnly, MASKED)
 
-#if LT_PART != 1
+#if LT_PART != 1 && LT_PART != 5
 // The one-step kernels of the Smagorinsky collision (COLL 3): every variant BGK has.  The 3-D units build them in
 // an object of their own (LT_PART 4, inst4_<tag>.hip), beside the rest.
 int one_step_smagorinsky(const StepArgs &a, bool name_only, const char **name) {
@@ -155,20 +175,46 @@ int one_step_smagorinsky(const StepArgs &a, bool name_only, const char **name) {
 #endif
   return kNoKernel;
 }
-#endif  // LT_PART != 1
+#endif  // LT_PART != 1 && LT_PART != 5
 
-#endif  // LT_PART < 2 || LT_PART == 4
+#if LT_PART == 5
+// The one-step kernels with a body force (COLL 5 = BGK, 7 = Smagorinsky): every variant BGK has
+template <int C>
+int one_step_forced_of(const StepArgs &a, bool name_only, const char **name) {
+  const int coll = a.coll;
+#if LT_IS_3D
+  LT_TRY_THREE_AXES(C, kFused) LT_TRY_THREE_AXES(C, kCollideOnly)
+#endif
+  if (a.abb_depth > 1) return kNoKernel;
+  LT_TRY_TWO_OUTLETS(0, C, kFused) LT_TRY_TWO_OUTLETS(0, C, kCollideOnly)
+#if LT_IS_3D
+  LT_TRY_TWO_OUTLETS(1, C, kFused) LT_TRY_TWO_OUTLETS(1, C, kCollideOnly)
+#endif
+  LT_COLLISION_SET(0, C, 0)
+  LT_COLLISION_SET(0, C, 1)
+#if LT_IS_3D
+  LT_TRY_PACK(C, 0)
+  LT_TRY_PACK(C, 1)
+  LT_COLLISION_SET(1, C, 0)
+  LT_COLLISION_SET(1, C, 1)
+#endif
+  return kNoKernel;
+}
+#endif  // LT_PART == 5
 
-#if LT_PART == 2 || LT_PART == 3 || LT_PART == 0
+#endif  // LT_PART < 2 || LT_PART == 4 || LT_PART == 5
+
+#if LT_PART == 2 || LT_PART == 3 || LT_PART == 0 || LT_PART == 5
 // Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
 // returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
 // one node per thread and per block: the kernel's NPT = NPB = 1
 // SCHED 1: separate producer and consumer waves (twostep_roles.hpp)
-// Smagorinsky (COLL 3): the plain one-role sweep of D3Q19 fp32
+// Smagorinsky (COLL 3) and BGK with a body force (COLL 5): the plain one-role sweep of D3Q19 fp32
 template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
 int launch_twice(const StepArgs &a, bool name_only, const char **name) {
   if constexpr (S::D == 3 && T0 > 0 &&
-                (COLL == 0 || COLL == 1 || (COLL == 3 && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
+                (COLL == 0 || COLL == 1 ||
+                 ((COLL == 3 || COLL == 5) && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
     using B = TwoStep<T, S, T0, T1>;
     if (name_only) {
       static char buf[96];
@@ -181,7 +227,8 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
     if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 1 || a.masked || a.planes < 1 || a.p_stride != 1 ||
         (long long)a.n0 * a.n1 * (long long)sizeof(T) >= (1ll << 32))
       return kNoKernel;
-    KParams<T> p;
+    using P = std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>;
+    P p;
     memset(&p, 0, sizeof p);
     p.in = static_cast<const T *>(a.in);
     p.out = static_cast<T *>(a.out);
@@ -198,6 +245,7 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
     p.tau_inv = (T)(1.0 / a.tau);
     p.tau = (T)a.tau;
     p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);
+    if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
     p.nb = a.shift == 3 ? 1 : (a.shift == 4 ? 2 : 0);   // A/B: 1 = no XCD-aware renumbering of the workgroups, 2 = per segment layer
     p.pack_lo = static_cast<T *>(a.pack_lo);
     p.pack_hi = static_cast<T *>(a.pack_hi);
@@ -212,8 +260,8 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
     const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len +
                                                                    (a.planes2 + a.seg_len - 1) / a.seg_len));
     constexpr int threads = SCHED ? RoleWaves<B::NI, B::NO>::THREADS : (B::NI + 63) / 64 * 64;
-    hipLaunchKernelGGL((lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1, SCHED>), dim3(grid), dim3(threads), 0,
-                       a.stream, p, a.seg_len);
+    void (*kern)(const P, const int) = lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1, SCHED>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, a.stream, p, a.seg_len);
     return (int)hipGetLastError();
   } else {
     return kNoKernel;
@@ -226,6 +274,19 @@ int twice_roles(const StepArgs &a, bool name_only, const char **name) {
   constexpr int W = kTwiceW, R = kTwiceR;
   if (a.layout == 0) return launch_twice<0, 1, W, R, 0, 1>(a, name_only, name);
   return launch_twice<1, 1, W, R, 0, 1>(a, name_only, name);
+}
+#elif LT_PART == 5
+// the two-step launches with a body force: plain sweeps of periodic plans (no packing, no signalling launch)
+int twice_forced(const StepArgs &a, bool name_only, const char **name) {
+  constexpr int W = kTwiceW, R = kTwiceR;
+  if constexpr (R > 0) {
+    if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
+    if (a.layout == 0 && a.coll == 5) return launch_twice<0, 5, W, R>(a, name_only, name);
+    if (a.layout == 1 && a.coll == 5) return launch_twice<1, 5, W, R>(a, name_only, name);
+    // (Smagorinsky with a force, COLL 7: 168 VGPRs and 84-92 bytes of scratch per lane under every scheduler setting
+    // where the unforced sweep has 168 and none -- not built, the plan keeps the one-step kernel: DESIGN.md section 4)
+  }
+  return kNoKernel;
 }
 #else
 // the unmasked 3-D two-step launches of this unit
@@ -259,8 +320,8 @@ int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
   }
   return kNoKernel;
 }
-#endif  // LT_PART == 3, else
-#endif  // LT_PART 0, 2, 3
+#endif  // LT_PART == 3, 5, else
+#endif  // LT_PART 0, 2, 3, 5
 
 #if LT_PART < 2
 // Two fused steps per launch for plans with boundaries (twostep_masked.hpp, lbm2m_kernel): whole periodic
@@ -437,6 +498,7 @@ int launch_many(const StepArgs &a, bool name_only, const char **name) {
 
 int dispatch(const StepArgs &a, bool name_only, const char **name) {
   const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
+  if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name_only, name);   // body force: inst5_<tag>.hip
   if (a.mode == kFusedMany) {
     if (a.masked) {
       if (coll == 0) return launch_many<0, true>(a, name_only, name);
@@ -655,6 +717,14 @@ int LT_CAT(twice_, LT_TAG)(const StepArgs &a, bool name_only, const char **name)
 #elif LT_PART == 3
 int LT_CAT(roles_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
   return twice_roles(a, name_only, name);
+}
+#elif LT_PART == 5
+int LT_CAT(forced_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
+  if (a.mode == kFusedTwice) return S::D == 3 ? twice_forced(a, name_only, name) : kNoKernel;
+  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
+  if (a.coll == 5) return one_step_forced_of<5>(a, name_only, name);
+  if (a.coll == 7) return one_step_forced_of<7>(a, name_only, name);
+  return kNoKernel;
 }
 #elif LT_PART == 4
 int LT_CAT(smag_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {

@@ -2,7 +2,7 @@
 ``from lettuce_amd.ext import BGKCollision`` works like ``from lettuce.ext import BGKCollision``."""
 import importlib
 
-_MODULES = ("_equilibrium", "_collision", "_boundary", "_flows", "_reporter")
+_MODULES = ("_equilibrium", "_force", "_collision", "_boundary", "_flows", "_reporter")
 __all__ = ["D1Q3", "D2Q9", "D3Q15", "D3Q19", "D3Q27"]
 
 from .._stencil import D1Q3, D2Q9, D3Q15, D3Q19, D3Q27  # noqa: E402,F401

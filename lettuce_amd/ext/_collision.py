@@ -3,8 +3,9 @@
 Each ``__call__`` is a pure whole-field function ``flow -> tensor`` usable outside a
 ``Simulation`` (the reference's tests call ``collision(flow)`` directly).  On a native context
 and for the flow's grid-shaped state it is one launch of the engine's collide kernel;
-otherwise the reference's torch expressions are evaluated.  TRT / MRT / regularised
-collisions and forcing schemes on the engine are out of scope.
+otherwise the reference's torch expressions are evaluated.  BGK and Smagorinsky take a body force
+(``force=Guo(...)`` / ``ShanChen(...)``, ext/_force.py), on the engine when its acceleration is uniform.
+TRT / MRT / regularised collisions are out of scope.
 """
 import warnings
 from typing import AnyStr, Optional
@@ -13,15 +14,17 @@ import torch
 
 from .._simulation import Collision
 from ..native_desc import NativeCollision
+from ._force import Force
 from ..util import LettuceException
 
 __all__ = ["BGKCollision", "KBCCollision", "KBCCollision2D", "KBCCollision3D", "NoCollision",
            "SmagorinskyCollision"]
 
 
-def _engine_collide(flow, kind, tau, constant=None):
+def _engine_collide(flow, kind, tau, constant=None, force=None):
     """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``constant``: the
-    Smagorinsky constant, a per-launch setting of the kind's one plan (handed over before every collide)."""
+    Smagorinsky constant, ``force``: the collision's body force (a Force or None) -- per-launch settings of the
+    kind's one plan, handed over before every collide."""
     if flow._engine_plan(flow.f) is None:
         return None
     plans = flow.__dict__.setdefault("_collision_plans", {})
@@ -31,6 +34,11 @@ def _engine_collide(flow, kind, tau, constant=None):
                            device=flow.f.device)
     if constant is not None:
         plans[kind].set_smagorinsky(constant)
+    if kind in ("bgk", "smagorinsky"):
+        if force is None:
+            plans[kind].set_force(None)
+        else:
+            plans[kind].set_force(*force.native_generator().plan_args())
     return plans[kind].collide(flow.f, torch.empty_like(flow.f), tau)
 
 
@@ -47,10 +55,11 @@ class BGKCollision(Collision):
         self.force = force
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
-        if self.force is None:
-            out = _engine_collide(flow, "bgk", self.tau)
+        if self.native_available():
+            out = _engine_collide(flow, "bgk", self.tau, force=self.force)
             if out is not None:
                 return out
+        if self.force is None:
             u = flow.u() + 0
             feq = flow.equilibrium(flow, u=u)
             return flow.f - 1.0 / self.tau * (flow.f - feq) + 0
@@ -64,10 +73,11 @@ class BGKCollision(Collision):
         return type(self).__name__
 
     def native_available(self) -> bool:
-        return self.force is None
+        return self.force is None or (isinstance(self.force, Force) and self.force.native_available())
 
     def native_generator(self) -> "NativeCollision":
-        return NativeCollision("bgk", tau=lambda flow: self.tau, arithmetic=getattr(self, "arithmetic", "exact"))
+        return NativeCollision("bgk", tau=lambda flow: self.tau, arithmetic=getattr(self, "arithmetic", "exact"),
+                               force=None if self.force is None else self.force.native_generator())
 
 
 class KBCCollision(Collision):
@@ -192,7 +202,7 @@ class SmagorinskyCollision(Collision):
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
         if self.native_available():
-            out = _engine_collide(flow, "smagorinsky", self.tau, self.constant)
+            out = _engine_collide(flow, "smagorinsky", self.tau, self.constant, force=self.force)
             if out is not None:
                 return out
         rho = flow.rho()
@@ -220,10 +230,12 @@ class SmagorinskyCollision(Collision):
         return flow.f - 1.0 / self.tau_eff * (flow.f - feq) + si
 
     def native_available(self) -> bool:
-        return self.force is None and self.iterations == 2
+        return self.iterations == 2 and (
+            self.force is None or (isinstance(self.force, Force) and self.force.native_available()))
 
     def native_generator(self) -> "NativeCollision":
-        return NativeCollision("smagorinsky", tau=lambda flow: self.tau, constant=lambda flow: self.constant)
+        return NativeCollision("smagorinsky", tau=lambda flow: self.tau, constant=lambda flow: self.constant,
+                               force=None if self.force is None else self.force.native_generator())
 
 
 class NoCollision(Collision):

@@ -3,8 +3,8 @@ Taylor-Green vortex (2-D/3-D), flow around an obstacle, doubly periodic shear la
 the reference, plus the 3-D variant BASELINE.json's cfg5 asks for).
 
 API of lettuce/ext/_flows/_ext_flow.py:8-42, taylorgreen.py:16-122, obstacle.py:54-151,
-doublyshear.py:19-80.  The other demo flows (Couette, Poiseuille, cavity, decaying turbulence)
-are out of scope.
+doublyshear.py:19-80, poiseuille.py:19-95 (the channel a body force drives).  The other demo flows (Couette,
+cavity, decaying turbulence) are out of scope.
 """
 import warnings
 from abc import ABC, abstractmethod
@@ -21,7 +21,7 @@ from ._boundary import AntiBounceBackOutlet, BounceBackBoundary, EquilibriumBoun
 from ._equilibrium import QuadraticEquilibrium
 
 __all__ = ["ExtFlow", "TaylorGreenVortex", "TaylorGreenVortex2D", "TaylorGreenVortex3D",
-           "Obstacle", "DoublyPeriodicShear2D", "DoublyPeriodicShear3D", "flow_by_name"]
+           "Obstacle", "DoublyPeriodicShear2D", "DoublyPeriodicShear3D", "PoiseuilleFlow2D", "flow_by_name"]
 
 
 class ExtFlow(Flow, ABC):
@@ -336,10 +336,72 @@ class DoublyPeriodicShear3D(ExtFlow):
         return []
 
 
+class PoiseuilleFlow2D(ExtFlow):
+    """Plane channel between bounce-back rows at y = 0 and y = -1, periodic along x, driven by a body force
+    (lettuce/ext/_flows/poiseuille.py:19-95): pass ``flow.acceleration`` to a ``Guo`` or ``ShanChen`` force of the
+    collision.  The walls sit half a lattice spacing inside the boundary rows, which ``analytic_solution`` accounts
+    for."""
+
+    def __init__(self, context: "Context", resolution: Union[int, List[int]], reynolds_number,
+                 mach_number, stencil: Optional["Stencil"] = None,
+                 equilibrium: Optional["Equilibrium"] = None, initialize_with_zeros=True):
+        self.stencil = D2Q9() if stencil is None else (stencil() if callable(stencil) else stencil)
+        self.initialize_with_zeros = initialize_with_zeros
+        super().__init__(context, resolution, reynolds_number, mach_number, self.stencil,
+                         equilibrium)
+
+    def analytic_solution(self, t=0):
+        half_lattice_spacing = 0.5 / self.resolution[0]
+        x, y = self.grid
+        nu = self.units.viscosity_pu
+        rho = 1
+        ux = (self.acceleration[0] / (2 * rho * nu)
+              * ((y - half_lattice_spacing) * (1 - half_lattice_spacing - y)))
+        uy = self.context.zero_tensor(self.resolution)
+        u = torch.stack([ux, uy], dim=0)
+        p = y * 0 + self.units.convert_density_lu_to_pressure_pu(rho)
+        return p, u
+
+    def initial_pu(self):
+        if self.initialize_with_zeros:
+            zeros = self.context.zero_tensor(self.resolution)
+            return zeros[None, ...], torch.stack(2 * [zeros], dim=0)
+        return self.analytic_solution()
+
+    def make_units(self, reynolds_number, mach_number, resolution: List[int]) -> "UnitConversion":
+        return UnitConversion(reynolds_number=reynolds_number, mach_number=mach_number,
+                              characteristic_length_lu=resolution[0] - 1, characteristic_length_pu=1,
+                              characteristic_velocity_pu=1)
+
+    def make_resolution(self, resolution, stencil=None) -> List[int]:
+        if isinstance(resolution, list):
+            assert len(resolution) == self.stencil.d
+        if isinstance(resolution, int):
+            resolution = [resolution] * self.stencil.d
+        return resolution
+
+    @property
+    def grid(self):
+        xyz = tuple(torch.linspace(0, 1, steps=n, device=self.context.device, dtype=self.context.dtype)
+                    for n in self.resolution)
+        return torch.meshgrid(*xyz, indexing="ij")
+
+    @property
+    def boundaries(self):
+        mask = self.context.zero_tensor(self.resolution, dtype=bool)
+        mask[:, [0, -1]] = True
+        return [BounceBackBoundary(mask=mask)]
+
+    @property
+    def acceleration(self):
+        return self.context.convert_to_tensor([0.001, 0])
+
+
 # name -> flow class, as used by `lettuce benchmark` (lettuce/ext/_flows/_flow_by_name.py:10-16)
 flow_by_name = {
     "taylor2D": [TaylorGreenVortex, D2Q9],
     "taylor3D": [TaylorGreenVortex, D3Q19],
     "shear2D": [DoublyPeriodicShear2D, D2Q9],
     "shear3D": [DoublyPeriodicShear3D, D3Q19],
+    "poiseuille2d": [PoiseuilleFlow2D, D2Q9],
 }

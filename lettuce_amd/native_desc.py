@@ -7,14 +7,29 @@ protocol returns plain descriptors: an enum-like ``kind`` plus the scalar parame
 kernels take.
 """
 from dataclasses import dataclass, field
-from typing import Callable, Optional
+from typing import Callable, Optional, Tuple
 
-__all__ = ["NativeEquilibrium", "NativeCollision", "NativeBoundary"]
+__all__ = ["NativeEquilibrium", "NativeCollision", "NativeBoundary", "NativeForce"]
 
 
 @dataclass
 class NativeEquilibrium:
     kind: str = "quadratic"
+
+
+@dataclass
+class NativeForce:
+    """A uniform body force inside the engine's collide kernels (``lt_plan_set_force``).  The three values are read
+    late, per batch, because the reference's schemes read ``force.acceleration`` and ``force.tau`` on every call
+    (lettuce/ext/_force/guo.py:14-31, shan_chen.py:14-25)."""
+    kind: str                                  # 'guo' | 'shan_chen'
+    acceleration: Callable[[], Tuple[float, ...]]      # lattice units, logical order x, y, z
+    ueq_scale: Callable[[], float]             # u* = j / rho + ueq_scale * a / rho
+    source_scale: Callable[[], float]          # factor of the source term (0: none)
+
+    def plan_args(self) -> Tuple[Tuple[float, ...], float, float]:
+        """the arguments of ``Plan.set_force`` now (hashable: part of the steppers' carry key)"""
+        return (tuple(float(a) for a in self.acceleration()), float(self.ueq_scale()), float(self.source_scale()))
 
 
 @dataclass
@@ -30,6 +45,8 @@ class NativeCollision:
     # 'smagorinsky': the constant, evaluated per batch like tau (the reference reads collision.constant on every
     # call, lettuce/ext/_collision/smagorinsky_collision.py:32); None for the other kinds
     constant: Optional[Callable[["Flow"], float]] = None
+    # 'bgk' / 'smagorinsky': the body force of the collision, or None
+    force: Optional[NativeForce] = None
 
 
 @dataclass
