@@ -41,18 +41,17 @@ struct Unit {
   int q, d;
 };
 
-const Unit kUnits[5][2] = {
-    {{lt::step_d2q9_f32, lt::aux_d2q9_f32, lt::name_d2q9_f32, 9, 2},
-     {lt::step_d2q9_f64, lt::aux_d2q9_f64, lt::name_d2q9_f64, 9, 2}},
-    {{lt::step_d3q19_f32, lt::aux_d3q19_f32, lt::name_d3q19_f32, 19, 3},
-     {lt::step_d3q19_f64, lt::aux_d3q19_f64, lt::name_d3q19_f64, 19, 3}},
-    {{lt::step_d3q27_f32, lt::aux_d3q27_f32, lt::name_d3q27_f32, 27, 3},
-     {lt::step_d3q27_f64, lt::aux_d3q27_f64, lt::name_d3q27_f64, 27, 3}},
-    {{lt::step_d1q3_f32, lt::aux_d1q3_f32, lt::name_d1q3_f32, 3, 1},
-     {lt::step_d1q3_f64, lt::aux_d1q3_f64, lt::name_d1q3_f64, 3, 1}},
-    {{lt::step_d3q15_f32, lt::aux_d3q15_f32, lt::name_d3q15_f32, 15, 3},
-     {lt::step_d3q15_f64, lt::aux_d3q15_f64, lt::name_d3q15_f64, 15, 3}},
-};
+// every unit of dispatch.hpp's list, which is in the order of the ABI's enums: kUnits[2 * stencil + dtype]
+#define LT_UNIT_ROW(tag) {lt::step_##tag, lt::aux_##tag, lt::name_##tag, LT_FIELD(q, tag), LT_FIELD(d, tag)},
+const Unit kUnits[] = {LT_UNITS(LT_UNIT_ROW)};
+#undef LT_UNIT_ROW
+static_assert(LT_D2Q9 == 0 && LT_D3Q19 == 1 && LT_D3Q27 == 2 && LT_D1Q3 == 3 && LT_D3Q15 == 4 && LT_F32 == 0 && LT_F64 == 1 &&
+              sizeof kUnits == 10 * sizeof(Unit), "LT_UNITS is not in the order of lt_stencil and lt_dtype");
+// has the unit a kernel for these arguments?  (its name goes into a buffer of ours)
+bool has_kernel(const Unit &unit, const lt::StepArgs &a) {
+  char name[192];
+  return unit.name(a, lt::NameBuf{name, sizeof name}) != nullptr;
+}
 
 constexpr int kReduceBlocks = 1024;
 
@@ -539,7 +538,7 @@ const char *force_refuses(const lt_plan *p, int mode) {
     lt::StepArgs a;
     memset(&a, 0, sizeof a);
     a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = lt::kFusedTwice;
-    if (!p->unit.name(a)) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
+    if (!has_kernel(p->unit, a)) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
   }
   return nullptr;
 }
@@ -729,7 +728,7 @@ bool two_step_possible(lt_plan *p, const char **why) {
   a.masked = p->masked;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? tile.width : 0;
-  if (!p->unit.name(a)) {
+  if (!has_kernel(p->unit, a)) {
     *why = "no two-step kernel for this lattice / dtype / collision";
     return false;
   }
@@ -894,7 +893,7 @@ bool many_step_wanted(lt_plan *p) {
   memset(&a, 0, sizeof a);
   a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = lt::kFusedMany;
   a.masked = p->masked;
-  if (!p->unit.name(a)) return false;
+  if (!has_kernel(p->unit, a)) return false;
   if (p->many == 1) return true;
   // automatic only where the many-step kernel is bit-identical to the one-step kernel, so that the
   // result of n steps does not depend on how the caller splits them into batches (KBC agrees at
@@ -1080,7 +1079,7 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   if (d->stencil < 0 || d->stencil > 4) return fail(LT_ERR_UNSUPPORTED, "stencil %d", d->stencil);
   if (d->dtype < 0 || d->dtype > 1) return fail(LT_ERR_UNSUPPORTED, "dtype %d (fp32/fp64 only)", d->dtype);
   if (d->collision < 0 || d->collision > LT_COLLISION_SMAGORINSKY) return fail(LT_ERR_UNSUPPORTED, "collision %d", d->collision);
-  const Unit unit = kUnits[d->stencil][d->dtype];
+  const Unit unit = kUnits[2 * d->stencil + d->dtype];
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   if (d->collision == LT_COLLISION_KBC && d->stencil != LT_D2Q9 && d->stencil != LT_D3Q27)
     return fail(LT_ERR_UNSUPPORTED, "KBC collision exists for D2Q9 and D3Q27 only");
@@ -1392,10 +1391,9 @@ const char *lt_plan_kernel_name(lt_plan *p) {
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
   a.shift = p->shift;
-  if (a.mode == lt::kFusedTwice && !p->unit.name(a)) a.mode = lt::kFused;
+  if (a.mode == lt::kFusedTwice && !has_kernel(p->unit, a)) a.mode = lt::kFused;
   a.tune = resolve_tune(p);
-  const char *n = p->unit.name(a);
-  snprintf(p->kernel_name, sizeof p->kernel_name, "%s", n ? n : "");
+  if (!p->unit.name(a, lt::NameBuf{p->kernel_name, sizeof p->kernel_name})) p->kernel_name[0] = 0;
   return p->kernel_name;
 }
 
@@ -1670,7 +1668,7 @@ int lt_two_step_limits(const lt_plan_desc *d, int32_t masked, int32_t *tile_widt
   if (!d) return fail(LT_ERR_INVALID, "null descriptor");
   if (d->stencil < 0 || d->stencil > 4) return fail(LT_ERR_UNSUPPORTED, "stencil %d", d->stencil);
   if (d->dtype < 0 || d->dtype > 1) return fail(LT_ERR_UNSUPPORTED, "dtype %d (fp32/fp64 only)", d->dtype);
-  const Unit &unit = kUnits[d->stencil][d->dtype];
+  const Unit &unit = kUnits[2 * d->stencil + d->dtype];
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   const int esize = d->dtype == LT_F32 ? 4 : 8;
   long long e0, e1, e2;

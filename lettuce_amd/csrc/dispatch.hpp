@@ -2,6 +2,7 @@
 // per-(stencil, dtype) translation units that instantiate the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace lt {
@@ -64,59 +65,55 @@ struct AuxArgs {
   hipStream_t stream;
 };
 
+// Kernel names are written into a buffer of the caller's (lt_plan_kernel_name: the plan's; a probe: a local one).
+// The units' functions take a pointer to one: null launches, non-null only names the kernel the arguments select.
+struct NameBuf {
+  char *s;
+  size_t cap;
+};
+
 typedef int (*StepFn)(const StepArgs &);
 typedef int (*AuxFn)(const AuxArgs &);
-typedef const char *(*NameFn)(const StepArgs &);
+typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buffer, or null: no kernel
 
-// one set per translation unit inst_<stencil>_<dtype>.hip
-#define LT_DECLARE_UNIT(tag)              \
-  int step_##tag(const StepArgs &);       \
-  int aux_##tag(const AuxArgs &);         \
-  const char *name_##tag(const StepArgs &);
+// The units: one per lattice and scalar type.                lattice, scalar, Q, D, KBC, role-wave sweep
+#define LT_UNIT_d2q9_f32  D2Q9,  float,   9, 2, 1, 0
+#define LT_UNIT_d2q9_f64  D2Q9,  double,  9, 2, 1, 0
+#define LT_UNIT_d3q19_f32 D3Q19, float,  19, 3, 0, 1
+#define LT_UNIT_d3q19_f64 D3Q19, double, 19, 3, 0, 0
+#define LT_UNIT_d3q27_f32 D3Q27, float,  27, 3, 1, 0
+#define LT_UNIT_d3q27_f64 D3Q27, double, 27, 3, 1, 0
+#define LT_UNIT_d1q3_f32  D1Q3,  float,   3, 1, 0, 0
+#define LT_UNIT_d1q3_f64  D1Q3,  double,  3, 1, 0, 0
+#define LT_UNIT_d3q15_f32 D3Q15, float,  15, 3, 0, 0
+#define LT_UNIT_d3q15_f64 D3Q15, double, 15, 3, 0, 0
+// ... in the order of the ABI's enums: lt_stencil the slower index, lt_dtype the faster (api.hip, kUnits)
+#define LT_UNITS(X)                                                                                  \
+  X(d2q9_f32) X(d2q9_f64) X(d3q19_f32) X(d3q19_f64) X(d3q27_f32) X(d3q27_f64) X(d1q3_f32) X(d1q3_f64) \
+  X(d3q15_f32) X(d3q15_f64)
+// LT_FIELD(name, tag): a column of a unit; tag may be a macro (the build's LT_UNIT)
+#define LT_FIELD(name, tag) LT_FIELD_A(name, tag)
+#define LT_FIELD_A(name, tag) LT_FIELD_B(name, LT_UNIT_##tag)
+#define LT_FIELD_B(name, ...) LT_FIELD_##name(__VA_ARGS__)
+#define LT_FIELD_lattice(s, t, q, d, kbc, roles) s
+#define LT_FIELD_scalar(s, t, q, d, kbc, roles) t
+#define LT_FIELD_q(s, t, q, d, kbc, roles) q
+#define LT_FIELD_d(s, t, q, d, kbc, roles) d
+#define LT_FIELD_kbc(s, t, q, d, kbc, roles) kbc
+#define LT_FIELD_roles(s, t, q, d, kbc, roles) roles
 
-// the unmasked 3-D two-step launches of a unit, instantiated by inst2_<tag>.hip (unit.inc, LT_PART)
-#define LT_DECLARE_TWICE(tag) int twice_##tag(const StepArgs &, bool name_only, const char **name);
-LT_DECLARE_TWICE(d3q15_f32)
-LT_DECLARE_TWICE(d3q15_f64)
-LT_DECLARE_TWICE(d3q19_f32)
-LT_DECLARE_TWICE(d3q19_f64)
-LT_DECLARE_TWICE(d3q27_f32)
-LT_DECLARE_TWICE(d3q27_f64)
-// ... and those with separate producer and consumer waves, instantiated by inst3_<tag>.hip
-int roles_d3q19_f32(const StepArgs &, bool name_only, const char **name);
-
-// ... and the one-step Smagorinsky kernels of the 3-D units, instantiated by inst4_<tag>.hip
-#define LT_DECLARE_SMAG(tag) int smag_##tag(const StepArgs &, bool name_only, const char **name);
-LT_DECLARE_SMAG(d3q15_f32)
-LT_DECLARE_SMAG(d3q15_f64)
-LT_DECLARE_SMAG(d3q19_f32)
-LT_DECLARE_SMAG(d3q19_f64)
-LT_DECLARE_SMAG(d3q27_f32)
-LT_DECLARE_SMAG(d3q27_f64)
-
-// ... and the kernels with a body force of every unit, instantiated by inst5_<tag>.hip
-#define LT_DECLARE_FORCED(tag) int forced_##tag(const StepArgs &, bool name_only, const char **name);
-LT_DECLARE_FORCED(d1q3_f32)
-LT_DECLARE_FORCED(d1q3_f64)
-LT_DECLARE_FORCED(d2q9_f32)
-LT_DECLARE_FORCED(d2q9_f64)
-LT_DECLARE_FORCED(d3q15_f32)
-LT_DECLARE_FORCED(d3q15_f64)
-LT_DECLARE_FORCED(d3q19_f32)
-LT_DECLARE_FORCED(d3q19_f64)
-LT_DECLARE_FORCED(d3q27_f32)
-LT_DECLARE_FORCED(d3q27_f64)
-
-LT_DECLARE_UNIT(d1q3_f32)
-LT_DECLARE_UNIT(d1q3_f64)
-LT_DECLARE_UNIT(d3q15_f32)
-LT_DECLARE_UNIT(d3q15_f64)
-LT_DECLARE_UNIT(d2q9_f32)
-LT_DECLARE_UNIT(d2q9_f64)
-LT_DECLARE_UNIT(d3q19_f32)
-LT_DECLARE_UNIT(d3q19_f64)
-LT_DECLARE_UNIT(d3q27_f32)
-LT_DECLARE_UNIT(d3q27_f64)
+// What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
+// on to the unit's other objects -- forced (the kernels with a body force, every unit), sweeps and smagorinsky (3-D
+// units), roles (units with a role-wave sweep).  Declared for every unit, defined where the Makefile builds the part.
+#define LT_DECLARE_UNIT(tag)                                   \
+  int step_##tag(const StepArgs &);                            \
+  int aux_##tag(const AuxArgs &);                              \
+  const char *name_##tag(const StepArgs &, const NameBuf &);   \
+  int forced_##tag(const StepArgs &, const NameBuf *);         \
+  int twice_##tag(const StepArgs &, const NameBuf *);          \
+  int smag_##tag(const StepArgs &, const NameBuf *);           \
+  int roles_##tag(const StepArgs &, const NameBuf *);
+LT_UNITS(LT_DECLARE_UNIT)
 
 // returns -1 when the combination has no instantiated kernel, else the hipError_t of the launch
 constexpr int kNoKernel = -1;

@@ -1,8 +1,6 @@
-// Included by inst_<stencil>_<dtype>.hip after defining LT_S (lattice), LT_T (scalar),
-// LT_TAG (function suffix) and LT_HAS_KBC / LT_IS_3D.  Instantiates every kernel variant the
-// engine offers for that pair and provides the three type-erased entry points.
+// The kernels of one unit (a lattice and a scalar type: dispatch.hpp, LT_UNITS) and the host code that picks and
+// launches them.  inst.hip includes this once per object, with -DLT_UNIT=<tag> -DLT_PART=<name> from the Makefile.
 #include <cstdio>
-#include <cstring>
 #include <algorithm>
 #include <type_traits>
 
@@ -11,26 +9,55 @@
 #include "twostep_masked.hpp"
 #include "twostep2d.hpp"
 
-// LT_PART: 0 = the whole unit in one translation unit; 1 = everything but the unmasked 3-D two-step launches
-// (lbm2_kernel), which inst2_<tag>.hip (LT_PART 2) instantiates -- its own object file, so that it builds beside the
-// rest and can carry its own scheduler setting (Makefile: fp64 D3Q19 is 2.4 % faster with max-ilp, the masked
-// one-step kernels of the same lattice 8 % slower)
-// 3 = the two-step launches with separate producer and consumer waves (the kernel's SCHED = 1) of a unit that has
-// them (LT_HAS_ROLES, inst3_<tag>.hip): again an object of its own, because that schedule wants another scheduler
-// setting than the one-role kernels beside it (Makefile)
-// 4 = the one-step kernels of the Smagorinsky collision of a 3-D unit (inst4_<tag>.hip): an object of its own so that
-// the build takes no longer than before (the D3Q27 fp32 unit with its KBC kernels is the longest job)
-// 5 = the kernels with a body force (the kernels' COLL = 5: BGK, 7: Smagorinsky) of every unit (inst5_<tag>.hip): every
-// one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep -- objects of their own, so
-// that the objects of the unforced kernels are what they were
-#ifndef LT_PART
-#define LT_PART 0
-#endif
-#ifndef LT_HAS_ROLES
-#define LT_HAS_ROLES 0
-#endif
 #define LT_CAT_(a, b) a##b
 #define LT_CAT(a, b) LT_CAT_(a, b)
+#define LT_TAG LT_UNIT
+#define LT_S lt::LT_FIELD(lattice, LT_UNIT)
+#define LT_T LT_FIELD(scalar, LT_UNIT)
+#define LT_IS_3D (LT_FIELD(d, LT_UNIT) == 3)
+#define LT_HAS_KBC LT_FIELD(kbc, LT_UNIT)
+#define LT_HAS_ROLES LT_FIELD(roles, LT_UNIT)
+
+// LT_PART names the object of the unit that is being built (Makefile: build/inst<N>_<tag>.o):
+//   main (inst_)          dispatch(), the auxiliary kernels and the three entry points api.hip calls; the one-step
+//                         kernels without a body force, the many-step, the 2-D and the masked two-step launches.  A 3-D
+//                         unit (LT_IS_3D) leaves its unmasked two-step launches and its Smagorinsky kernels to the next
+//                         three objects and calls them
+//   sweeps (inst2_)       3-D units: the unmasked two-step launches (lbm2_kernel) -- an object of its own, so that it
+//                         builds beside the rest and can carry its own scheduler setting (Makefile: fp64 D3Q19 is 2.4 %
+//                         faster with max-ilp, the masked one-step kernels of the same lattice 8 % slower)
+//   roles (inst3_)        units with LT_HAS_ROLES: the two-step launches with separate producer and consumer waves (the
+//                         kernel's SCHED = 1) -- that schedule wants another scheduler setting than the one-role kernels
+//   smagorinsky (inst4_)  3-D units: the one-step kernels of the Smagorinsky collision -- an object of its own so that
+//                         the build takes no longer than before (D3Q27 fp32 with its KBC kernels is the longest job)
+//   forced (inst5_)       every unit: the kernels with a body force (the kernels' COLL = 5: BGK, 7: Smagorinsky) -- every
+//                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; objects
+//                         of their own, so that the objects of the unforced kernels are what they were
+// LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
+#define LT_PART_main 1
+#define LT_PART_sweeps 2
+#define LT_PART_roles 3
+#define LT_PART_smagorinsky 4
+#define LT_PART_forced 5
+#define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
+#if LT_PART_IS(main)
+#define LT_ONE_STEP 1
+#define LT_SWEEP 0
+#elif LT_PART_IS(sweeps)
+#define LT_ONE_STEP 0
+#define LT_SWEEP 1
+#elif LT_PART_IS(roles)
+#define LT_ONE_STEP 0
+#define LT_SWEEP 1
+#elif LT_PART_IS(smagorinsky)
+#define LT_ONE_STEP 1
+#define LT_SWEEP 0
+#elif LT_PART_IS(forced)
+#define LT_ONE_STEP 1
+#define LT_SWEEP 1
+#else
+#error "LT_PART: main, sweeps, roles, smagorinsky or forced"
+#endif
 
 namespace lt {
 namespace {
@@ -47,6 +74,40 @@ constexpr int kTwiceW = 256 / (int)sizeof(T);
 constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
                         : (sizeof(T) == 4 && kTwicePerNode * (kTwiceW + 2) * 6 <= 160 * 1024 ? 4 : 0);
 
+// The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
+// to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
+template <int COLL>
+using ParamsOf = std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>;
+template <class P>
+P params_of(const StepArgs &a, int n2) {
+  P p{};
+  p.in = static_cast<const T *>(a.in);
+  p.out = static_cast<T *>(a.out);
+  p.n0 = a.n0; p.n1 = a.n1; p.n2 = n2;
+  p.nv0 = a.n0;
+  p.p_begin = a.p_begin;
+  p.p_stride = a.p_stride;
+  p.wrap2 = a.wrap2;
+  p.N = (long long)a.n0 * a.n1 * n2;
+  p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
+  p.No = a.stride_out > 0 ? a.stride_out : p.N;
+  p.tau_inv = (T)(1.0 / a.tau);
+  const double beta = 1. / (2 * a.tau);          // kbc_collision.py:97-99
+  p.beta = (T)beta;
+  p.inv_beta = (T)(1. / beta);
+  p.tau = (T)a.tau;
+  p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
+  p.node = a.node;
+  p.nsm_bits = a.nsm_bits;
+  p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
+  p.nb = a.nb;
+  p.pack_lo = static_cast<T *>(a.pack_lo);
+  p.pack_hi = static_cast<T *>(a.pack_hi);
+  p.pack_lo_plane = a.pack_lo_plane;
+  p.pack_hi_plane = a.pack_hi_plane;
+  return p;
+}
+
 // uniform body force (lt_plan_set_force): the acceleration permuted from the logical order x, y, z to the memory axes
 // of the layout, as the kernels read the velocity
 template <int LAYOUT>
@@ -61,55 +122,49 @@ void set_force(KParamsF<T> &p, const StepArgs &a) {
   p.source_scale = (T)a.source_scale;
 }
 
-#if LT_PART < 2 || LT_PART == 4 || LT_PART == 5
+// Kernel names, as lt_plan_kernel_name reports them: the kernel's identifier and its template arguments behind the
+// scalar type and the lattice, "lbm2m_kernel<float, lt::D3Q19, 0, 1, 64, 8, 2>".  An argument wrapped in elided() is a
+// trailing one that the name leaves out while it has its default (0 / false).
+template <class V>
+struct Elided {
+  V v;
+};
+template <class V>
+Elided<V> elided(V v) { return {v}; }
+inline int name_arg(char *s, size_t n, int v) { return snprintf(s, n, ", %d", v); }
+inline int name_arg(char *s, size_t n, bool v) { return snprintf(s, n, v ? ", true" : ", false"); }
+template <class V>
+int name_arg(char *s, size_t n, Elided<V> e) { return e.v == V() ? 0 : name_arg(s, n, e.v); }
+
+// always 0: the launchers return it for "there is such a kernel".  A buffer too short holds the name's beginning
+template <class... A>
+int kernel_name(const NameBuf &out, const char *kernel, A... args) {
+  size_t len = (size_t)snprintf(out.s, out.cap, "%s<%s, lt::%s", kernel, sizeof(T) == 4 ? "float" : "double", S::NAME);
+  const auto put = [&](auto v) { if (len < out.cap) len += (size_t)name_arg(out.s + len, out.cap - len, v); };
+  (put(args), ...);
+  if (len < out.cap) snprintf(out.s + len, out.cap - len, ">");
+  return 0;
+}
+
+#if LT_ONE_STEP
 
 // one node per thread: the kernels' VEC = 1, SHIFT = 0
 template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
-int launch(const StepArgs &a, bool name_only, const char **name) {
+int launch(const StepArgs &a, const NameBuf *name) {
   constexpr bool STREAM = MODE != kCollideOnly, COLLIDE = MODE != kStreamOnly;
   constexpr bool OCC4 = (COLL == 2 && MASKED && sizeof(T) == 4 && S::Q == 27 && ABBD == 0);
-  using P = std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>;
+  using P = ParamsOf<COLL>;
+  if (name)
+    return kernel_name(*name, OCC4 ? "lbm_kernel_occ4" : "lbm_kernel", LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE,
+                       PACK, elided(ABBD));
   void (*kern)(const P);
   if constexpr (OCC4)
     kern = lbm_kernel_occ4<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK>;
   else
     kern = lbm_kernel<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK, ABBD>;
-  if (name_only) {
-    static char buf[160];
-    snprintf(buf, sizeof buf, "%s<%s, lt::%s, %d, %d, %s, %s, %s, 1, 0, %d, %s%s>",
-             OCC4 ? "lbm_kernel_occ4" : "lbm_kernel", sizeof(T) == 4 ? "float" : "double", S::NAME, LAYOUT, COLL,
-             STREAM ? "true" : "false", COLLIDE ? "true" : "false", MASKED ? "true" : "false",
-             TUNE, PACK ? "true" : "false", ABBD == 0 ? "" : (ABBD == 1 ? ", 1" : ", 2"));
-    *name = buf;
-    return 0;
-  }
-  P p;
-  p.in = static_cast<const T *>(a.in);
-  p.out = static_cast<T *>(a.out);
-  p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
-  p.nv0 = a.n0;
-  p.p_begin = a.p_begin;
-  p.p_stride = a.p_stride;
-  p.wrap2 = a.wrap2;
-  p.N = (long long)a.n0 * a.n1 * a.n2;
-  p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-  p.No = a.stride_out > 0 ? a.stride_out : p.N;
+  P p = params_of<P>(a, a.n2);
   p.nvec_total = (unsigned)((long long)p.nv0 * a.n1 * a.planes);
-  p.tau_inv = (T)(1.0 / a.tau);
-  const double beta = 1. / (2 * a.tau);          // kbc_collision.py:97-99
-  p.beta = (T)beta;
-  p.inv_beta = (T)(1. / beta);
-  p.tau = (T)a.tau;
-  p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
   if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
-  p.node = a.node;
-  p.nsm_bits = a.nsm_bits;
-  p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
-  p.nb = a.nb;
-  p.pack_lo = static_cast<T *>(a.pack_lo);
-  p.pack_hi = static_cast<T *>(a.pack_hi);
-  p.pack_lo_plane = a.pack_lo_plane;
-  p.pack_hi_plane = a.pack_hi_plane;
   p.abb0_slot = a.n0 % 64 == 0 ? a.abb0_slot : 0;
   if (p.nvec_total == 0) return 0;
   const unsigned grid = (p.nvec_total + kThreads - 1) / kThreads;
@@ -124,64 +179,37 @@ int launch(const StepArgs &a, bool name_only, const char **name) {
 // waves/SIMD by 8-13 %, and nontemporal stores (+3-4 %) and loads (+1.6 %) help once the
 // populations exceed the caches (TUNE 3).  TUNE 0 (cached accesses) is kept for grids that fit in
 // L2 / Infinity Cache.
-#define LT_TRY(LAYOUT, COLL, MODE, MASKED)                                                       \
-  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked == MASKED) {            \
-    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 0>(a, name_only, name); \
-    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 3>(a, name_only, name); \
+#define LT_TRY(LAYOUT, COLL, MODE, MASKED)                                    \
+  if (a.layout == LAYOUT && a.mode == MODE && a.masked == MASKED) {           \
+    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 0>(a, name); \
+    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 3>(a, name); \
   }
 
 // slab boundary-plane launch with fused halo packing (fused mode, slab layout)
-#define LT_TRY_PACK(COLL, MASKED)                                                               \
-  if (a.layout == 1 && coll == COLL && a.mode == kFused && a.masked == MASKED &&                 \
-      a.pack_lo != nullptr && a.abb_depth == 0)                                                                      \
-    return launch<1, COLL, kFused, (MASKED != 0), 0, true>(a, name_only, name);
+#define LT_TRY_PACK(COLL, MASKED)                                                                             \
+  if (a.layout == 1 && a.mode == kFused && a.masked == MASKED && a.pack_lo != nullptr && a.abb_depth == 0)    \
+    return launch<1, COLL, kFused, (MASKED != 0), 0, true>(a, name);
 
 // plans with two anti-bounce-back outlets (kernels.hpp, neighbour_moments DEPTH 1): masked kernels that
 // apply boundaries, i.e. fused and collide-only
-#define LT_TRY_TWO_OUTLETS(LAYOUT, COLL, MODE)                                                  \
-  if (a.layout == LAYOUT && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 1) \
-    return launch<LAYOUT, COLL, MODE, true, 0, false, 1>(a, name_only, name);
+#define LT_TRY_TWO_OUTLETS(LAYOUT, COLL, MODE)                                 \
+  if (a.layout == LAYOUT && a.mode == MODE && a.masked && a.abb_depth == 1)    \
+    return launch<LAYOUT, COLL, MODE, true, 0, false, 1>(a, name);
 
 // outlets on all three axes of a 3-D flow (their planes meet in corners: DEPTH 2), reference layout
-#define LT_TRY_THREE_AXES(COLL, MODE)                                                           \
-  if (a.layout == 0 && coll == COLL && a.mode == MODE && a.masked && a.abb_depth == 2) \
-    return launch<0, COLL, MODE, true, 0, false, 2>(a, name_only, name);
+#define LT_TRY_THREE_AXES(COLL, MODE)                                   \
+  if (a.layout == 0 && a.mode == MODE && a.masked && a.abb_depth == 2)  \
+    return launch<0, COLL, MODE, true, 0, false, 2>(a, name);
 
 #define LT_COLLISION_SET(LAYOUT, COLL, MASKED) \
   LT_TRY(LAYOUT, COLL, kFused, MASKED)         \
   LT_TRY(LAYOUT, COLL, kCollideOnly, MASKED)
 
-#if LT_PART != 1 && LT_PART != 5
-// The one-step kernels of the Smagorinsky collision (COLL 3): every variant BGK has.  The 3-D units build them in
-// an object of their own (LT_PART 4, inst4_<tag>.hip), beside the rest.
-int one_step_smagorinsky(const StepArgs &a, bool name_only, const char **name) {
-  const int coll = a.coll;
-  if (coll != 3 || (a.mode != kFused && a.mode != kCollideOnly)) return kNoKernel;
-#if LT_IS_3D
-  LT_TRY_THREE_AXES(3, kFused) LT_TRY_THREE_AXES(3, kCollideOnly)
-#endif
-  if (a.abb_depth > 1) return kNoKernel;
-  LT_TRY_TWO_OUTLETS(0, 3, kFused) LT_TRY_TWO_OUTLETS(0, 3, kCollideOnly)
-#if LT_IS_3D
-  LT_TRY_TWO_OUTLETS(1, 3, kFused) LT_TRY_TWO_OUTLETS(1, 3, kCollideOnly)
-#endif
-  LT_COLLISION_SET(0, 3, 0)
-  LT_COLLISION_SET(0, 3, 1)
-#if LT_IS_3D
-  LT_TRY_PACK(3, 0)
-  LT_TRY_PACK(3, 1)
-  LT_COLLISION_SET(1, 3, 0)
-  LT_COLLISION_SET(1, 3, 1)
-#endif
-  return kNoKernel;
-}
-#endif  // LT_PART != 1 && LT_PART != 5
-
-#if LT_PART == 5
-// The one-step kernels with a body force (COLL 5 = BGK, 7 = Smagorinsky): every variant BGK has
+// The one-step kernels of collision C, fused and collide-only: main has them for 0 (none), 1 (BGK) and, with
+// LT_HAS_KBC, 2; Smagorinsky (3) has every variant BGK has, and so have BGK and Smagorinsky with a body force (5, 7).
+// The order matters where the conditions overlap: the outlet depths before the rest, packed before the plain slab set.
 template <int C>
-int one_step_forced_of(const StepArgs &a, bool name_only, const char **name) {
-  const int coll = a.coll;
+int one_step_of(const StepArgs &a, const NameBuf *name) {
 #if LT_IS_3D
   LT_TRY_THREE_AXES(C, kFused) LT_TRY_THREE_AXES(C, kCollideOnly)
 #endif
@@ -190,9 +218,11 @@ int one_step_forced_of(const StepArgs &a, bool name_only, const char **name) {
 #if LT_IS_3D
   LT_TRY_TWO_OUTLETS(1, C, kFused) LT_TRY_TWO_OUTLETS(1, C, kCollideOnly)
 #endif
+  // reference layout
   LT_COLLISION_SET(0, C, 0)
   LT_COLLISION_SET(0, C, 1)
 #if LT_IS_3D
+  // slab layout (multi-GPU z-slabs)
   LT_TRY_PACK(C, 0)
   LT_TRY_PACK(C, 1)
   LT_COLLISION_SET(1, C, 0)
@@ -200,60 +230,38 @@ int one_step_forced_of(const StepArgs &a, bool name_only, const char **name) {
 #endif
   return kNoKernel;
 }
-#endif  // LT_PART == 5
 
-#endif  // LT_PART < 2 || LT_PART == 4 || LT_PART == 5
+#endif  // LT_ONE_STEP
 
-#if LT_PART == 2 || LT_PART == 3 || LT_PART == 0 || LT_PART == 5
+#if LT_SWEEP
 // Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
 // returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
 // one node per thread and per block: the kernel's NPT = NPB = 1
 // SCHED 1: separate producer and consumer waves (twostep_roles.hpp)
 // Smagorinsky (COLL 3) and BGK with a body force (COLL 5): the plain one-role sweep of D3Q19 fp32
 template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
-int launch_twice(const StepArgs &a, bool name_only, const char **name) {
+int launch_twice(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 3 && T0 > 0 &&
                 (COLL == 0 || COLL == 1 ||
                  ((COLL == 3 || COLL == 5) && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
     using B = TwoStep<T, S, T0, T1>;
-    if (name_only) {
-      static char buf[96];
-      snprintf(buf, sizeof buf, "lbm2_kernel<%s, lt::%s, %d, %d, %d, %d, 1, %d, 1%s>", sizeof(T) == 4 ? "float" : "double",
-               S::NAME, LAYOUT, COLL, T0, T1, MODE, SCHED ? ", 1" : "");
-      *name = buf;
-      return 0;
-    }
+    if (name) return kernel_name(*name, "lbm2_kernel", LAYOUT, COLL, T0, T1, 1, MODE, 1, elided(SCHED));
     // in-plane byte offsets are 32-bit in the kernel
     if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 1 || a.masked || a.planes < 1 || a.p_stride != 1 ||
         (long long)a.n0 * a.n1 * (long long)sizeof(T) >= (1ll << 32))
       return kNoKernel;
-    using P = std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>;
-    P p;
-    memset(&p, 0, sizeof p);
-    p.in = static_cast<const T *>(a.in);
-    p.out = static_cast<T *>(a.out);
-    p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
-    p.nv0 = a.n0;
-    p.wrap2 = a.wrap2;
-    p.p_begin = a.p_begin;
+    if (MODE == 2 && (!a.signal || a.planes2 < 2 || a.planes2 > a.seg_len || a.seg_len < 2)) return kNoKernel;
+    using P = ParamsOf<COLL>;
+    P p = params_of<P>(a, a.n2);
+    // the output planes: [p_begin, p_end) and, at a slab's other edge, [p_begin2, p_end2); a.seg_len of them per workgroup
     p.p_end = a.p_begin + a.planes;
     p.p_begin2 = a.p_begin2;
     p.p_end2 = a.p_begin2 + a.planes2;
-    p.N = (long long)a.n0 * a.n1 * a.n2;
-    p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-    p.No = a.stride_out > 0 ? a.stride_out : p.N;
-    p.tau_inv = (T)(1.0 / a.tau);
-    p.tau = (T)a.tau;
-    p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);
     if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
     p.nb = a.shift == 3 ? 1 : (a.shift == 4 ? 2 : 0);   // A/B: 1 = no XCD-aware renumbering of the workgroups, 2 = per segment layer
-    p.pack_lo = static_cast<T *>(a.pack_lo);
-    p.pack_hi = static_cast<T *>(a.pack_hi);
-    p.pack_lo_plane = a.pack_lo_plane;
-    p.pack_hi_plane = a.pack_hi_plane;
+    // MODE 2: the edge workgroups first, each adds 1 to *signal (kernels.hpp, KParams)
     p.signal = MODE == 2 ? a.signal : nullptr;
     p.edge_first = MODE == 2 ? 1 : 0;
-    if (MODE == 2 && (!a.signal || a.planes2 < 2 || a.planes2 > a.seg_len || a.seg_len < 2)) return kNoKernel;
     p.ghost_lo = static_cast<const T *>(a.ghost_lo);
     p.ghost_hi = static_cast<const T *>(a.ghost_hi);
     p.lo = a.interior_begin; p.hi = a.interior_end;
@@ -268,81 +276,65 @@ int launch_twice(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
-#if LT_PART == 3
-// the BGK sweeps of this unit with separate producer and consumer waves, where they won their A/B (DESIGN.md section 7)
-int twice_roles(const StepArgs &a, bool name_only, const char **name) {
-  constexpr int W = kTwiceW, R = kTwiceR;
-  if (a.layout == 0) return launch_twice<0, 1, W, R, 0, 1>(a, name_only, name);
-  return launch_twice<1, 1, W, R, 0, 1>(a, name_only, name);
-}
-#elif LT_PART == 5
-// the two-step launches with a body force: plain sweeps of periodic plans (no packing, no signalling launch)
-int twice_forced(const StepArgs &a, bool name_only, const char **name) {
+// the sweeps of this object
+int sweep(const StepArgs &a, const NameBuf *name) {
   constexpr int W = kTwiceW, R = kTwiceR;
   if constexpr (R > 0) {
+#if LT_PART_IS(roles)
+    // BGK with separate producer and consumer waves, where they won their A/B (DESIGN.md section 7)
+    if (a.layout == 0) return launch_twice<0, 1, W, R, 0, 1>(a, name);
+    return launch_twice<1, 1, W, R, 0, 1>(a, name);
+#elif LT_PART_IS(forced)
+    // with a body force: plain sweeps of periodic plans (no packing, no signalling launch)
     if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
-    if (a.layout == 0 && a.coll == 5) return launch_twice<0, 5, W, R>(a, name_only, name);
-    if (a.layout == 1 && a.coll == 5) return launch_twice<1, 5, W, R>(a, name_only, name);
+    if (a.layout == 0 && a.coll == 5) return launch_twice<0, 5, W, R>(a, name);
+    if (a.layout == 1 && a.coll == 5) return launch_twice<1, 5, W, R>(a, name);
     // (Smagorinsky with a force, COLL 7: 168 VGPRs and 84-92 bytes of scratch per lane under every scheduler setting
     // where the unforced sweep has 168 and none -- not built, the plan keeps the one-step kernel: DESIGN.md section 4)
-  }
-  return kNoKernel;
-}
 #else
-// the unmasked 3-D two-step launches of this unit
-int twice_unmasked(const StepArgs &a, bool name_only, const char **name) {
-  const int coll = a.coll;
-  constexpr int W = kTwiceW, R = kTwiceR;
-  if constexpr (R > 0) {
+    // the unmasked two-step launches of a 3-D unit
+    const int coll = a.coll;
 #if LT_HAS_ROLES
-    // the plain BGK sweep: inst3_<tag>.hip; shift policy 6 runs the one-role schedule (A/B)
+    // the plain BGK sweep: part roles; shift policy 6 runs the one-role schedule (A/B)
     if (coll == 1 && a.shift != 6 && (a.layout == 0 || !(a.pack_lo || a.pack_hi || a.signal)))
-      return LT_CAT(roles_, LT_TAG)(a, name_only, name);
+      return LT_CAT(roles_, LT_TAG)(a, name);
 #endif
-    if (a.layout == 0 && coll == 0) return launch_twice<0, 0, W, R>(a, name_only, name);
-    if (a.layout == 0 && coll == 1) return launch_twice<0, 1, W, R>(a, name_only, name);
-    if (a.layout == 0 && coll == 3) return launch_twice<0, 3, W, R>(a, name_only, name);
-#if LT_IS_3D
+    if (a.layout == 0 && coll == 0) return launch_twice<0, 0, W, R>(a, name);
+    if (a.layout == 0 && coll == 1) return launch_twice<0, 1, W, R>(a, name);
+    if (a.layout == 0 && coll == 3) return launch_twice<0, 3, W, R>(a, name);
     // Smagorinsky has the plain sweep only: no edge launch with packing, no signalling launch
     if (coll == 3 && (a.pack_lo || a.pack_hi || a.signal)) return kNoKernel;
     if (a.layout == 1 && (a.pack_lo || a.pack_hi)) {     // slab edge launch with fused halo packing
-      if (coll == 0) return launch_twice<1, 0, W, R, 1>(a, name_only, name);
-      if (coll == 1) return launch_twice<1, 1, W, R, 1>(a, name_only, name);
+      if (coll == 0) return launch_twice<1, 0, W, R, 1>(a, name);
+      if (coll == 1) return launch_twice<1, 1, W, R, 1>(a, name);
     }
     if (a.layout == 1 && a.signal) {                     // whole slab, edge workgroups first
-      if (coll == 0) return launch_twice<1, 0, W, R, 2>(a, name_only, name);
-      if (coll == 1) return launch_twice<1, 1, W, R, 2>(a, name_only, name);
+      if (coll == 0) return launch_twice<1, 0, W, R, 2>(a, name);
+      if (coll == 1) return launch_twice<1, 1, W, R, 2>(a, name);
     }
-    if (a.layout == 1 && coll == 0) return launch_twice<1, 0, W, R>(a, name_only, name);
-    if (a.layout == 1 && coll == 1) return launch_twice<1, 1, W, R>(a, name_only, name);
-    if (a.layout == 1 && coll == 3) return launch_twice<1, 3, W, R>(a, name_only, name);
+    if (a.layout == 1 && coll == 0) return launch_twice<1, 0, W, R>(a, name);
+    if (a.layout == 1 && coll == 1) return launch_twice<1, 1, W, R>(a, name);
+    if (a.layout == 1 && coll == 3) return launch_twice<1, 3, W, R>(a, name);
 #endif
   }
   return kNoKernel;
 }
-#endif  // LT_PART == 3, 5, else
-#endif  // LT_PART 0, 2, 3, 5
+#endif  // LT_SWEEP
 
-#if LT_PART < 2
+#if LT_PART_IS(main)
 // Two fused steps per launch for plans with boundaries (twostep_masked.hpp, lbm2m_kernel): whole periodic
 // grid, reference layout.  api.hip admits the plan (masked_two_step_ok); here: the grid tiles, the field is
 // below 4 GiB (32-bit buffer offsets; BGK in the reference layout: a population is, and fields beyond 4 GiB run
 // the instantiation with a descriptor per population) and three LDS slots of the downward populations fit.
 template <int LAYOUT, int COLL, int T0, int T1, int AX = 2>
-int launch_twice_masked(const StepArgs &a, bool name_only, const char **name) {
+int launch_twice_masked(const StepArgs &a, const NameBuf *name) {
   // BGK / streaming on tiles of 8 rows (4 for D3Q27 fp32).  KBC inside this kernel (256 VGPRs, spills: not faster
   // than one update per launch) and 4-row fp64 tiles of D3Q19 (slower than one update per launch) lost their A/B
   // (DESIGN.md section 4)
   if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1) && !(sizeof(T) == 8 && T1 == 4)) {
     if constexpr (two_step_masked_lds<T, S, LAYOUT, T0, T1>() <= 160 * 1024) {
       using B = TwoStep<T, S, T0, T1>;
-      if (name_only) {
-        static char buf[96];
-        snprintf(buf, sizeof buf, "lbm2m_kernel<%s, lt::%s, %d, %d, %d, %d, %d>", sizeof(T) == 4 ? "float" : "double",
-                 S::NAME, LAYOUT, COLL, T0, T1, AX);
-        *name = buf;
-        return 0;
-      }
+      if (name) return kernel_name(*name, "lbm2m_kernel", LAYOUT, COLL, T0, T1, AX);
       // (D3Q27: 26.7 GLUPS at 384^3 against 27.2 with one update per launch -- its 2 x 27 population bases spill;
       // D3Q19: 52-55 GLUPS at 384^3 / 512^3 against 38: profiles/r04y_large_obstacle.jsonl)
       constexpr bool kHasBig = LAYOUT == 0 && COLL == 1 && S::Q <= 19;
@@ -351,23 +343,8 @@ int launch_twice_masked(const StepArgs &a, bool name_only, const char **name) {
       if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 2 || !a.masked || a.planes < 2 || a.p_stride != 1 ||
           a.planes2 != 0 || a.pack_lo || a.pack_hi || (big && (!kHasBig || pop_bytes >= (1ll << 32))))
         return kNoKernel;
-      KParams<T> p;
-      memset(&p, 0, sizeof p);
-      p.in = static_cast<const T *>(a.in);
-      p.out = static_cast<T *>(a.out);
-      p.n0 = a.n0; p.n1 = a.n1; p.n2 = a.n2;
-      p.nv0 = a.n0;
-      p.wrap2 = a.wrap2;
-      p.p_begin = a.p_begin;
-      p.p_end = a.p_begin + a.planes;
-      p.N = (long long)a.n0 * a.n1 * a.n2;
-      p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-      p.No = a.stride_out > 0 ? a.stride_out : p.N;
-      p.tau_inv = (T)(1.0 / a.tau);
-      p.node = a.node;
-      p.nsm_bits = a.nsm_bits;
-      p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
-      p.nb = a.nb;
+      KParams<T> p = params_of<KParams<T>>(a, a.n2);
+      p.p_end = a.p_begin + a.planes;      // the output planes, a.seg_len of them per workgroup
       const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len));
       if constexpr (kHasBig) {
         if (big) {
@@ -387,63 +364,21 @@ int launch_twice_masked(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
-// Two fused steps per launch on 2-D lattices (twostep2d.hpp, lbm2d2_kernel): whole periodic grid, no masks;
-// a.seg_len rows per workgroup, strips of W columns (api.hip picks W and the segment length).
-template <int COLL, int W>
-int launch_twice2d(const StepArgs &a, bool name_only, const char **name) {
+// Two fused steps per launch on 2-D lattices (twostep2d.hpp): whole periodic grid, a.seg_len rows per workgroup,
+// strips of W columns (api.hip picks W and the segment length).  Without masks lbm2d2_kernel, with boundaries
+// lbm2d2m_kernel: api.hip admits the plan (masked_two_step_axis)
+template <int COLL, int W, bool MASKED>
+int launch_twice2d(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 2 && (COLL == 0 || COLL == 1)) {
-    if (name_only) {
-      static char buf[96];
-      snprintf(buf, sizeof buf, "lbm2d2_kernel<%s, lt::%s, %d, %d>", sizeof(T) == 4 ? "float" : "double", S::NAME, COLL, W);
-      *name = buf;
-      return 0;
-    }
-    if (a.layout != 0 || a.masked || a.n0 % W != 0 || a.seg_len < 1 || a.n1 < 1 || a.n2 != 1) return kNoKernel;
-    KParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.in = static_cast<const T *>(a.in);
-    p.out = static_cast<T *>(a.out);
-    p.n0 = a.n0; p.n1 = a.n1; p.n2 = 1;
-    p.N = (long long)a.n0 * a.n1;
-    p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-    p.No = a.stride_out > 0 ? a.stride_out : p.N;
-    p.tau_inv = (T)(1.0 / a.tau);
+    if (name) return kernel_name(*name, MASKED ? "lbm2d2m_kernel" : "lbm2d2_kernel", COLL, W);
+    if (a.layout != 0 || (a.masked != 0) != MASKED || a.n0 % W != 0 || a.seg_len < (MASKED ? 2 : 1) ||
+        a.n1 < (MASKED ? 3 : 1) || a.n2 != 1)
+      return kNoKernel;
+    const KParams<T> p = params_of<KParams<T>>(a, 1);      // n2 = 1: the field is one plane
     const unsigned grid = (unsigned)((a.n0 / W) * ((a.n1 + a.seg_len - 1) / a.seg_len));
-    hipLaunchKernelGGL((lbm2d2_kernel<T, S, COLL, W>), dim3(grid), dim3(TwoStep2D<T, W>::THREADS), 0, a.stream, p,
-                       a.seg_len);
-    return (int)hipGetLastError();
-  } else {
-    return kNoKernel;
-  }
-}
-
-// ... and with boundaries (lbm2d2m_kernel): api.hip admits the plan (masked_two_step_axis)
-template <int COLL, int W>
-int launch_twice2d_masked(const StepArgs &a, bool name_only, const char **name) {
-  if constexpr (S::D == 2 && (COLL == 0 || COLL == 1)) {
-    if (name_only) {
-      static char buf[96];
-      snprintf(buf, sizeof buf, "lbm2d2m_kernel<%s, lt::%s, %d, %d>", sizeof(T) == 4 ? "float" : "double", S::NAME, COLL, W);
-      *name = buf;
-      return 0;
-    }
-    if (a.layout != 0 || !a.masked || a.n0 % W != 0 || a.seg_len < 2 || a.n1 < 3 || a.n2 != 1) return kNoKernel;
-    KParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.in = static_cast<const T *>(a.in);
-    p.out = static_cast<T *>(a.out);
-    p.n0 = a.n0; p.n1 = a.n1; p.n2 = 1;
-    p.N = (long long)a.n0 * a.n1;
-    p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-    p.No = a.stride_out > 0 ? a.stride_out : p.N;
-    p.tau_inv = (T)(1.0 / a.tau);
-    p.node = a.node;
-    p.nsm_bits = a.nsm_bits;
-    p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
-    p.nb = a.nb;
-    const unsigned grid = (unsigned)((a.n0 / W) * ((a.n1 + a.seg_len - 1) / a.seg_len));
-    hipLaunchKernelGGL((lbm2d2m_kernel<T, S, COLL, W>), dim3(grid), dim3(TwoStep2D<T, W>::THREADS), 0, a.stream, p,
-                       a.seg_len);
+    void (*kern)(const KParams<T>, const int);
+    if constexpr (MASKED) kern = lbm2d2m_kernel<T, S, COLL, W>; else kern = lbm2d2_kernel<T, S, COLL, W>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(TwoStep2D<T, W>::THREADS), 0, a.stream, p, a.seg_len);
     return (int)hipGetLastError();
   } else {
     return kNoKernel;
@@ -453,40 +388,18 @@ int launch_twice2d_masked(const StepArgs &a, bool name_only, const char **name) 
 // Up to kManyMax steps per launch on small 2-D grids (kernels.hpp, lbm_many_kernel)
 constexpr int kManyTile = 8, kManyMax = 8;
 template <int COLL, bool MASKED>
-int launch_many(const StepArgs &a, bool name_only, const char **name) {
+int launch_many(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 2 && (COLL != 2 || LT_HAS_KBC)) {
     using G = ManyStep2D<kManyTile, kManyTile, kManyMax>;
-    if (name_only) {
-      static char buf[96];
-      snprintf(buf, sizeof buf, "lbm_many_kernel<%s, lt::%s, %d, %d, %d, %d%s>", sizeof(T) == 4 ? "float" : "double",
-               S::NAME, COLL, kManyTile, kManyTile, kManyMax, MASKED ? ", true" : "");
-      *name = buf;
-      return 0;
-    }
+    if (name) return kernel_name(*name, "lbm_many_kernel", COLL, kManyTile, kManyTile, kManyMax, elided(MASKED));
     // plans with an outlet recompute one more ring: one step fewer per launch
     const int outlets = MASKED ? a.n_abb : 0;
     if (a.layout != 0 || (a.masked != 0) != MASKED || a.n0 % kManyTile != 0 || a.n1 % kManyTile != 0 || a.seg_len < 1 ||
         a.seg_len > kManyMax - (outlets ? 1 : 0) || a.planes != a.n2 || outlets > 1)
       return kNoKernel;
-    KParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.in = static_cast<const T *>(a.in);
-    p.out = static_cast<T *>(a.out);
-    p.n0 = a.n0; p.n1 = a.n1; p.n2 = 1;
-    p.nv0 = a.n0;
-    p.wrap2 = 1;
-    p.N = (long long)a.n0 * a.n1;
-    p.Ni = a.stride_in > 0 ? a.stride_in : p.N;
-    p.No = a.stride_out > 0 ? a.stride_out : p.N;
-    p.tau_inv = (T)(1.0 / a.tau);
-    const double beta = 1. / (2 * a.tau);
-    p.beta = (T)beta;
-    p.inv_beta = (T)(1. / beta);
-    p.node = a.node;
-    p.nsm_bits = a.nsm_bits;
-    p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
-    p.nb = a.nb;
-    p.abb0_slot = outlets;                       // here: 1 = the plan has an outlet (one more ring)
+    KParams<T> p = params_of<KParams<T>>(a, 1);      // n2 = 1: the field is one plane ...
+    p.wrap2 = 1;                                     // ... which is its own neighbour along a2
+    p.abb0_slot = outlets;                           // here: 1 = the plan has an outlet (one more ring)
     const unsigned grid = (unsigned)((a.n0 / kManyTile) * (a.n1 / kManyTile));
     hipLaunchKernelGGL((lbm_many_kernel<T, S, COLL, kManyTile, kManyTile, kManyMax, MASKED>), dim3(grid),
                        dim3(G::THREADS), 0, a.stream, p, a.seg_len);
@@ -496,122 +409,81 @@ int launch_many(const StepArgs &a, bool name_only, const char **name) {
   }
 }
 
-int dispatch(const StepArgs &a, bool name_only, const char **name) {
-  const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
-  if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name_only, name);   // body force: inst5_<tag>.hip
-  if (a.mode == kFusedMany) {
-    if (a.masked) {
-      if (coll == 0) return launch_many<0, true>(a, name_only, name);
-      if (coll == 1) return launch_many<1, true>(a, name_only, name);
-      if (coll == 2) return launch_many<2, true>(a, name_only, name);
-      return kNoKernel;
-    }
-    if (coll == 0) return launch_many<0, false>(a, name_only, name);
-    if (coll == 1) return launch_many<1, false>(a, name_only, name);
-    if (coll == 2) return launch_many<2, false>(a, name_only, name);
-    return kNoKernel;
+template <int C>
+int many_of(const StepArgs &a, const NameBuf *name) {
+  return a.masked ? launch_many<C, true>(a, name) : launch_many<C, false>(a, name);
+}
+
+// strips of a.strip columns (api.hip: the widest of 512 / 256 / 128 / 64 that divides the contiguous extent)
+template <int C>
+int strips_of(const StepArgs &a, const NameBuf *name) {
+#define LT_TRY_STRIP(W) \
+  if (a.strip == W) return a.masked ? launch_twice2d<C, W, true>(a, name) : launch_twice2d<C, W, false>(a, name);
+  LT_TRY_STRIP(512) LT_TRY_STRIP(256) LT_TRY_STRIP(128) LT_TRY_STRIP(64)
+#undef LT_TRY_STRIP
+  return kNoKernel;
+}
+
+#if LT_IS_3D
+// two steps per launch of a 3-D unit: with boundaries here, without in the unit's part sweeps
+int twice_3d(const StepArgs &a, const NameBuf *name) {
+  constexpr int W = kTwiceW, R = kTwiceR;
+  if constexpr (R > 0) {
+    if (!a.masked) return LT_CAT(twice_, LT_TAG)(a, name);
+    // a.abb_axis: memory axis of the plan's outlet (2 also for plans without one)
+    // rows of the tile with boundaries: the third slot of the downward populations must fit too (D3Q19 fp64:
+    // 8 rows are 168.6 KB -> 4 rows; the rule of api.hip's two_step_tile_of)
+    constexpr int RM = (R == 8 && two_step_masked_lds<T, S, 0, W, 8>() > 160 * 1024) ? 4 : R;
+#define LT_TRY_MASKED_TWICE(LAYOUT_, COLL_, AX_)                       \
+  if (a.layout == LAYOUT_ && a.coll == COLL_ && a.abb_axis == AX_)     \
+    return launch_twice_masked<LAYOUT_, COLL_, W, RM, AX_>(a, name);
+    LT_TRY_MASKED_TWICE(0, 0, 2) LT_TRY_MASKED_TWICE(0, 1, 2)
+    LT_TRY_MASKED_TWICE(0, 0, 0) LT_TRY_MASKED_TWICE(0, 1, 0)
+    LT_TRY_MASKED_TWICE(1, 0, 2) LT_TRY_MASKED_TWICE(1, 1, 2)
+    LT_TRY_MASKED_TWICE(1, 0, 0) LT_TRY_MASKED_TWICE(1, 1, 0)
+#undef LT_TRY_MASKED_TWICE
   }
-  if (a.mode == kFusedTwice && S::D == 2) {
-    // strips of a.wide2d columns (api.hip: the widest of 512 / 256 / 128 / 64 that divides the contiguous extent)
-    if (a.layout != 0) return kNoKernel;
-    if (a.masked) {
-#define LT_TRY_2DM(COLL, W) if (coll == COLL && a.strip == W) return launch_twice2d_masked<COLL, W>(a, name_only, name);
-      LT_TRY_2DM(0, 512) LT_TRY_2DM(0, 256) LT_TRY_2DM(0, 128) LT_TRY_2DM(0, 64)
-      LT_TRY_2DM(1, 512) LT_TRY_2DM(1, 256) LT_TRY_2DM(1, 128) LT_TRY_2DM(1, 64)
-#undef LT_TRY_2DM
-      return kNoKernel;
-    }
-#define LT_TRY_2D(COLL, W) if (coll == COLL && a.strip == W) return launch_twice2d<COLL, W>(a, name_only, name);
-    LT_TRY_2D(0, 512) LT_TRY_2D(0, 256) LT_TRY_2D(0, 128) LT_TRY_2D(0, 64)
-    LT_TRY_2D(1, 512) LT_TRY_2D(1, 256) LT_TRY_2D(1, 128) LT_TRY_2D(1, 64)
+  return kNoKernel;
+}
+#endif
+
+int dispatch(const StepArgs &a, const NameBuf *name) {
+  const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
+  if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
+  if (a.mode == kFusedMany) {
+    if (coll == 0) return many_of<0>(a, name);
+    if (coll == 1) return many_of<1>(a, name);
+    if (coll == 2) return many_of<2>(a, name);
     return kNoKernel;
   }
   if (a.mode == kFusedTwice) {
-    constexpr int W = kTwiceW, R = kTwiceR;
-    if constexpr (R > 0) {
-      if (a.masked) {
-        // a.abb_axis: memory axis of the plan's outlet (2 also for plans without one)
-        // rows of the tile with boundaries: the third slot of the downward populations must fit too (D3Q19 fp64:
-        // 8 rows are 168.6 KB -> 4 rows; the rule of api.hip's two_step_tile_of)
-        constexpr int RM = (R == 8 && two_step_masked_lds<T, S, 0, W, 8>() > 160 * 1024) ? 4 : R;
-#define LT_TRY_MASKED_TWICE(LAYOUT_, COLL_, AX_)                                     \
-  if (a.layout == LAYOUT_ && coll == COLL_ && a.abb_axis == AX_)                     \
-    return launch_twice_masked<LAYOUT_, COLL_, W, RM, AX_>(a, name_only, name);
-        LT_TRY_MASKED_TWICE(0, 0, 2) LT_TRY_MASKED_TWICE(0, 1, 2)
-        LT_TRY_MASKED_TWICE(0, 0, 0) LT_TRY_MASKED_TWICE(0, 1, 0)
 #if LT_IS_3D
-        LT_TRY_MASKED_TWICE(1, 0, 2) LT_TRY_MASKED_TWICE(1, 1, 2)
-        LT_TRY_MASKED_TWICE(1, 0, 0) LT_TRY_MASKED_TWICE(1, 1, 0)
-#endif
-#undef LT_TRY_MASKED_TWICE
-        return kNoKernel;
-      }
-#if LT_PART == 1
-      return LT_CAT(twice_, LT_TAG)(a, name_only, name);      // inst2_<tag>.hip
+    return twice_3d(a, name);
 #else
-      return twice_unmasked(a, name_only, name);
+    if (S::D != 2 || a.layout != 0) return kNoKernel;
+    if (coll == 0) return strips_of<0>(a, name);
+    if (coll == 1) return strips_of<1>(a, name);
+    return kNoKernel;
 #endif
-    }
+  }
+  if (a.mode == kStreamOnly) {      // the one kernel that does not collide: no check of the outlet depth
+    LT_TRY(0, 0, kStreamOnly, 0)
+    LT_TRY(0, 0, kStreamOnly, 1)
+#if LT_IS_3D
+    LT_TRY(1, 0, kStreamOnly, 0)
+    LT_TRY(1, 0, kStreamOnly, 1)
+#endif
     return kNoKernel;
   }
-  if (coll == 3) {
-#if LT_PART == 1
-    return LT_CAT(smag_, LT_TAG)(a, name_only, name);       // inst4_<tag>.hip
+  if (coll == 0) return one_step_of<0>(a, name);
+  if (coll == 1) return one_step_of<1>(a, name);
+#if LT_HAS_KBC
+  if (coll == 2) return one_step_of<2>(a, name);
+#endif
+#if LT_IS_3D
+  if (coll == 3) return LT_CAT(smag_, LT_TAG)(a, name);       // part smagorinsky
 #else
-    return one_step_smagorinsky(a, name_only, name);
-#endif
-  }
-#if LT_IS_3D
-  LT_TRY_THREE_AXES(0, kFused) LT_TRY_THREE_AXES(0, kCollideOnly)
-  LT_TRY_THREE_AXES(1, kFused) LT_TRY_THREE_AXES(1, kCollideOnly)
-#if LT_HAS_KBC
-  LT_TRY_THREE_AXES(2, kFused) LT_TRY_THREE_AXES(2, kCollideOnly)
-#endif
-#endif
-  if (a.abb_depth > 1 && a.mode != kStreamOnly) return kNoKernel;
-  LT_TRY_TWO_OUTLETS(0, 0, kFused) LT_TRY_TWO_OUTLETS(0, 0, kCollideOnly)
-  LT_TRY_TWO_OUTLETS(0, 1, kFused) LT_TRY_TWO_OUTLETS(0, 1, kCollideOnly)
-#if LT_HAS_KBC
-  LT_TRY_TWO_OUTLETS(0, 2, kFused) LT_TRY_TWO_OUTLETS(0, 2, kCollideOnly)
-#endif
-#if LT_IS_3D
-  LT_TRY_TWO_OUTLETS(1, 0, kFused) LT_TRY_TWO_OUTLETS(1, 0, kCollideOnly)
-  LT_TRY_TWO_OUTLETS(1, 1, kFused) LT_TRY_TWO_OUTLETS(1, 1, kCollideOnly)
-#if LT_HAS_KBC
-  LT_TRY_TWO_OUTLETS(1, 2, kFused) LT_TRY_TWO_OUTLETS(1, 2, kCollideOnly)
-#endif
-#endif
-  // reference layout
-  LT_COLLISION_SET(0, 0, 0)
-  LT_COLLISION_SET(0, 0, 1)
-  LT_COLLISION_SET(0, 1, 0)
-  LT_COLLISION_SET(0, 1, 1)
-#if LT_HAS_KBC
-  LT_COLLISION_SET(0, 2, 0)
-  LT_COLLISION_SET(0, 2, 1)
-#endif
-  LT_TRY(0, 0, kStreamOnly, 0)
-  LT_TRY(0, 0, kStreamOnly, 1)
-#if LT_IS_3D
-  // slab layout (multi-GPU z-slabs)
-  LT_TRY_PACK(0, 0)
-  LT_TRY_PACK(0, 1)
-  LT_TRY_PACK(1, 0)
-  LT_TRY_PACK(1, 1)
-#if LT_HAS_KBC
-  LT_TRY_PACK(2, 0)
-  LT_TRY_PACK(2, 1)
-#endif
-  LT_COLLISION_SET(1, 0, 0)
-  LT_COLLISION_SET(1, 0, 1)
-  LT_COLLISION_SET(1, 1, 0)
-  LT_COLLISION_SET(1, 1, 1)
-#if LT_HAS_KBC
-  LT_COLLISION_SET(1, 2, 0)
-  LT_COLLISION_SET(1, 2, 1)
-#endif
-  LT_TRY(1, 0, kStreamOnly, 0)
-  LT_TRY(1, 0, kStreamOnly, 1)
+  if (coll == 3) return one_step_of<3>(a, name);
 #endif
   return kNoKernel;
 }
@@ -706,36 +578,16 @@ int aux_impl(const AuxArgs &a) {
   return (int)hipGetLastError();
 }
 
-#endif  // LT_PART < 2
+#endif  // LT_PART_IS(main)
 
 }  // namespace
 
-#if LT_PART == 2
-int LT_CAT(twice_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
-  return twice_unmasked(a, name_only, name);
-}
-#elif LT_PART == 3
-int LT_CAT(roles_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
-  return twice_roles(a, name_only, name);
-}
-#elif LT_PART == 5
-int LT_CAT(forced_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
-  if (a.mode == kFusedTwice) return S::D == 3 ? twice_forced(a, name_only, name) : kNoKernel;
-  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == 5) return one_step_forced_of<5>(a, name_only, name);
-  if (a.coll == 7) return one_step_forced_of<7>(a, name_only, name);
-  return kNoKernel;
-}
-#elif LT_PART == 4
-int LT_CAT(smag_, LT_TAG)(const StepArgs &a, bool name_only, const char **name) {
-  return one_step_smagorinsky(a, name_only, name);
-}
-#else
-int LT_CAT(step_, LT_TAG)(const StepArgs &a) { return dispatch(a, false, nullptr); }
+// what the object exports (dispatch.hpp, LT_DECLARE_UNIT)
+#if LT_PART_IS(main)
+int LT_CAT(step_, LT_TAG)(const StepArgs &a) { return dispatch(a, nullptr); }
 
-const char *LT_CAT(name_, LT_TAG)(const StepArgs &a) {
-  const char *n = nullptr;
-  return dispatch(a, true, &n) == 0 ? n : nullptr;
+const char *LT_CAT(name_, LT_TAG)(const StepArgs &a, const NameBuf &name) {
+  return dispatch(a, &name) == 0 ? name.s : nullptr;
 }
 
 int LT_CAT(aux_, LT_TAG)(const AuxArgs &a) {
@@ -744,6 +596,19 @@ int LT_CAT(aux_, LT_TAG)(const AuxArgs &a) {
 #endif
   return aux_impl<0>(a);
 }
-#endif  // LT_PART
+#elif LT_PART_IS(sweeps)
+int LT_CAT(twice_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep(a, name); }
+#elif LT_PART_IS(roles)
+int LT_CAT(roles_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep(a, name); }
+#elif LT_PART_IS(smagorinsky)
+int LT_CAT(smag_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_of<3>(a, name); }
+#elif LT_PART_IS(forced)
+int LT_CAT(forced_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
+  if (a.coll == 5) return one_step_of<5>(a, name);
+  if (a.coll == 7) return one_step_of<7>(a, name);
+  return kNoKernel;
+}
+#endif
 
 }  // namespace lt

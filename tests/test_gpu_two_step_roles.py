@@ -11,7 +11,7 @@ from conftest import TORCH_DT
 
 pytestmark = pytest.mark.gpu
 
-# the dtypes whose D3Q19 BGK sweep is instantiated with separate roles (csrc/unit.inc, kRoleWaves)
+# the dtypes whose D3Q19 BGK sweep is instantiated with separate roles (csrc/dispatch.hpp, the last column of the units)
 ROLE_DTYPES = ["f32"]
 TAU = 0.6
 
