@@ -386,7 +386,156 @@ def shear3d_case(dt):
 
 
 # --------------------------------------------------------------------------- #
+# bgk_bits: periodic BGK on states WITHOUT symmetries (the Taylor-Green and shear-layer vectors above are smooth and
+# symmetric: rho within 1e-3 of 1, opposite populations nearly equal, so a summation order exchanged between a
+# population and its opposite cancels, and dividends near 0 / negative populations never occur).  The reference's CPU
+# path gives the same bits for these with 1 and with 8 threads (asserted here), so they are a target a kernel can be
+# held to with assert_array_equal.
+BITS_LATTICES = ("D1Q3", "D2Q9", "D3Q15", "D3Q19", "D3Q27")
+BITS_TAUS = {"moderate": (0.501, 0.7, 1.7), "wide": (0.7, 1.7)}     # wide at tau = 0.501 blows up within 5 steps
+BITS_GRID = {1: [37], 2: [7, 5], 3: [6, 5, 7]}
+# the smallest grids the multi-step launchers take: one 64 x 8 tile in fp32, two 32-wide tiles in fp64, each its own
+# neighbour; lattice -> the dtypes that have such a kernel
+TILE_GRID = {2: [5, 64], 3: [2, 8, 64]}
+TILE_DTYPES = {"D1Q3": (), "D2Q9": ("f32", "f64"), "D3Q15": ("f32", "f64"), "D3Q19": ("f32", "f64"), "D3Q27": ("f32",)}
+TILE_TAU = 0.501
+MANY_GRID = [8, 64]
+BB_LATTICES = ("D2Q9", "D3Q19")
+BB_TAU = 0.7
+
+
+def asymmetric_state(stencil, res, kind, seed):
+    """float64 populations: equilibria of a random density (moderate: 1 + (rand - 0.5); wide: 20^(2 rand - 1)) and
+    a random velocity (0.1 (rand - 0.5) per component), times 1 +- 5 % per population"""
+    g = torch.Generator().manual_seed(seed)
+    r = torch.rand(res, generator=g, dtype=torch.float64)
+    rho = 1 + (r - 0.5) if kind == "moderate" else 20.0 ** (2 * r - 1)
+    u = 0.1 * (torch.rand([stencil.d] + list(res), generator=g, dtype=torch.float64) - 0.5)
+    noise = 1 + 0.05 * (2 * torch.rand([stencil.q] + list(res), generator=g, dtype=torch.float64) - 1)
+    e = torch.tensor(np.asarray(stencil.e), dtype=torch.float64)
+    w = torch.tensor(np.asarray(stencil.w), dtype=torch.float64).reshape([-1] + [1] * stencil.d)
+    eu = torch.tensordot(e, u, dims=1)
+    uu = (u * u).sum(0)
+    return w * rho * (1 + 3 * eu + 4.5 * eu * eu - 1.5 * uu) * noise
+
+
+def bits_run(stencil, res, dt, f0, tau, snapshots, block=None):
+    """the reference's Simulation on a TaylorGreenVortex carrier (one dimension: DecayingTurbulence, the one flow of
+    the reference that takes a 1-D stencil) whose populations are overwritten with f0 (already in the run's dtype);
+    block: a bounce-back solid.  Returns ({n: f after n steps}, sim); run with 1 and with 8
+    threads, which must agree bit for bit."""
+    ctx = lt.Context(device="cpu", dtype=DT[dt], use_native=False)
+
+    class Carrier(lt.TaylorGreenVortex):
+        @property
+        def boundaries(self):
+            return [] if block is None else [lt.BounceBackBoundary(block)]
+    runs = []
+    for threads in (1, 8):
+        torch.set_num_threads(threads)
+        if stencil.d == 1:
+            flow = quiet(lt.DecayingTurbulence, ctx, list(res), 100, 0.05, stencil=stencil, initialize_pressure=False,
+                         initialize_fneq=False, randseed=1)
+        else:
+            flow = quiet(Carrier, ctx, list(res), 100, 0.05, stencil)
+        assert flow.f.shape == f0.shape and flow.f.dtype == f0.dtype
+        flow.f = f0.clone()
+        sim = quiet(lt.Simulation, flow, lt.BGKCollision(tau), [])
+        out = {}
+        for i in range(1, max(snapshots) + 1):
+            quiet(sim, 1)
+            if i in snapshots:
+                out[i] = npy(flow.f)
+        runs.append(out)
+    for n in snapshots:
+        assert np.isfinite(runs[0][n]).all(), (dt, tau, n)
+        assert runs[0][n].tobytes() == runs[1][n].tobytes(), f"1 and 8 threads differ: {dt} tau {tau} step {n}"
+    return runs[0], sim
+
+
+def sum_block(dt):
+    """torch.sum(f, dim=0) sums in cascade order only whole blocks of four SIMD vectors of the flattened node index;
+    the nodes after the last block are summed in four interleaved partial sums (tests/bgk_arithmetic.py).  The
+    block in nodes for ATen's 32-byte vectors (the sum kernel is built for AVX2, also where the CPU has AVX-512);
+    bits_check asserts that it is the right one on the machine that generates."""
+    return 4 * 32 // (8 if dt == "f64" else 4)
+
+
+def bits_check(sname, dt, f0, tau, snaps, solid=None):
+    """the reference's bits are those of the kernels' arithmetic restated in numpy, with rho of the tail nodes in
+    row_sum order: what the GPU tests rely on where a grid is no multiple of the block"""
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    for path in (root, os.path.join(root, "tests")):
+        if path not in sys.path:
+            sys.path.insert(0, path)
+    import bgk_arithmetic
+    for n, want in snaps.items():
+        got = bgk_arithmetic.steps(npy(f0), sname, tau, n, sum_block(dt), None if solid is None else npy(solid))
+        assert got.tobytes() == want.tobytes(), f"{sname} {dt} tau {tau} step {n}: not the restated arithmetic's bits"
+
+
+def bits_key(kind, tau, n):
+    return f"{kind}_tau{tau}_f{n}"
+
+
+def bgk_bits_cases():
+    for li, sname in enumerate(BITS_LATTICES):
+        stencil = getattr(lt, sname)()
+        for dt in ("f64", "f32"):
+            name = f"bgk_bits_{sname.lower()}_{dt}"
+            if wanted(name):
+                res = BITS_GRID[stencil.d]
+                out = {"resolution": np.array(res), "sum_block": np.array(sum_block(dt))}
+                for ki, (kind, taus) in enumerate(BITS_TAUS.items()):
+                    f0 = asymmetric_state(stencil, res, kind, 9100 + 10 * li + ki).to(DT[dt])
+                    assert torch.isfinite(f0).all()
+                    out[f"f0_{kind}"] = npy(f0)
+                    out[f"taus_{kind}"] = np.array(taus, dtype=np.float64)
+                    for tau in taus:
+                        snaps, _ = bits_run(stencil, res, dt, f0, tau, (1, 5))
+                        bits_check(sname, dt, f0, tau, snaps)
+                        for n, f in snaps.items():
+                            out[bits_key(kind, tau, n)] = f
+                save(name, **out)
+            name = f"bgk_bits_tiles_{sname.lower()}_{dt}"
+            if wanted(name) and dt in TILE_DTYPES[sname]:
+                res = TILE_GRID[stencil.d]
+                f0 = asymmetric_state(stencil, res, "moderate", 9200 + li).to(DT[dt])
+                snaps, _ = bits_run(stencil, res, dt, f0, TILE_TAU, (4, 5))
+                assert int(np.prod(res)) % 64 == 0          # whole blocks for every vector width
+                bits_check(sname, dt, f0, TILE_TAU, snaps)
+                save(name, resolution=np.array(res), tau=np.float64(TILE_TAU), f0=npy(f0), f4=snaps[4], f5=snaps[5])
+            # the many-step kernel (D2Q9) wants both extents % 8, which [5, 64] is not: the smallest grid it shares
+            # with the two-step kernel; f10 = 9 fused steps = one launch of 8 and one of 1
+            name = f"bgk_bits_many_{sname.lower()}_{dt}"
+            if wanted(name) and sname == "D2Q9":
+                res = MANY_GRID
+                f0 = asymmetric_state(stencil, res, "moderate", 9250 + li).to(DT[dt])
+                snaps, _ = bits_run(stencil, res, dt, f0, TILE_TAU, (4, 5, 10))
+                assert int(np.prod(res)) % 64 == 0
+                bits_check(sname, dt, f0, TILE_TAU, snaps)
+                save(name, resolution=np.array(res), tau=np.float64(TILE_TAU), f0=npy(f0),
+                     **{f"f{n}": f for n, f in snaps.items()})
+            name = f"bgk_bits_bb_{sname.lower()}_{dt}"
+            if wanted(name) and sname in BB_LATTICES:
+                res = BITS_GRID[stencil.d]
+                block = torch.zeros(res, dtype=torch.bool)
+                block[tuple(slice(n // 2 - 1, n // 2 + 1) for n in res)] = True
+                f0 = asymmetric_state(stencil, res, "moderate", 9300 + li).to(DT[dt])
+                snaps, sim = bits_run(stencil, res, dt, f0, BB_TAU, (1, 5), block=block)
+                assert [type(b).__name__ for b in sim.boundaries[1:]] == ["BounceBackBoundary"]
+                bits_check(sname, dt, f0, BB_TAU, snaps, solid=block)
+                save(name, resolution=np.array(res), sum_block=np.array(sum_block(dt)), tau=np.float64(BB_TAU), f0=npy(f0), f1=snaps[1], f5=snaps[5],
+                     block_mask=npy(block), no_collision_mask=npy(sim.no_collision_mask),
+                     no_streaming_mask=np.packbits(npy(sim.no_streaming_mask).astype(bool), axis=None),
+                     no_streaming_mask_shape=np.array(sim.no_streaming_mask.shape))
+    torch.set_num_threads(8)
+
+
+# --------------------------------------------------------------------------- #
 if __name__ == "__main__":
+    if not ONLY or any("bgk_bits" in k or k in "bgk_bits" for k in ONLY):
+        bgk_bits_cases()
     # cfg1 (examples/00_simplest_TGV.py): 128^2 fp64; keep only energies + a 100-step f
     tgv_case("tgv2d_d2q9_bgk_128_f64", 128, lt.D2Q9(), 100, 0.05, "f64", "bgk", {100}, 100)
     tgv_case("tgv2d_d2q9_bgk_32_f64", 32, lt.D2Q9(), 100, 0.05, "f64", "bgk", {10, 100}, 10)

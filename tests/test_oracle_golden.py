@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import bgk_arithmetic
 from conftest import golden, unpack_nsm, TORCH_DT
 from oracle import lettuce_oracle as orc
 
@@ -252,3 +253,119 @@ def test_two_anti_bounce_back_outlets(name, lat, dt):
         sim.step()
         if i in (1, 2, 6):
             close(sim.f.numpy(), g[f"f{i}"], dt, scale=2)
+
+
+# --------------------------------------------------------------------------- states without symmetries (bgk_bits_*)
+BITS_TAUS = {"moderate": (0.501, 0.7, 1.7), "wide": (0.7, 1.7)}
+BITS = [(lat, dt) for lat in ("D1Q3", "D2Q9", "D3Q15", "D3Q19", "D3Q27") for dt in ("f64", "f32")]
+BITS_TILES = [(lat, dt) for lat, dt in BITS if lat != "D1Q3" and (lat, dt) != ("D3Q27", "f64")]
+BITS_BB = [(lat, dt) for lat in ("D2Q9", "D3Q19") for dt in ("f64", "f32")]
+
+
+def bits_key(kind, tau, n):
+    return f"{kind}_tau{tau}_f{n}"
+
+
+def close_scaled(a, b, dt):
+    """the file's tolerance per unit of the largest population (the wide states reach |f| ~ 10: the tolerance is one
+    of rounding, which scales with the magnitude)"""
+    close(a, b, dt, scale=max(1.0, float(np.abs(b).max())))
+
+
+@pytest.mark.parametrize("lat,dt", BITS, ids=[f"{l.lower()}-{d}" for l, d in BITS])
+def test_bgk_on_states_without_symmetries(lat, dt):
+    """The oracle in the fixture's dtype against the reference's CPU path on random densities (moderate: 0.5 .. 1.5,
+    wide: 1/20 .. 20), random velocities and +-5 % per population, tau down to 0.501 (negative populations).  At the
+    tolerance of this file, not bitwise: the oracle's einsum order follows the CPU's BLAS, which differs between
+    machines; the HIP kernels are held to these vectors bit for bit (test_gpu_bgk_bits_vs_reference.py)."""
+    g = golden(f"bgk_bits_{lat.lower()}_{dt}")
+    assert list(g["f0_moderate"].shape[1:]) == [int(r) for r in g["resolution"]]
+    for kind, taus in BITS_TAUS.items():
+        assert g[f"taus_{kind}"].tolist() == list(taus)
+        f0 = g[f"f0_{kind}"]
+        assert f0.dtype == np.dtype(np.float64 if dt == "f64" else np.float32)
+        for tau in taus:
+            sim = orc.OracleSimulation(orc.LATTICES[lat], torch.tensor(f0), "bgk", tau)
+            close_scaled(sim.step(1).numpy(), g[bits_key(kind, tau, 1)], dt)
+            close_scaled(sim.step(4).numpy(), g[bits_key(kind, tau, 5)], dt)
+    if lat != "D1Q3":                                          # the edge the division emulation is wanted on
+        assert (g[bits_key("moderate", 0.501, 5)] < 0).any()
+
+
+@pytest.mark.parametrize("lat,dt", BITS_TILES, ids=[f"{l.lower()}-{d}" for l, d in BITS_TILES])
+def test_bgk_on_states_without_symmetries_on_the_smallest_tiles(lat, dt):
+    g = golden(f"bgk_bits_tiles_{lat.lower()}_{dt}")
+    assert [int(r) for r in g["resolution"]] == ([5, 64] if lat == "D2Q9" else [2, 8, 64])
+    sim = orc.OracleSimulation(orc.LATTICES[lat], torch.tensor(g["f0"]), "bgk", float(g["tau"]))
+    close_scaled(sim.step(4).numpy(), g["f4"], dt)
+    close_scaled(sim.step(1).numpy(), g["f5"], dt)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_bgk_on_states_without_symmetries_on_the_smallest_many_step_grid(dt):
+    g = golden(f"bgk_bits_many_d2q9_{dt}")
+    assert [int(r) for r in g["resolution"]] == [8, 64]
+    sim = orc.OracleSimulation(orc.LATTICES["D2Q9"], torch.tensor(g["f0"]), "bgk", float(g["tau"]))
+    close_scaled(sim.step(4).numpy(), g["f4"], dt)
+    close_scaled(sim.step(1).numpy(), g["f5"], dt)
+    close_scaled(sim.step(5).numpy(), g["f10"], dt)
+
+
+@pytest.mark.parametrize("lat,dt", BITS_BB, ids=[f"{l.lower()}-{d}" for l, d in BITS_BB])
+def test_bgk_on_states_without_symmetries_around_a_bounce_back_block(lat, dt):
+    g = golden(f"bgk_bits_bb_{lat.lower()}_{dt}")
+    b = orc.OracleBoundary("bounce_back", mask=torch.tensor(g["block_mask"]))
+    sim = orc.OracleSimulation(orc.LATTICES[lat], torch.tensor(g["f0"]), "bgk", float(g["tau"]), boundaries=[b])
+    np.testing.assert_array_equal(sim.no_collision_mask.numpy(), g["no_collision_mask"])
+    np.testing.assert_array_equal(sim.no_streaming_mask.numpy(), unpack_nsm(g))
+    assert g["no_collision_mask"].sum() == 2 ** len(g["resolution"]) and not unpack_nsm(g).any()
+    close_scaled(sim.step(1).numpy(), g["f1"], dt)
+    close_scaled(sim.step(4).numpy(), g["f5"], dt)
+
+
+def test_the_reference_sums_rho_in_another_order_after_the_last_whole_block():
+    """What the vectors without symmetries found: torch.sum over q has two orders.  Whole blocks of four SIMD vectors
+    of the flattened node index are summed in cascade order (what the HIP kernels reproduce at every node), the nodes
+    after the last whole block in four interleaved partial sums (tests/bgk_arithmetic.py).  On this machine's torch
+    too: a field of 2 blocks + 3 nodes, fp32 and fp64."""
+    g = torch.Generator().manual_seed(1)
+    for dtype, block in ((torch.float32, 32), (torch.float64, 16)):
+        f = (torch.rand([27, 2 * block + 3], generator=g, dtype=torch.float64) + 0.5).to(dtype)
+        rho = torch.sum(f, dim=0).numpy()
+        cascade = bgk_arithmetic.density_kernel_order(f.numpy())
+        interleaved = bgk_arithmetic.density_row_sum_order(f.numpy())
+        np.testing.assert_array_equal(rho[:2 * block], cascade[:2 * block])
+        np.testing.assert_array_equal(rho[2 * block:], interleaved[2 * block:])
+        assert (cascade != interleaved).any()
+
+
+@pytest.mark.parametrize("lat,dt", BITS, ids=[f"{l.lower()}-{d}" for l, d in BITS])
+def test_the_reference_vectors_are_the_kernels_arithmetic_but_for_rho_in_the_tail(lat, dt):
+    """Bit for bit, every vector of bgk_bits_*: the numpy restatement of the kernels' arithmetic with rho of the tail
+    nodes in the interleaved order.  With the GPU tests (kernel == the restatement in ONE order, everywhere) this is
+    the whole difference between the engine and the reference on a ragged grid."""
+    g = golden(f"bgk_bits_{lat.lower()}_{dt}")
+    block = int(g["sum_block"])
+    assert block == (16 if dt == "f64" else 32)
+    differs = False
+    for kind, taus in BITS_TAUS.items():
+        f0 = g[f"f0_{kind}"]
+        for tau in taus:
+            for n in (1, 5):
+                want = g[bits_key(kind, tau, n)]
+                np.testing.assert_array_equal(bgk_arithmetic.steps(f0, lat, tau, n, block), want)
+                differs |= bool((bgk_arithmetic.steps(f0, lat, tau, n, None) != want).any())
+    assert differs == (lat != "D1Q3")               # the tail is not idle: one order alone misses the vectors
+    if (lat.lower(), dt) in [(l.lower(), d) for l, d in BITS_TILES]:
+        t = golden(f"bgk_bits_tiles_{lat.lower()}_{dt}")
+        for n in (4, 5):                            # whole blocks only: one order
+            np.testing.assert_array_equal(bgk_arithmetic.steps(t["f0"], lat, float(t["tau"]), n, None), t[f"f{n}"])
+    if (lat, dt) in BITS_BB:
+        b = golden(f"bgk_bits_bb_{lat.lower()}_{dt}")
+        for n in (1, 5):
+            np.testing.assert_array_equal(bgk_arithmetic.steps(b["f0"], lat, float(b["tau"]), n, int(b["sum_block"]),
+                                                               b["block_mask"].astype(bool)), b[f"f{n}"])
+    if lat == "D2Q9":
+        m = golden(f"bgk_bits_many_d2q9_{dt}")
+        for n in (4, 5, 10):
+            np.testing.assert_array_equal(bgk_arithmetic.steps(m["f0"], lat, float(m["tau"]), n, None), m[f"f{n}"])
