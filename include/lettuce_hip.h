@@ -60,8 +60,13 @@ enum lt_stencil { LT_D2Q9 = 0, LT_D3Q19 = 1, LT_D3Q27 = 2, LT_D1Q3 = 3, LT_D3Q15
 /* AT_DISPATCH_FLOATING_TYPES, lettuce/cuda_native/_template.py:357 */
 enum lt_dtype { LT_F32 = 0, LT_F64 = 1 };
 /* lettuce/ext/_collision/no_collision.py:9-17, bgk_collision.py:12-35, kbc_collision.py:11-166,
- * smagorinsky_collision.py:7-36 (every stencil; the constant: lt_plan_set_smagorinsky) */
-enum lt_collision { LT_COLLISION_NONE = 0, LT_COLLISION_BGK = 1, LT_COLLISION_KBC = 2, LT_COLLISION_SMAGORINSKY = 3 };
+ * smagorinsky_collision.py:7-36 (every stencil; the constant: lt_plan_set_smagorinsky), trt_collision.py:6-27 (every
+ * stencil; `tau` is tau_plus, tau_minus: lt_plan_set_trt), regularized_collision.py:8-44 (every stencil).  4-7 are not
+ * collisions: inside the library a body force adds 4 to the plan's value (lt_plan_set_force) */
+enum lt_collision {
+  LT_COLLISION_NONE = 0, LT_COLLISION_BGK = 1, LT_COLLISION_KBC = 2, LT_COLLISION_SMAGORINSKY = 3,
+  LT_COLLISION_TRT = 8, LT_COLLISION_REGULARIZED = 9
+};
 /* lettuce/ext/_boundary/bounce_back_boundary.py:10-32, equilibrium_boundary_pu.py:13-46,
  * anti_bounce_back_outlet.py:13-109 */
 enum lt_boundary_kind {
@@ -412,6 +417,17 @@ int lt_plan_set_two_step(lt_plan *plan, int32_t mode, int32_t planes_per_workgro
  * mode takes them in the streaming regime as it does for BGK, lt_plan_set_two_step(plan, 1, ...) wherever the grid
  * tiles; every other plan keeps the one-step kernel (lt_plan_two_step_admitted tells why). */
 int lt_plan_set_smagorinsky(lt_plan *plan, double constant);
+/* tau_minus of a plan with LT_COLLISION_TRT, the relaxation time of the antisymmetric part of f - feq over an opposite
+ * pair (trt_collision.py:23-25); the symmetric part relaxes with the `tau` of every call (tau_plus).  1.0, the
+ * reference's default, until set.  Read at every launch, so it may change between calls like tau.  LT_ERR_INVALID (plan
+ * unchanged) for a non-positive or non-finite value, on a plan of another collision and for a null plan.
+ * LT_COLLISION_TRT and LT_COLLISION_REGULARIZED have every one-step kernel BGK has (masks, both layouts, packed plane
+ * launches, up to three outlets) and no body force (lt_plan_set_force: LT_ERR_UNSUPPORTED, as on KBC).  Two steps per
+ * launch exist for D3Q19 fp32 on periodic plans without masks (the plain sweep, both layouts), taken with
+ * lt_plan_set_two_step(plan, 1, ...) only -- never by the automatic mode.  On every other plan lt_run, lt_continue and
+ * lt_resident_advance keep the one-step kernel; the explicit multi-step entry points and lt_plan_two_step_admitted
+ * return LT_ERR_UNSUPPORTED with a reason that names the collision. */
+int lt_plan_set_trt(lt_plan *plan, double tau_minus);
 /* A uniform body force on a plan with LT_COLLISION_BGK or LT_COLLISION_SMAGORINSKY.  acceleration: `dims` values in
  * lattice units, logical order x, y, z.  A colliding node (no_collision_mask == 0) then does
  *   u*   = j / rho + (ueq_scale * a) / rho

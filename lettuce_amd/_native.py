@@ -30,6 +30,9 @@ LT_MAX_Q = 27
 STENCIL_IDS = {"D2Q9": 0, "D3Q19": 1, "D3Q27": 2, "D1Q3": 3, "D3Q15": 4}
 DTYPE_IDS = {torch.float32: 0, torch.float64: 1}
 COLLISION_IDS = {"none": 0, "bgk": 1, "kbc": 2, "smagorinsky": 3}
+# the collisions behind them in lt_collision (4-7 are not collisions: a body force adds 4 inside the library); a mapping
+# of its own, which Plan consults next to COLLISION_IDS
+MORE_COLLISION_IDS = {"trt": 8, "regularized": 9}
 BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3}
 LAYOUT_REFERENCE, LAYOUT_SLAB = 0, 1
 
@@ -99,6 +102,7 @@ SYMBOLS = {
     "lt_stream_collide_twice": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "lt_plan_set_two_step": (ctypes.c_int, [_vp, _i32, _i32]),
     "lt_plan_set_smagorinsky": (ctypes.c_int, [_vp, _dbl]),
+    "lt_plan_set_trt": (ctypes.c_int, [_vp, _dbl]),
     "lt_plan_set_force": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _dbl, _dbl]),
     "lt_stream_collide_twice_planes": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp]),
     "lt_stream_collide_twice_planes_packed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp, _vp, _vp]),
@@ -247,7 +251,7 @@ class Plan:
                                     f"(available: {sorted(STENCIL_IDS)})")
         if dtype not in DTYPE_IDS:
             raise NativeEngineError(f"dtype {dtype} has no HIP kernels (float32/float64 only)")
-        if collision not in COLLISION_IDS:
+        if collision not in COLLISION_IDS and collision not in MORE_COLLISION_IDS:
             raise NativeEngineError(f"collision {collision!r} has no HIP kernels")
         if len(boundaries) > LT_MAX_BOUNDARIES:
             raise NativeEngineError(f"{len(boundaries)} boundaries; the engine takes "
@@ -268,7 +272,7 @@ class Plan:
         desc.abi_version = LT_ABI_VERSION
         desc.stencil = STENCIL_IDS[stencil]
         desc.dtype = DTYPE_IDS[dtype]
-        desc.collision = COLLISION_IDS[collision]
+        desc.collision = COLLISION_IDS[collision] if collision in COLLISION_IDS else MORE_COLLISION_IDS[collision]
         desc.layout = layout
         desc.ghost_planes = ghost_planes
         desc.dims = self.d
@@ -722,6 +726,10 @@ class Plan:
     def set_smagorinsky(self, constant: float = 0.17):
         """the constant of a plan with the Smagorinsky collision; read at every launch, like tau"""
         self._check(self.lib.lt_plan_set_smagorinsky(self._handle, float(constant)))
+
+    def set_trt(self, tau_minus: float = 1.0):
+        """tau_minus of a TRT plan (lt_plan_set_trt): read at every launch, so it may change between calls like tau"""
+        self._check(self.lib.lt_plan_set_trt(self._handle, float(tau_minus)))
 
     def set_force(self, acceleration=None, ueq_scale: float = 0.5, source_scale: float = 0.0):
         """A uniform body force on a BGK / Smagorinsky plan, read at every launch like tau: ``acceleration`` in lattice

@@ -198,6 +198,11 @@ class _NativeStepper:
             constant = float(self.collision.constant(flow))
             self.plan.set_smagorinsky(constant)
             key = (tau, constant)
+        if self.collision.tau_minus is not None:
+            # TRT: tau_minus is re-read per batch and handed to the plan in the same way
+            tau_minus = float(self.collision.tau_minus(flow))
+            self.plan.set_trt(tau_minus)
+            key = (tau, tau_minus)
         if self.collision.force is not None:
             # a body force: acceleration and scales are re-read per batch too; a changed force starts from flow.f
             force = self.collision.force.plan_args()

@@ -389,7 +389,7 @@ class SlabSimulation:
 
     ``flow`` is built on ``slab.extended_resolution`` with ``slab=slab`` (so that its initial
     condition and its boundary masks equal the global ones on this rank's planes); ``collision``
-    is a BGK / KBC / Smagorinsky / NoCollision object.  Boundaries may be bounce-back, equilibrium (uniform or with
+    is a BGK / KBC / Smagorinsky / TRT / Regularized / NoCollision object.  Boundaries may be bounce-back, equilibrium (uniform or with
     per-node velocity / pressure given on the extended slab) and an anti-bounce-back outlet along any axis
     (along z it lives on the rank that holds the first / last plane of the global grid, together with the
     plane next to it).  ``engine`` defaults to the HIP engine; tests inject a
@@ -438,6 +438,7 @@ class SlabSimulation:
         desc = collision.native_generator()
         self._tau = desc.tau
         self._constant = desc.constant      # Smagorinsky: re-read per batch like tau (else None)
+        self._tau_minus = desc.tau_minus    # TRT: re-read per batch like tau (else None)
         self._force = desc.force            # body force: re-read per batch as well (else None)
         # boundaries: same ordering and masks as Simulation (built on the extended slab, then cut
         # to this rank's planes + one ghost plane per side and laid out z-slowest)
@@ -472,6 +473,8 @@ class SlabSimulation:
             engine.set_boundaries(entries, ncm, nsm, flow.units)      # test stand-ins
         self.engine = engine
         if self._constant is not None and not hasattr(engine, "set_smagorinsky"):
+            raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
+        if self._tau_minus is not None and not hasattr(engine, "set_trt"):
             raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
         if self._force is not None:
             if not hasattr(engine, "set_force"):
@@ -725,6 +728,8 @@ class SlabSimulation:
         tau = float(self._tau(self.flow))
         if self._constant is not None:
             self.engine.set_smagorinsky(float(self._constant(self.flow)))
+        if self._tau_minus is not None:
+            self.engine.set_trt(float(self._tau_minus(self.flow)))
         if self._force is not None:
             self.engine.set_force(*self._force.plan_args())
         cur, nxt, carried = self._start_batch(tau)

@@ -131,6 +131,7 @@ struct lt_plan {
   int residency = -1;        // workgroups per CU of the big launches: -1 = automatic, 0 = no cap
   int n_cu = 0;              // compute units of the plan's device
   double smagorinsky = 0.17; // Smagorinsky constant (lt_plan_set_smagorinsky); the reference's default
+  double tau_minus = 1.0;    // TRT: relaxation time of the antisymmetric part (lt_plan_set_trt); the reference's default
   // uniform body force (lt_plan_set_force): read at every launch like tau.  forced: the kernels with COLL = 4 + collision
   struct Force {
     bool on = false;
@@ -192,7 +193,7 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau, smagorinsky; int masked, tune, shift, residency; Force force; } gkey = {};
+  struct { void *a, *b; double tau, smagorinsky, tau_minus; int masked, tune, shift, residency; Force force; } gkey = {};
 };
 
 namespace {
@@ -542,6 +543,24 @@ const char *force_refuses(const lt_plan *p, int mode) {
   }
   return nullptr;
 }
+// TRT and the regularised collision: the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 plans
+// without masks (unit.inc, part relaxations).  nullptr: `mode` may have a launch for the plan
+bool is_relaxation(const lt_plan *p) {
+  return p->desc.collision == LT_COLLISION_TRT || p->desc.collision == LT_COLLISION_REGULARIZED;
+}
+const char *relaxation_refuses(const lt_plan *p, int mode) {
+  if (!is_relaxation(p) || (mode != lt::kFusedMany && mode != lt::kFusedTwice)) return nullptr;
+  const bool trt = p->desc.collision == LT_COLLISION_TRT;
+  if (mode == lt::kFusedTwice && p->unit.d == 3 && !p->masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
+      p->desc.dtype == LT_F32)
+    return nullptr;
+  return trt ? "the TRT collision has the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 plans "
+               "without masks only: no many-step, 2-D, masked, role-wave, edge, packed or signalling two-step kernel "
+               "takes it"
+             : "the regularised collision has the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 "
+               "plans without masks only: no many-step, 2-D, masked, role-wave, edge, packed or signalling two-step "
+               "kernel takes it";
+}
 const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
                                       "edge, packed or signalling launches): slabs keep the one-step kernels";
 
@@ -556,6 +575,8 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
     return fail(LT_ERR_INVALID, "streaming from ghost planes: range [%lld, %lld) must stay in [1, %d)",
                 pb, pe, p->n2 - 1);
   if (const char *why = force_refuses(p, mode))
+    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
+  if (const char *why = relaxation_refuses(p, mode))
     return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
   if (mode == lt::kFusedMany && (p->desc.ghost_planes || (p->masked && p->n_abb > 1)))
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: no slabs, at most one anti-bounce-back outlet");
@@ -588,6 +609,7 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   a.wrap2 = p->desc.ghost_planes ? 0 : 1;
   a.tau = tau > 0.0 ? tau : 1.0;
   a.smagorinsky = p->smagorinsky;
+  a.tau_minus = p->tau_minus;
   a.accel[0] = p->force.a[0]; a.accel[1] = p->force.a[1]; a.accel[2] = p->force.a[2];
   a.ueq_scale = p->force.ueq_scale; a.source_scale = p->force.source_scale;
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
@@ -652,6 +674,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
       return -fail(LT_ERR_HIP, "cannot create the graph stream/events");
   }
   const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.smagorinsky == p->smagorinsky &&
+                    p->gkey.tau_minus == p->tau_minus &&
                     p->gkey.force == p->force &&
                     p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
                     p->gkey.shift == p->shift;
@@ -672,7 +695,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->smagorinsky, p->masked, p->tune, p->shift, p->residency, p->force};
+    p->gkey = {cur, other, tau, p->smagorinsky, p->tau_minus, p->masked, p->tune, p->shift, p->residency, p->force};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -694,6 +717,10 @@ bool two_step_possible(lt_plan *p, const char **why) {
   const char *dummy;
   if (!why) why = &dummy;
   if (const char *refused = force_refuses(p, lt::kFusedTwice)) {
+    *why = refused;
+    return false;
+  }
+  if (const char *refused = relaxation_refuses(p, lt::kFusedTwice)) {
     *why = refused;
     return false;
   }
@@ -753,6 +780,8 @@ bool two_step_wanted(lt_plan *p) {
   // a body force: never automatic (the forced two-step sweep has not been measured against two one-step launches,
   // DESIGN.md section 7); lt_plan_set_two_step(plan, 1, ...) takes it
   if (p->force.on) return false;
+  // TRT, regularised: never automatic either, for the same reason
+  if (is_relaxation(p)) return false;
   // (Smagorinsky, D3Q19 fp32: bit-identical to two one-step launches and 0.279-0.309 against 0.409-0.475 ms per
   // update at 256^3, every sample below every sample of the one-step pair: automatic like BGK)
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
@@ -886,7 +915,7 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->mas
 // 2-D kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
 // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
-  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on) return false;
+  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on || is_relaxation(p)) return false;
   if (p->masked && p->n_abb > 1) return false;
   if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
   lt::StepArgs a;
@@ -1078,7 +1107,9 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
     return fail(LT_ERR_INVALID, "ABI version %d, library is %d", d->abi_version, LT_ABI_VERSION);
   if (d->stencil < 0 || d->stencil > 4) return fail(LT_ERR_UNSUPPORTED, "stencil %d", d->stencil);
   if (d->dtype < 0 || d->dtype > 1) return fail(LT_ERR_UNSUPPORTED, "dtype %d (fp32/fp64 only)", d->dtype);
-  if (d->collision < 0 || d->collision > LT_COLLISION_SMAGORINSKY) return fail(LT_ERR_UNSUPPORTED, "collision %d", d->collision);
+  if ((d->collision < 0 || d->collision > LT_COLLISION_SMAGORINSKY) && d->collision != LT_COLLISION_TRT &&
+      d->collision != LT_COLLISION_REGULARIZED)
+    return fail(LT_ERR_UNSUPPORTED, "collision %d", d->collision);
   const Unit unit = kUnits[2 * d->stencil + d->dtype];
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   if (d->collision == LT_COLLISION_KBC && d->stencil != LT_D2Q9 && d->stencil != LT_D3Q27)
@@ -1736,6 +1767,16 @@ int lt_plan_set_smagorinsky(lt_plan *p, double constant) {
   if (!(constant >= 0.0) || !std::isfinite(constant))
     return fail(LT_ERR_INVALID, "Smagorinsky constant %g (finite and >= 0)", constant);
   p->smagorinsky = constant;
+  return LT_OK;
+}
+
+int lt_plan_set_trt(lt_plan *p, double tau_minus) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (p->desc.collision != LT_COLLISION_TRT)
+    return fail(LT_ERR_INVALID, "the plan's collision is %d, not TRT", p->desc.collision);
+  if (!(tau_minus > 0.0) || !std::isfinite(tau_minus))
+    return fail(LT_ERR_INVALID, "TRT relaxation time tau_minus = %g (finite and > 0)", tau_minus);
+  p->tau_minus = tau_minus;
   return LT_OK;
 }
 

@@ -20,6 +20,7 @@ struct StepArgs {
   int wrap2;
   double tau;
   double smagorinsky;    // Smagorinsky constant (collision 3); the units square it
+  double tau_minus;      // TRT (collision 8): the relaxation time of the antisymmetric part; tau is tau_plus
   // body force (coll & 4, lt_plan_set_force): acceleration in the logical order x, y, z (the units permute it to the
   // memory axes of the layout) and the two scales of the scheme
   double accel[3], ueq_scale, source_scale;
@@ -27,7 +28,7 @@ struct StepArgs {
   const unsigned *nsm_bits;
   const void *bt;        // BoundaryTable<T>* (device)
   int nb;
-  int layout, coll, mode, masked, shift, tune;   // coll: lt_collision, + 4 with a body force (the kernels' COLL)
+  int layout, coll, mode, masked, shift, tune;   // coll: lt_collision (0-3, 8, 9), + 4 with a body force (the kernels' COLL)
   int strip;             // kFusedTwice on 2-D lattices: columns per workgroup (512 / 256 / 128 / 64)
   int abb_axis;          // kFusedTwice with masks: memory axis of the plan's outlet (2 without one)
   int n_abb;             // anti-bounce-back outlets of the plan
@@ -103,13 +104,15 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 #define LT_FIELD_roles(s, t, q, d, kbc, roles) roles
 
 // What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
-// on to the unit's other objects -- forced (the kernels with a body force, every unit), sweeps and smagorinsky (3-D
+// on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
+// collision), every unit, sweeps and smagorinsky (3-D
 // units), roles (units with a role-wave sweep).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
   int aux_##tag(const AuxArgs &);                              \
   const char *name_##tag(const StepArgs &, const NameBuf &);   \
   int forced_##tag(const StepArgs &, const NameBuf *);         \
+  int relax_##tag(const StepArgs &, const NameBuf *);          \
   int twice_##tag(const StepArgs &, const NameBuf *);          \
   int smag_##tag(const StepArgs &, const NameBuf *);           \
   int roles_##tag(const StepArgs &, const NameBuf *);

@@ -62,8 +62,9 @@ struct KParams {
                              // same memory channels, DESIGN.md section 4 "population stride")
   unsigned nvec_total;       // threads doing work: nv0 * n1 * planes
   T tau_inv;                 // BGK: 1/tau
-  T beta, inv_beta;          // KBC: 1/(2 tau), 1/beta
-  T tau, smag_c2;            // Smagorinsky: tau and the squared constant
+  T beta, inv_beta;          // KBC: 1/(2 tau), 1/beta; TRT reads beta as 1/(2 tau_plus)
+  T tau, smag_c2;            // Smagorinsky: tau and the squared constant.  smag_c2 is the collision's own scalar: TRT
+                             // (COLL 8) reads it as 1/(2 tau_minus), the regularised collision (COLL 9) as 1 - 1/tau
   const unsigned char *node; // [N] boundary index | 0x80 if any no-streaming bit (or null)
   const unsigned *nsm_bits;  // [N] bit q set: population q keeps its value (or null)
   const BoundaryTable<T> *bt;
@@ -553,6 +554,104 @@ __device__ __forceinline__ void collide_smagorinsky(T (&f)[S::Q][VEC], T tau, T 
   });
 }
 
+// Two relaxation times (lettuce/ext/_collision/trt_collision.py:16-27): the symmetric part of f - feq over an opposite
+// pair relaxes with tau_plus (the `tau` of the call), the antisymmetric part with tau_minus,
+//   sp = (f_q + f_o) - (feq_q + feq_o),  sm = (f_q - f_o) - (feq_q - feq_o),
+//   f_q -= sp a + sm b,  f_o -= sp a - sm b,   a = 1 / (2 tau_plus), b = 1 / (2 tau_minus).
+// The reference evaluates the expression of f_o on its own: its sp is the same sums with the operands swapped and its
+// sm the exact negative, so one evaluation per pair returns both values as the reference's order of operations gives
+// them.  The rest population has sm = 0.  rho, u and feq are BGK's, bit for bit.  The reference divides by 2.0 * tau
+// where a and b are reciprocals formed once on the host in double: compared with the reference at rounding level.  No
+// contraction by the compiler (every kernel this is inlined into returns the same bits).
+template <typename T, class S, int LAYOUT, int VEC, int k>
+__device__ __forceinline__ void collide_trt(T (&f)[S::Q][VEC], T a, T b) {
+#pragma clang fp contract(off)
+  T rho, j[3], u[3];
+  moments<T, S, LAYOUT, VEC, k>(f, rho, j);
+  u[0] = j[0] / rho; u[1] = j[1] / rho; u[2] = j[2] / rho;
+  const T uxu = square_norm<S, LAYOUT>(u);
+  T held = T(0);                                  // feq_q while for_each_feq forms feq_o (it hands out q, then o)
+  for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+#pragma clang fp contract(off)
+    constexpr int q = decltype(qc)::value;
+    constexpr int o = S::OPP[q];
+    if constexpr (q == o) {
+      const T sp = (f[q][k] + f[q][k]) - (feq + feq);
+      f[q][k] = f[q][k] - sp * a;
+    } else if constexpr (q < o) {
+      held = feq;
+    } else {                                      // o < q: the pair (o, q) with feq_o held
+      const T sp = (f[o][k] + f[q][k]) - (held + feq);
+      const T sm = (f[o][k] - f[q][k]) - (held - feq);
+      const T spa = sp * a, smb = sm * b;
+      f[o][k] = f[o][k] - (spa + smb);
+      f[q][k] = f[q][k] - (spa - smb);
+    }
+  });
+}
+
+// Regularised collision of Latt and Chopard (lettuce/ext/_collision/regularized_collision.py:17-44): the
+// non-equilibrium part is rebuilt from its second moments alone,
+//   Pi_ab = sum_q e_qa e_qb (f_q - feq_q),
+//   f_q = feq_q + (1 - 1 / tau) w_q / (2 cs^4) (sum_ab e_qa e_qb Pi_ab - cs^2 tr Pi),
+// the contraction over all d x d components (the off-diagonal ones count twice).  Pi is summed over the opposite pairs
+// as collide_smagorinsky sums it (the reference's is a GEMM over q), and `c` = 1 - 1 / tau is formed once on the host
+// in double: compared with the reference at rounding level.  rho, u and feq are BGK's, bit for bit; the equilibria
+// take the registers of f once the differences are summed, so nothing but the six moments is held beside them.  No
+// contraction by the compiler; the one multiply-add per population is written as fma_t.
+template <typename T, class S, int LAYOUT, int VEC, int k>
+__device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c) {
+#pragma clang fp contract(off)
+  T rho, j[3], u[3];
+  moments<T, S, LAYOUT, VEC, k>(f, rho, j);
+  u[0] = j[0] / rho; u[1] = j[1] / rho; u[2] = j[2] / rho;
+  const T uxu = square_norm<S, LAYOUT>(u);
+  T xx = T(0), yy = T(0), zz = T(0), xy = T(0), xz = T(0), yz = T(0);
+  T first = T(0);                                 // f_q - feq_q while for_each_feq forms feq_o
+  for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+#pragma clang fp contract(off)
+    constexpr int q = decltype(qc)::value;
+    constexpr int o = S::OPP[q];
+    const T d = f[q][k] - feq;
+    f[q][k] = feq;
+    if constexpr (q < o) {
+      first = d;
+    } else if constexpr (q > o) {                 // e_a e_b is the pair's
+      constexpr int ex = S::E[q][0], ey = S::E[q][1], ez = S::E[q][2];
+      const T v = first + d;
+      if constexpr (ex != 0) xx += v;
+      if constexpr (ey != 0) yy += v;
+      if constexpr (ez != 0) zz += v;
+      if constexpr (ex * ey > 0) xy += v; else if constexpr (ex * ey < 0) xy -= v;
+      if constexpr (ex * ez > 0) xz += v; else if constexpr (ex * ez < 0) xz -= v;
+      if constexpr (ey * ez > 0) yz += v; else if constexpr (ey * ez < 0) yz -= v;
+    }
+  });
+  T tr = xx;
+  if constexpr (S::D > 1) tr = tr + yy;
+  if constexpr (S::D > 2) tr = tr + zz;
+  const T ctr = T(kCs2) * tr;
+  const T xy2 = T(2) * xy, xz2 = T(2) * xz, yz2 = T(2) * yz;
+  static_for<S::Q>([&](auto qc) {
+    constexpr int q = decltype(qc)::value;
+    constexpr int o = S::OPP[q];
+    if constexpr (q <= o) {
+      constexpr int ex = S::E[q][0], ey = S::E[q][1], ez = S::E[q][2];
+      T t = T(0);
+      if constexpr (ex != 0) t = t + xx;
+      if constexpr (ey != 0) t = t + yy;
+      if constexpr (ez != 0) t = t + zz;
+      if constexpr (ex * ey > 0) t = t + xy2; else if constexpr (ex * ey < 0) t = t - xy2;
+      if constexpr (ex * ez > 0) t = t + xz2; else if constexpr (ex * ez < 0) t = t - xz2;
+      if constexpr (ey * ez > 0) t = t + yz2; else if constexpr (ey * ez < 0) t = t - yz2;
+      const T g = c * (t - ctr);
+      constexpr T wc = (T)(S::W[q] / (2.0 * kCs4));
+      f[q][k] = fma_t(wc, g, f[q][k]);
+      if constexpr (q < o) f[o][k] = fma_t(wc, g, f[o][k]);
+    }
+  });
+}
+
 // BGK (BASE 1) or Smagorinsky (BASE 3) with a uniform body force (lettuce/ext/_collision/bgk_collision.py:17-22,
 // smagorinsky_collision.py:19-36, lettuce/ext/_force/guo.py:14-31, shan_chen.py:14-25):
 //   u*   = j / rho + (ueq_scale a) / rho
@@ -765,6 +864,8 @@ __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, in
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(g, p.tau_inv);
         if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(g, p.beta, p.inv_beta);
         if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(g, p.tau, p.smag_c2);
+        if constexpr (COLL == 8) collide_trt<T, S, LAYOUT, 1, 0>(g, p.beta, p.smag_c2);
+        if constexpr (COLL == 9) collide_regularized<T, S, LAYOUT, 1, 0>(g, p.smag_c2);
         if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(g, p);
       }
       for (int t = 1; t < slot; ++t) {
@@ -897,7 +998,7 @@ __device__ __forceinline__ void lbm_body(const P &p) {
   int lane_slot = 0;
   T lane_rho = T(1), lane_j[3] = {T(0), T(0), T(0)};
   // (not with a body force: the neighbour's collision changes its momentum -- neighbour_moments collides it)
-  if constexpr (COLLIDE && MASKED && ABBD == 0 && (COLL & 4) == 0) {
+  if constexpr (COLLIDE && MASKED && ABBD == 0 && (COLL & 4) == 0) {   // (COLL 8 and 9 conserve rho and j, as 1-3 do)
     if (p.abb0_slot != 0) {
       const int slot = p.abb0_slot, plane = p.bt->plane[slot];
       const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -923,6 +1024,8 @@ __device__ __forceinline__ void lbm_body(const P &p) {
         if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(f, p.tau_inv);
         if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(f, p.beta, p.inv_beta);
         if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(f, p.tau, p.smag_c2);
+        if constexpr (COLL == 8) collide_trt<T, S, LAYOUT, 1, 0>(f, p.beta, p.smag_c2);
+        if constexpr (COLL == 9) collide_regularized<T, S, LAYOUT, 1, 0>(f, p.smag_c2);
         if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(f, p);
       }
       if constexpr (MASKED)

@@ -9,10 +9,10 @@
   constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
   constexpr int NU = B::template count<LAYOUT, 1>(), NC = B::template count<LAYOUT, 0>(),
                 ND = B::template count<LAYOUT, -1>();
-  static_assert(COLL == 0 || COLL == 1 || COLL == 3 || COLL == 5 || COLL == 7,
-                "two-step kernel: streaming only, BGK or Smagorinsky, the latter two also with a body force");
-  static_assert((COLL != 3 && (COLL & 4) == 0) || (SCHED == 0 && MODE == 0),
-                "Smagorinsky, body force: the plain one-role sweep only");
+  static_assert(COLL == 0 || COLL == 1 || COLL == 3 || COLL == 5 || COLL == 7 || COLL == 8 || COLL == 9,
+                "two-step kernel: streaming only, BGK or Smagorinsky, the latter two also with a body force, TRT, regularised");
+  static_assert((COLL != 3 && (COLL & 4) == 0 && COLL < 8) || (SCHED == 0 && MODE == 0),
+                "Smagorinsky, body force, TRT, regularised: the plain one-role sweep only");
   __shared__ T lds_u[4][NU][NI];
   __shared__ T lds_c[3][NC][NI];
   __shared__ T lds_d[2][ND][NI];
@@ -229,6 +229,10 @@
         static_for<NPT>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau_inv); });
       if constexpr (COLL == 3)
         static_for<NPT>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau, p.smag_c2); });
+      if constexpr (COLL == 8)
+        static_for<NPT>([&](auto kc) { collide_trt<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.beta, p.smag_c2); });
+      if constexpr (COLL == 9)
+        static_for<NPT>([&](auto kc) { collide_regularized<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.smag_c2); });
       if constexpr ((COLL & 4) != 0)
         static_for<NPT>([&](auto kc) { collide_forced<T, S, LAYOUT, NPT, decltype(kc)::value, (COLL & 3)>(pre, p); });
       static_for<S::Q>([&](auto qc) {
@@ -265,6 +269,10 @@
         static_for<NPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau_inv); });
       if constexpr (COLL == 3)
         static_for<NPB>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau, p.smag_c2); });
+      if constexpr (COLL == 8)
+        static_for<NPB>([&](auto kc) { collide_trt<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.beta, p.smag_c2); });
+      if constexpr (COLL == 9)
+        static_for<NPB>([&](auto kc) { collide_regularized<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.smag_c2); });
       if constexpr ((COLL & 4) != 0)
         static_for<NPB>([&](auto kc) { collide_forced<T, S, LAYOUT, NPB, decltype(kc)::value, (COLL & 3)>(f, p); });
     }

@@ -33,12 +33,16 @@
 //   forced (inst5_)       every unit: the kernels with a body force (the kernels' COLL = 5: BGK, 7: Smagorinsky) -- every
 //                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; objects
 //                         of their own, so that the objects of the unforced kernels are what they were
+//   relaxations (inst6_)  every unit: the TRT and the regularised collision (the kernels' COLL = 8 and 9) -- every
+//                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; again
+//                         objects of their own: the earlier objects stay what they were and none of these is the longest job
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
 #define LT_PART_roles 3
 #define LT_PART_smagorinsky 4
 #define LT_PART_forced 5
+#define LT_PART_relaxations 6
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
 #define LT_ONE_STEP 1
@@ -55,8 +59,11 @@
 #elif LT_PART_IS(forced)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 1
+#elif LT_PART_IS(relaxations)
+#define LT_ONE_STEP 1
+#define LT_SWEEP 1
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky or forced"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced or relaxations"
 #endif
 
 namespace lt {
@@ -97,6 +104,10 @@ P params_of(const StepArgs &a, int n2) {
   p.inv_beta = (T)(1. / beta);
   p.tau = (T)a.tau;
   p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
+  // the collision's own scalar (kernels.hpp, KParams): TRT 1 / (2 tau_minus) beside beta = 1 / (2 tau_plus)
+  // (trt_collision.py:22,25), the regularised collision 1 - 1 / tau (regularized_collision.py:42)
+  if (a.coll == 8) p.smag_c2 = (T)(1.0 / (2.0 * a.tau_minus));
+  if (a.coll == 9) p.smag_c2 = (T)(1.0 - 1.0 / a.tau);
   p.node = a.node;
   p.nsm_bits = a.nsm_bits;
   p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
@@ -206,7 +217,8 @@ int launch(const StepArgs &a, const NameBuf *name) {
   LT_TRY(LAYOUT, COLL, kCollideOnly, MASKED)
 
 // The one-step kernels of collision C, fused and collide-only: main has them for 0 (none), 1 (BGK) and, with
-// LT_HAS_KBC, 2; Smagorinsky (3) has every variant BGK has, and so have BGK and Smagorinsky with a body force (5, 7).
+// LT_HAS_KBC, 2; Smagorinsky (3) has every variant BGK has, and so have BGK and Smagorinsky with a body force (5, 7),
+// TRT (8) and the regularised collision (9).
 // The order matters where the conditions overlap: the outlet depths before the rest, packed before the plain slab set.
 template <int C>
 int one_step_of(const StepArgs &a, const NameBuf *name) {
@@ -238,12 +250,13 @@ int one_step_of(const StepArgs &a, const NameBuf *name) {
 // returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
 // one node per thread and per block: the kernel's NPT = NPB = 1
 // SCHED 1: separate producer and consumer waves (twostep_roles.hpp)
-// Smagorinsky (COLL 3) and BGK with a body force (COLL 5): the plain one-role sweep of D3Q19 fp32
+// Smagorinsky (COLL 3), BGK with a body force (COLL 5), TRT (8) and the regularised collision (9): the plain one-role
+// sweep of D3Q19 fp32
 template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
 int launch_twice(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 3 && T0 > 0 &&
                 (COLL == 0 || COLL == 1 ||
-                 ((COLL == 3 || COLL == 5) && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
+                 ((COLL == 3 || COLL == 5 || COLL == 8 || COLL == 9) && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
     using B = TwoStep<T, S, T0, T1>;
     if (name) return kernel_name(*name, "lbm2_kernel", LAYOUT, COLL, T0, T1, 1, MODE, 1, elided(SCHED));
     // in-plane byte offsets are 32-bit in the kernel
@@ -291,6 +304,13 @@ int sweep(const StepArgs &a, const NameBuf *name) {
     if (a.layout == 1 && a.coll == 5) return launch_twice<1, 5, W, R>(a, name);
     // (Smagorinsky with a force, COLL 7: 168 VGPRs and 84-92 bytes of scratch per lane under every scheduler setting
     // where the unforced sweep has 168 and none -- not built, the plan keeps the one-step kernel: DESIGN.md section 4)
+#elif LT_PART_IS(relaxations)
+    // TRT and the regularised collision: plain sweeps of periodic plans (no packing, no signalling launch)
+    if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
+    if (a.layout == 0 && a.coll == 8) return launch_twice<0, 8, W, R>(a, name);
+    if (a.layout == 1 && a.coll == 8) return launch_twice<1, 8, W, R>(a, name);
+    if (a.layout == 0 && a.coll == 9) return launch_twice<0, 9, W, R>(a, name);
+    if (a.layout == 1 && a.coll == 9) return launch_twice<1, 9, W, R>(a, name);
 #else
     // the unmasked two-step launches of a 3-D unit
     const int coll = a.coll;
@@ -450,6 +470,7 @@ int twice_3d(const StepArgs &a, const NameBuf *name) {
 int dispatch(const StepArgs &a, const NameBuf *name) {
   const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
   if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
+  if (coll == 8 || coll == 9) return LT_CAT(relax_, LT_TAG)(a, name);   // TRT, regularised: part relaxations
   if (a.mode == kFusedMany) {
     if (coll == 0) return many_of<0>(a, name);
     if (coll == 1) return many_of<1>(a, name);
@@ -607,6 +628,15 @@ int LT_CAT(forced_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
   if (a.coll == 5) return one_step_of<5>(a, name);
   if (a.coll == 7) return one_step_of<7>(a, name);
+  return kNoKernel;
+}
+#elif LT_PART_IS(relaxations)
+// one-step kernels and the plain sweep only: no many-step, 2-D or masked two-step launch
+int LT_CAT(relax_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
+  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
+  if (a.coll == 8) return one_step_of<8>(a, name);
+  if (a.coll == 9) return one_step_of<9>(a, name);
   return kNoKernel;
 }
 #endif

@@ -1,11 +1,14 @@
-"""Collision operators on the hot path: BGK, KBC (D2Q9 / D3Q27), Smagorinsky (every lattice) and NoCollision.
+"""Collision operators on the hot path: BGK, KBC (D2Q9 / D3Q27), Smagorinsky, TRT, regularised (every lattice) and
+NoCollision.
 
 Each ``__call__`` is a pure whole-field function ``flow -> tensor`` usable outside a
 ``Simulation`` (the reference's tests call ``collision(flow)`` directly).  On a native context
 and for the flow's grid-shaped state it is one launch of the engine's collide kernel;
 otherwise the reference's torch expressions are evaluated.  BGK and Smagorinsky take a body force
 (``force=Guo(...)`` / ``ShanChen(...)``, ext/_force.py), on the engine when its acceleration is uniform.
-TRT / MRT / regularised collisions are out of scope.
+TRT and the regularised collision are on the engine for every lattice as well (one-step kernels; the plain two-step
+sweep on D3Q19 fp32); neither takes a force, as in the reference.  MRT is out of scope: it needs
+the reference's Transform classes.
 """
 import warnings
 from typing import AnyStr, Optional
@@ -18,13 +21,13 @@ from ._force import Force
 from ..util import LettuceException
 
 __all__ = ["BGKCollision", "KBCCollision", "KBCCollision2D", "KBCCollision3D", "NoCollision",
-           "SmagorinskyCollision"]
+           "SmagorinskyCollision", "TRTCollision", "RegularizedCollision"]
 
 
-def _engine_collide(flow, kind, tau, constant=None, force=None):
+def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None):
     """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``constant``: the
-    Smagorinsky constant, ``force``: the collision's body force (a Force or None) -- per-launch settings of the
-    kind's one plan, handed over before every collide."""
+    Smagorinsky constant, ``tau_minus``: TRT's second relaxation time, ``force``: the collision's body force (a Force
+    or None) -- per-launch settings of the kind's one plan, handed over before every collide."""
     if flow._engine_plan(flow.f) is None:
         return None
     plans = flow.__dict__.setdefault("_collision_plans", {})
@@ -34,6 +37,8 @@ def _engine_collide(flow, kind, tau, constant=None, force=None):
                            device=flow.f.device)
     if constant is not None:
         plans[kind].set_smagorinsky(constant)
+    if tau_minus is not None:
+        plans[kind].set_trt(tau_minus)
     if kind in ("bgk", "smagorinsky"):
         if force is None:
             plans[kind].set_force(None)
@@ -236,6 +241,86 @@ class SmagorinskyCollision(Collision):
     def native_generator(self) -> "NativeCollision":
         return NativeCollision("smagorinsky", tau=lambda flow: self.tau, constant=lambda flow: self.constant,
                                force=None if self.force is None else self.force.native_generator())
+
+
+class TRTCollision(Collision):
+    """Two relaxation times (lettuce/ext/_collision/trt_collision.py:6-27): over an opposite pair the symmetric part of
+    f - feq relaxes with ``tau_plus`` (the constructor's ``tau``, which sets the viscosity), the antisymmetric part with
+    ``tau_minus``.  Both attributes are read on every call, as in the reference."""
+
+    def __init__(self, tau, tau_minus=1.0):
+        self.tau_plus = tau
+        self.tau_minus = tau_minus
+
+    def __call__(self, flow: "Flow") -> torch.Tensor:
+        out = _engine_collide(flow, "trt", self.tau_plus, tau_minus=self.tau_minus)
+        if out is not None:
+            return out
+        opposite = flow.stencil.opposite
+        feq = flow.equilibrium(flow)
+        f_diff_neq = (((flow.f + flow.f[opposite]) - (feq + feq[opposite])) / (2.0 * self.tau_plus))
+        f_diff_neq += (((flow.f - flow.f[opposite]) - (feq - feq[opposite])) / (2.0 * self.tau_minus))
+        return flow.f - f_diff_neq
+
+    def native_available(self) -> bool:
+        return True
+
+    def native_generator(self) -> "NativeCollision":
+        return NativeCollision("trt", tau=lambda flow: self.tau_plus, tau_minus=lambda flow: self.tau_minus)
+
+
+class RegularizedCollision(Collision):
+    """Regularised LBM of Latt and Chopard (lettuce/ext/_collision/regularized_collision.py:8-44): the non-equilibrium
+    populations are rebuilt from their second moments, f = feq + (1 - 1 / tau) w_q / (2 cs^4) Q_q : Pi_neq.
+
+    As in the reference the constructor's ``tau`` is not used: on the first call tau is taken from
+    ``flow.units.relaxation_parameter_lu`` (regularized_collision.py:18-19); assignments to ``.tau`` after that are
+    read on every call."""
+
+    def __init__(self, tau: float = None):
+        self.tau = tau
+        self.Q_matrix = None
+
+    def _prepare(self, flow):
+        if self.Q_matrix is not None:
+            return
+        self.tau = flow.units.relaxation_parameter_lu
+        e = flow.torch_stencil.e.to(flow.context.dtype)
+        q_matrix = torch.einsum("qa,qb->qab", e, e)
+        q_matrix = q_matrix - torch.eye(flow.stencil.d, device=e.device, dtype=e.dtype) * flow.torch_stencil.cs ** 2
+        self.Q_matrix = q_matrix
+
+    def __call__(self, flow: "Flow") -> torch.Tensor:
+        self._prepare(flow)
+        out = _engine_collide(flow, "regularized", self.tau)
+        if out is not None:
+            return out
+        feq = flow.equilibrium(flow)
+        f_neq = flow.f - feq
+        d, w = flow.stencil.d, flow.torch_stencil.w
+        cs4 = flow.stencil.cs ** 4
+        if f_neq.is_cuda:       # no BLAS on device tensors (see _flow.local_contract)
+            from .._flow import local_contract
+            e = flow.torch_stencil.e
+            ee = torch.einsum("qa,qb->abq", e, e).reshape(d * d, -1)
+            pi_neq = local_contract(ee, f_neq)
+            pi_neq = local_contract(self.Q_matrix.reshape(-1, d * d), pi_neq)
+            pi_neq = pi_neq * w.reshape([-1] + [1] * d)
+        else:
+            pi_neq = flow.shear_tensor(f_neq)
+            pi_neq = flow.einsum("qab,ab->q", [self.Q_matrix, pi_neq])
+            pi_neq = flow.einsum("q,q->q", [w, pi_neq])
+        fi1 = pi_neq / (2 * cs4)
+        return feq + (1. - 1. / self.tau) * fi1
+
+    def native_available(self) -> bool:
+        return True
+
+    def native_generator(self) -> "NativeCollision":
+        def tau(flow):
+            self._prepare(flow)
+            return self.tau
+        return NativeCollision("regularized", tau=tau)
 
 
 class NoCollision(Collision):

@@ -34,7 +34,7 @@ class NativeForce:
 
 @dataclass
 class NativeCollision:
-    kind: str                                  # 'none' | 'bgk' | 'kbc' | 'smagorinsky'
+    kind: str                                  # 'none' | 'bgk' | 'kbc' | 'smagorinsky' | 'trt' | 'regularized'
     # relaxation time used for the next batch of steps; evaluated per call because the
     # reference re-reads collision.tau on every invocation
     # (lettuce/cuda_native/ext/_collision/bgk_collision.py:30)
@@ -45,6 +45,9 @@ class NativeCollision:
     # 'smagorinsky': the constant, evaluated per batch like tau (the reference reads collision.constant on every
     # call, lettuce/ext/_collision/smagorinsky_collision.py:32); None for the other kinds
     constant: Optional[Callable[["Flow"], float]] = None
+    # 'trt': tau_minus, evaluated per batch like tau (the reference reads collision.tau_minus on every call,
+    # lettuce/ext/_collision/trt_collision.py:25; `tau` is its tau_plus); None for the other kinds
+    tau_minus: Optional[Callable[["Flow"], float]] = None
     # 'bgk' / 'smagorinsky': the body force of the collision, or None
     force: Optional[NativeForce] = None
 
