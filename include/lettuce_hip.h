@@ -72,7 +72,11 @@ enum lt_collision {
 enum lt_boundary_kind {
   LT_BOUNDARY_BOUNCE_BACK = 1,
   LT_BOUNDARY_EQUILIBRIUM = 2,
-  LT_BOUNDARY_ABB_OUTLET = 3
+  LT_BOUNDARY_ABB_OUTLET = 3,
+  /* EquilibriumOutletP (equilibrium_outlet_p.py:12-91): every node of the outlet plane gets feq(rho_outlet, u of the
+   * node next to it).  axis, side and flags as for the ABB outlet; one-step kernels only (lt_run keeps them; the
+   * entry points with several steps per launch answer LT_ERR_UNSUPPORTED and name the boundary). */
+  LT_BOUNDARY_PRESSURE_OUTLET = 4
 };
 enum lt_layout { LT_LAYOUT_REFERENCE = 0, LT_LAYOUT_SLAB = 1 };
 #define LT_BOUNDARY_ABSENT 1
@@ -81,13 +85,15 @@ enum lt_layout { LT_LAYOUT_REFERENCE = 0, LT_LAYOUT_SLAB = 1 };
  * is the boundary whose index in no_collision_mask is i + 1. */
 typedef struct lt_boundary_desc {
   int32_t kind;            /* lt_boundary_kind */
-  int32_t axis;            /* ABB outlet: logical axis of `direction` (0 = x) */
-  int32_t side;            /* ABB outlet: +1 or -1 */
-  int32_t flags;           /* ABB outlet on a slab plan (ghost_planes > 0) whose normal is the decomposed axis:
+  int32_t axis;            /* ABB / pressure outlet: logical axis of `direction` (0 = x) */
+  int32_t side;            /* ABB / pressure outlet: +1 or -1 */
+  int32_t flags;           /* ABB / pressure outlet on a slab plan (ghost_planes > 0) whose normal is the decomposed axis:
                             * bit 0 (LT_BOUNDARY_ABSENT) = another rank holds the first / last plane of the
                             * global grid, this rank has no outlet; else 0 */
   /* EQUILIBRIUM with uniform velocity/pressure: the populations written on the masked
-   * nodes, i.e. feq(rho(p_pu), u_lu(v_pu)) as the host evaluated it in the flow's dtype. */
+   * nodes, i.e. feq(rho(p_pu), u_lu(v_pu)) as the host evaluated it in the flow's dtype.
+   * PRESSURE OUTLET: feq[0] is rho_outlet (rounded to the plan's dtype when it is uploaded); the struct keeps its
+   * size and LT_ABI_VERSION its value.  lt_plan_update_boundary takes a new one between calls. */
   double feq[LT_MAX_Q];
   /* EQUILIBRIUM with per-node velocity/pressure: device pointer to a [q, *res] field of the
    * plan's dtype (borrowed; must outlive the plan or be re-set), or NULL. */

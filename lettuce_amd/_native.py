@@ -33,7 +33,7 @@ COLLISION_IDS = {"none": 0, "bgk": 1, "kbc": 2, "smagorinsky": 3}
 # the collisions behind them in lt_collision (4-7 are not collisions: a body force adds 4 inside the library); a mapping
 # of its own, which Plan consults next to COLLISION_IDS
 MORE_COLLISION_IDS = {"trt": 8, "regularized": 9}
-BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3}
+BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3, "pressure_outlet": 4}
 LAYOUT_REFERENCE, LAYOUT_SLAB = 0, 1
 
 
@@ -237,7 +237,8 @@ class Plan:
     ``boundaries`` is a list of dicts in index order (index = position + 1 in
     ``no_collision_mask``): ``{"kind": "bounce_back"}``,
     ``{"kind": "equilibrium", "feq": [q floats] | "field": tensor[q,*res]}``,
-    ``{"kind": "abb_outlet", "axis": a, "side": +-1}``.
+    ``{"kind": "abb_outlet", "axis": a, "side": +-1}``,
+    ``{"kind": "pressure_outlet", "axis": a, "side": +-1, "rho_outlet": rho}`` (one-step kernels only).
     """
 
     def __init__(self, stencil: str, dtype: torch.dtype, collision: str,
@@ -295,6 +296,8 @@ class Plan:
         out.side = int(b.get("side", 0))
         out.flags = 0 if b.get("present", True) else 1      # LT_BOUNDARY_ABSENT: another rank holds the outlet plane
         out.feq_field_dev = None
+        if b["kind"] == "pressure_outlet":
+            out.feq[0] = float(b.get("rho_outlet", 1.0))      # lettuce_hip.h: rho_outlet travels in feq[0]
         if b["kind"] == "equilibrium":
             field = b.get("field")
             if field is not None:

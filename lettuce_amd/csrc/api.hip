@@ -155,6 +155,7 @@ struct lt_plan {
   double *partial = nullptr;
   int masked = 0;
   int n_abb = 0;             // anti-bounce-back outlets of the plan
+  int n_pout = 0;            // constant-pressure outlets of the plan (one-step kernels only: pressure_outlet_refuses)
   int abb_depth = 0;         // how deep an outlet's neighbour must be rebuilt (lt_plan_create)
   int nsm_confined = 1;      // the no-streaming bits are exactly those of the plan's outlet (lt_plan_set_masks)
   int inlet_faces_outlet = 1;  // outlet along a0: every node of the opposite face is an equilibrium node
@@ -216,7 +217,8 @@ int upload_boundaries(lt_plan *p, hipStream_t stream) {
     const lt_boundary_desc &b = p->desc.boundaries[i];
     const int s = i + 1;
     h.kind[s] = b.kind;
-    if (b.kind == LT_BOUNDARY_ABB_OUTLET) {
+    if (b.kind == LT_BOUNDARY_PRESSURE_OUTLET) h.rho_outlet[s] = (T)b.feq[0];   // rounded as the reference's tensor is
+    if (b.kind == LT_BOUNDARY_ABB_OUTLET || b.kind == LT_BOUNDARY_PRESSURE_OUTLET) {
       const int ax = mem_axis_of(p, b.axis);
       h.mem_axis[s] = ax;
       h.side[s] = b.side;
@@ -242,11 +244,13 @@ int check_boundary(const lt_plan *p, const lt_boundary_desc &b, int n_abb_before
     case LT_BOUNDARY_BOUNCE_BACK:
     case LT_BOUNDARY_EQUILIBRIUM:
       return LT_OK;
-    case LT_BOUNDARY_ABB_OUTLET: {
+    case LT_BOUNDARY_ABB_OUTLET:
+    case LT_BOUNDARY_PRESSURE_OUTLET: {
+      const char *what = b.kind == LT_BOUNDARY_ABB_OUTLET ? "anti-bounce-back outlet" : "constant-pressure outlet";
       if (b.axis < 0 || b.axis >= p->unit.d || (b.side != 1 && b.side != -1))
-        return fail(LT_ERR_INVALID, "anti-bounce-back outlet: axis %d side %d", b.axis, b.side);
+        return fail(LT_ERR_INVALID, "%s: axis %d side %d", what, b.axis, b.side);
       if (p->desc.shape[b.axis] < 2)
-        return fail(LT_ERR_INVALID, "anti-bounce-back outlet needs >= 2 planes along its axis");
+        return fail(LT_ERR_INVALID, "%s needs >= 2 planes along its axis", what);
       if (p->desc.ghost_planes && b.axis == 2 && !(b.flags & LT_BOUNDARY_ABSENT) && p->desc.shape[2] < 2)
         return fail(LT_ERR_INVALID, "an outlet along the decomposed (z) axis needs >= 2 planes on its rank");
       return LT_OK;
@@ -564,6 +568,16 @@ const char *relaxation_refuses(const lt_plan *p, int mode) {
 const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
                                       "edge, packed or signalling launches): slabs keep the one-step kernels";
 
+// The constant-pressure outlet (LT_BOUNDARY_PRESSURE_OUTLET) has the one-step kernels only (unit.inc, part outlets).
+// Refused by name, not through the admission tests of the masked two-step kernels, which were written for the
+// anti-bounce-back outlet's no-streaming bits
+const char *const kPressureOutletMultiStep = "a constant-pressure outlet (EquilibriumOutletP) has the one-step kernels only: "
+                                             "no masked two-step, 2-D two-step, many-step or two-ghost-plane slab kernel "
+                                             "takes it";
+const char *pressure_outlet_refuses(const lt_plan *p, int mode) {
+  return p->n_pout > 0 && (mode == lt::kFusedMany || mode == lt::kFusedTwice) ? kPressureOutletMultiStep : nullptr;
+}
+
 int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long pb, long long pe,
          void *stream, long long stride = 1, void *pack_lo = nullptr, void *pack_hi = nullptr) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
@@ -577,6 +591,8 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   if (const char *why = force_refuses(p, mode))
     return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
   if (const char *why = relaxation_refuses(p, mode))
+    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
+  if (const char *why = pressure_outlet_refuses(p, mode))
     return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
   if (mode == lt::kFusedMany && (p->desc.ghost_planes || (p->masked && p->n_abb > 1)))
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: no slabs, at most one anti-bounce-back outlet");
@@ -618,8 +634,9 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   a.abb_depth = p->abb_depth;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.n_abb = p->masked ? p->n_abb : 0;
+  a.n_pout = p->masked ? p->n_pout : 0;
   a.abb0_slot = 0;
-  if (p->masked && p->n_abb == 1)
+  if (p->masked && p->n_abb == 1 && p->n_pout == 0)
     for (int i = 0; i < p->desc.n_boundaries; ++i) {
       const lt_boundary_desc &b = p->desc.boundaries[i];
       if (b.kind == LT_BOUNDARY_ABB_OUTLET && !(b.flags & LT_BOUNDARY_ABSENT) && mem_axis_of(p, b.axis) == 0)
@@ -721,6 +738,10 @@ bool two_step_possible(lt_plan *p, const char **why) {
     return false;
   }
   if (const char *refused = relaxation_refuses(p, lt::kFusedTwice)) {
+    *why = refused;
+    return false;
+  }
+  if (const char *refused = pressure_outlet_refuses(p, lt::kFusedTwice)) {
     *why = refused;
     return false;
   }
@@ -915,7 +936,7 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->mas
 // 2-D kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
 // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
-  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on || is_relaxation(p)) return false;
+  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on || is_relaxation(p) || p->n_pout > 0) return false;
   if (p->masked && p->n_abb > 1) return false;
   if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
   lt::StepArgs a;
@@ -1083,10 +1104,15 @@ int store_admission(lt_plan *p, hipStream_t hs) {
 }
 
 // the outlets' axes decide how deep an outlet's neighbour must be rebuilt (see lt_plan_create); -1: unsupported
+// (outlets of both kinds: a constant-pressure outlet reads its neighbour as an anti-bounce-back outlet does, and
+// rewrites its plane)
 int abb_depth_of(const lt_plan_desc &d) {
   int n_abb = 0, axes = 0;
   for (int i = 0; i < d.n_boundaries; ++i)
-    if (d.boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET) { ++n_abb; axes |= 1 << d.boundaries[i].axis; }
+    if (d.boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET || d.boundaries[i].kind == LT_BOUNDARY_PRESSURE_OUTLET) {
+      ++n_abb;
+      axes |= 1 << d.boundaries[i].axis;
+    }
   const int n_axes = (axes & 1) + ((axes >> 1) & 1) + ((axes >> 2) & 1);
   const int depth = n_abb <= 1 ? 0 : (n_axes <= 2 ? 1 : n_axes - 1);
   return depth > 1 && d.layout != LT_LAYOUT_REFERENCE ? -1 : depth;
@@ -1155,6 +1181,7 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
     const int rc = check_boundary(p, d->boundaries[i], n_abb);
     if (rc) { delete p; return rc; }
     if (d->boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET) ++n_abb;
+    if (d->boundaries[i].kind == LT_BOUNDARY_PRESSURE_OUTLET) ++p->n_pout;
   }
   p->n_abb = n_abb;
   // How deep the kernels must rebuild an outlet's neighbour (neighbour_moments, DEPTH): where the planes of outlets
@@ -1251,8 +1278,11 @@ int lt_plan_update_boundary(lt_plan *p, int32_t index, const lt_boundary_desc *b
   }
   p->abb_depth = depth;
   // an outlet that moves (axis, side, present / absent) changes which kernels apply and what they compute on its plane
-  const bool moved = b->kind == LT_BOUNDARY_ABB_OUTLET &&
+  const bool moved = (b->kind == LT_BOUNDARY_ABB_OUTLET || b->kind == LT_BOUNDARY_PRESSURE_OUTLET) &&
                      (b->axis != old.axis || b->side != old.side || b->flags != old.flags);
+  // a constant-pressure outlet's density is read from the boundary table at every launch, like an inlet's feq; a
+  // captured graph is still dropped with it, so that nothing replayed was recorded for another outlet
+  const bool density = b->kind == LT_BOUNDARY_PRESSURE_OUTLET && b->feq[0] != old.feq[0];
   // an equilibrium boundary that switches between its constant feq and a per-node field takes the other branch of
   // the kernels' boundary dispatch -- the code the first-use check exists for
   const bool source = b->kind == LT_BOUNDARY_EQUILIBRIUM && (b->feq_field_dev == nullptr) != (old.feq_field_dev == nullptr);
@@ -1260,7 +1290,7 @@ int lt_plan_update_boundary(lt_plan *p, int32_t index, const lt_boundary_desc *b
   rc = p->desc.dtype == LT_F32 ? upload_boundaries<float>(p, hs) : upload_boundaries<double>(p, hs);
   if (rc) return rc;
   if (moved || source) p->canary = 0;                // the first-use check runs again
-  if (moved && p->gexec) {                           // the captured launches carry the old outlet's kernel arguments
+  if ((moved || density) && p->gexec) {              // the captured launches carry the old outlet's kernel arguments
     (void)hipGraphExecDestroy(p->gexec);
     p->gexec = nullptr;
   }
@@ -1419,6 +1449,7 @@ const char *lt_plan_kernel_name(lt_plan *p) {
   if (many_step_wanted(p)) a.mode = lt::kFusedMany;
   a.masked = p->masked;
   a.abb_depth = p->abb_depth;
+  a.n_pout = p->masked ? p->n_pout : 0;
   a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
   a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
   a.shift = p->shift;

@@ -34,6 +34,7 @@ struct StepArgs {
   int n_abb;             // anti-bounce-back outlets of the plan
   int abb0_slot;         // one-step kernels: 1-based index of the plan's only outlet if its normal is memory axis a0, else 0
   int abb_depth;         // anti-bounce-back outlets of the plan - 1 (0: at most one; the kernels exist for 0 and 1)
+  int n_pout;            // constant-pressure outlets of the plan: > 0 takes the unit's part outlets (one-step kernels only)
   int lds_bytes;         // unused dynamic LDS per workgroup (residency cap), 0 = none
   int seg_len;           // kFusedTwice: a2 planes per workgroup; kFusedMany: steps in this launch
   void *pack_lo, *pack_hi;         // fused halo packing (slab boundary launch) or null
@@ -105,7 +106,7 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 
 // What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
 // on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
-// collision), every unit, sweeps and smagorinsky (3-D
+// collision) and outlets (plans with a constant-pressure outlet), every unit, sweeps and smagorinsky (3-D
 // units), roles (units with a role-wave sweep).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
@@ -113,6 +114,9 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
   const char *name_##tag(const StepArgs &, const NameBuf &);   \
   int forced_##tag(const StepArgs &, const NameBuf *);         \
   int relax_##tag(const StepArgs &, const NameBuf *);          \
+  int outlets_##tag(const StepArgs &, const NameBuf *);        \
+  int outlets2_##tag(const StepArgs &, const NameBuf *);       \
+  int outlets3_##tag(const StepArgs &, const NameBuf *);       \
   int twice_##tag(const StepArgs &, const NameBuf *);          \
   int smag_##tag(const StepArgs &, const NameBuf *);           \
   int roles_##tag(const StepArgs &, const NameBuf *);

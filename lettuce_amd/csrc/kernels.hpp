@@ -33,6 +33,11 @@ constexpr int kMaxB = 127;   // == LT_MAX_BOUNDARIES: what the node byte's seven
 
 // boundary kinds (== lt_boundary_kind)
 constexpr int kBounceBack = 1, kEquilibrium = 2, kAbbOutlet = 3;
+// ... and the constant-pressure equilibrium outlet.  Only kernels instantiated for it know this kind: an outlet depth
+// (the kernels' ABBD, neighbour_moments' DEPTH) of kOutletsP + chain, the reserved range above the depths 0-2 of the
+// plans with anti-bounce-back outlets alone, whose kernels are compiled from the same text as before
+constexpr int kPressureOutlet = 4;
+constexpr int kOutletsP = 4;
 
 template <typename T>
 struct BoundaryTable {
@@ -43,6 +48,7 @@ struct BoundaryTable {
   int nbr[kMaxB + 1];        // ABB: memory coordinate of the plane next to it (inside)
   T feq[kMaxB + 1][27];      // EQUILIBRIUM, uniform
   const T *field[kMaxB + 1]; // EQUILIBRIUM, per node [q][N] (or null)
+  T rho_outlet[kMaxB + 1];   // PRESSURE OUTLET: the density it imposes, in the plan's scalar type
 };
 
 template <typename T>
@@ -766,9 +772,27 @@ __device__ __forceinline__ void bounce_back(T (&f)[S::Q][VEC]) {
   });
 }
 
+// EquilibriumOutletP (lettuce/ext/_boundary/equilibrium_outlet_p.py:63-73) on one node of the outlet plane, given
+// (rho, j) of the node next to it (neighbour_moments): ALL populations become feq(rho_outlet, u_n), u_n = j_n / rho_n
+// -- the quadratic equilibrium of the collisions, bit for bit (for_each_feq; the reference's cs^2).  The outlet's axis
+// does not enter: nothing of the node's own state survives, whichever way the plane faces.  No contraction by the
+// compiler (every kernel this is inlined into returns the same bits).
+template <typename T, class S, int LAYOUT, int VEC = 1, int k = 0>
+__device__ __forceinline__ void pressure_outlet_apply(T rho_outlet, T rn, const T (&jn)[3], T (&f)[S::Q][VEC]) {
+#pragma clang fp contract(off)
+  T u[3];
+  u[0] = jn[0] / rn; u[1] = jn[1] / rn; u[2] = jn[2] / rn;
+  const T uxu = square_norm<S, LAYOUT>(u);
+  for_each_feq<T, S, LAYOUT>(rho_outlet, u, uxu, [&](auto qc, T feq) { f[decltype(qc)::value][k] = feq; });
+}
+
 // What the boundaries with an index below `slot` do to (rho, j) of a node whose no_collision_mask index
 // is b (collision conserves both): bounce-back negates j, an equilibrium boundary replaces the moments
-// by those of its populations (neighbour_moments; also the two-step kernel's phase B)
+// by those of its populations (neighbour_moments; also the two-step kernel's phase B).  A constant-pressure outlet
+// (kPressureOutlet) does nothing here: it writes its plane, whatever the nodes' indices, and a node of that plane never
+// reaches this function -- the kernels of such plans rebuild it in full (neighbour_moments, DEPTH) -- while a node that
+// carries the outlet's index off its plane is left alone by the reference too (the in-place write, then a masked
+// torch.where that changes nothing)
 template <typename T, class S, int LAYOUT>
 __device__ __forceinline__ void lower_boundaries_on_moments(const KParams<T> &p, int b, int slot, unsigned own,
                                                             T &rho, T (&j)[3]) {
@@ -837,6 +861,9 @@ __device__ __forceinline__ void abb_apply(const KParams<T> &p, int slot, T rn, c
 // rewritten some of this node's populations, so the node's state is rebuilt in full -- pull, collision,
 // boundaries below `slot` in order, the lower outlet with ITS neighbour's moments at DEPTH - 1 -- instead
 // of being read off the conserved moments.  DEPTH = 0 is the kernel of plans with one outlet.
+// DEPTH = kOutletsP + chain: plans with a constant-pressure outlet, which asks for the same moments of its neighbour.
+// Outlets of both kinds count as "lower outlets"; a node in a lower pressure outlet's plane has ALL its populations
+// from that outlet, so a lower index of its own (b < slot) is not looked at twice: the rebuild walks the slots in order.
 template <typename T, class S, int LAYOUT, bool STREAM, bool MASKED, int COLL = 0, int DEPTH = 0, class P = KParams<T>>
 __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, int c2, int slot,
                                                   T &rho, T (&j)[3]) {
@@ -852,10 +879,11 @@ __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, in
       if (nd & 0x80) keep_unstreamed<T, S, 1, 0>(p, own, g);
     }
   }
-  if constexpr (DEPTH > 0) {
+  constexpr bool POUT = DEPTH >= kOutletsP;
+  if constexpr ((DEPTH & (kOutletsP - 1)) > 0) {
     bool touched = false;                      // does an outlet with a lower index rewrite this node?
     for (int t = 1; t < slot; ++t)
-      if (p.bt->kind[t] == kAbbOutlet) {
+      if (p.bt->kind[t] == kAbbOutlet || (POUT && p.bt->kind[t] == kPressureOutlet)) {
         const int ax = p.bt->mem_axis[t];
         touched = touched || (ax == 0 ? c0 : (ax == 1 ? c1 : c2)) == p.bt->plane[t];
       }
@@ -870,13 +898,15 @@ __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, in
       }
       for (int t = 1; t < slot; ++t) {
         const int kind = p.bt->kind[t];
-        if (kind == kAbbOutlet) {
+        if (kind == kAbbOutlet || (POUT && kind == kPressureOutlet)) {
           const int ax = p.bt->mem_axis[t], nbr = p.bt->nbr[t];
           if ((ax == 0 ? c0 : (ax == 1 ? c1 : c2)) == p.bt->plane[t]) {
             T rn, jn[3];
             neighbour_moments<T, S, LAYOUT, STREAM, MASKED, COLL, DEPTH - 1>(
                 p, ax == 0 ? nbr : c0, ax == 1 ? nbr : c1, ax == 2 ? nbr : c2, t, rn, jn);
-            abb_apply<T, S, LAYOUT, 1, 0>(p, t, rn, jn, g);
+            // (one call for both kinds: the chain is inlined once per level)
+            if (POUT && kind == kPressureOutlet) pressure_outlet_apply<T, S, LAYOUT, 1, 0>(p.bt->rho_outlet[t], rn, jn, g);
+            else abb_apply<T, S, LAYOUT, 1, 0>(p, t, rn, jn, g);
           }
         } else if (b == t) {
           if (kind == kBounceBack) {
@@ -924,16 +954,26 @@ __device__ __forceinline__ void apply_boundaries(const P &p, int b, int c0k, int
                                                  T lane_rho = T(1), const T *lane_j = nullptr) {
   for (int slot = 1; slot <= p.nb; ++slot) {
     const int kind = p.bt->kind[slot];
-    if (kind == kAbbOutlet) {
+    if (kind == kAbbOutlet || (ABBD >= kOutletsP && kind == kPressureOutlet)) {
       // applies on the whole outlet plane, whatever the node's index: the reference
       // mutates flow.f in place and the masked torch.where is then a no-op
-      // (anti_bounce_back_outlet.py:81-91, _simulation.py:186-188)
+      // (anti_bounce_back_outlet.py:81-91, _simulation.py:186-188).  The constant-pressure outlet as well, for the same
+      // reason (equilibrium_outlet_p.py:70-73): a bounce-back or inlet node of its plane has had its own boundary
+      // applied at its (lower) index and is overwritten here
       const int ax = p.bt->mem_axis[slot];
       const int coord = ax == 0 ? c0k : (ax == 1 ? c1 : c2);
       if (coord == p.bt->plane[slot]) {
         if (slot == lane_slot) {
           const T jn[3] = {lane_j[0], lane_j[1], lane_j[2]};
           abb_apply<T, S, LAYOUT, VEC, k>(p, slot, lane_rho, jn, f);
+        } else if constexpr (ABBD >= kOutletsP) {
+          // plans with a constant-pressure outlet: one gather of the neighbour serves both kinds
+          const int nbr = p.bt->nbr[slot];
+          T rn, jn[3];
+          neighbour_moments<T, S, LAYOUT, STREAM, true, COLL, ABBD>(p, ax == 0 ? nbr : c0k, ax == 1 ? nbr : c1,
+                                                                    ax == 2 ? nbr : c2, slot, rn, jn);
+          if (kind == kPressureOutlet) pressure_outlet_apply<T, S, LAYOUT, VEC, k>(p.bt->rho_outlet[slot], rn, jn, f);
+          else abb_apply<T, S, LAYOUT, VEC, k>(p, slot, rn, jn, f);
         } else {
           abb_outlet<T, S, LAYOUT, STREAM, true, VEC, k, COLL, ABBD>(p, slot, c0k, c1, c2, f);
         }
@@ -965,7 +1005,8 @@ constexpr int crossing_rank() {
   return r;
 }
 
-// ABBD: plans with ABBD + 1 anti-bounce-back outlets (neighbour_moments, DEPTH)
+// ABBD: plans with ABBD + 1 anti-bounce-back outlets (neighbour_moments, DEPTH); kOutletsP + chain: plans with a
+// constant-pressure outlet (no lane hand-over there: every such outlet gathers its neighbour)
 template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
           int TUNE = 0, bool PACK = false, int ABBD = 0, class P = KParams<T>>
 __device__ __forceinline__ void lbm_body(const P &p) {

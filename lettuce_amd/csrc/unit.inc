@@ -36,6 +36,14 @@
 //   relaxations (inst6_)  every unit: the TRT and the regularised collision (the kernels' COLL = 8 and 9) -- every
 //                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; again
 //                         objects of their own: the earlier objects stay what they were and none of these is the longest job
+//   outlets (inst7_)      every unit: the one-step kernels of plans with a constant-pressure outlet (EquilibriumOutletP;
+//                         the kernels' ABBD = kOutletsP + chain) -- every collision and every one-step variant the masked
+//                         kernels have, at the deepest chain of the layout only; objects of their own once more, so that
+//                         every plan without such an outlet launches the code it launched before.  This object: no
+//                         collision, BGK and KBC, and the entry point that passes on to the next two
+//   outlets2 (inst8_)     ... Smagorinsky, TRT and the regularised collision
+//   outlets3 (inst9_)     ... BGK and Smagorinsky with a body force -- three objects, because the chain of depth 2 inlines
+//                         the gather and the collision three times and one object per unit would be the longest job
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -43,6 +51,10 @@
 #define LT_PART_smagorinsky 4
 #define LT_PART_forced 5
 #define LT_PART_relaxations 6
+#define LT_PART_outlets 7
+#define LT_PART_outlets2 8
+#define LT_PART_outlets3 9
+#define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
 #define LT_ONE_STEP 1
@@ -62,8 +74,11 @@
 #elif LT_PART_IS(relaxations)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 1
+#elif LT_PART_IS_OUTLETS
+#define LT_ONE_STEP 1
+#define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced or relaxations"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2 or outlets3"
 #endif
 
 namespace lt {
@@ -242,6 +257,41 @@ int one_step_of(const StepArgs &a, const NameBuf *name) {
 #endif
   return kNoKernel;
 }
+
+#if LT_PART_IS_OUTLETS
+// Plans with a constant-pressure outlet, alone or beside anti-bounce-back outlets: masked kernels that apply boundaries
+// (fused and collide-only), both cache policies, the packed plane launch of the slabs.  One chain depth per layout, the
+// deepest a plan of that layout can need (api.hip, abb_depth_of): outlets on all three axes in the reference layout of a
+// 3-D unit (2), on two axes in the slab layout and in 2-D (1); two outlets on the one axis of a 1-D lattice count as depth 1
+// too (on a lattice of two nodes each outlet's neighbour lies in the other's plane).  A plan with fewer axes or one outlet
+// takes the same kernel: the chain is followed only where a lower outlet's plane holds the neighbour.
+template <int LAYOUT>
+constexpr int kOutletChain = S::D == 3 && LAYOUT == 0 ? 2 : 1;
+
+template <int C, int LAYOUT>
+int pressure_outlets_in(const StepArgs &a, const NameBuf *name) {
+  constexpr int ABBD = kOutletsP + kOutletChain<LAYOUT>;
+  if (a.abb_depth > kOutletChain<LAYOUT>) return kNoKernel;
+  if constexpr (LAYOUT == 1) {
+    if (a.mode == kFused && a.pack_lo != nullptr) return launch<1, C, kFused, true, 0, true, ABBD>(a, name);
+  }
+  if (a.mode == kFused && a.tune == 0) return launch<LAYOUT, C, kFused, true, 0, false, ABBD>(a, name);
+  if (a.mode == kFused && a.tune == 3) return launch<LAYOUT, C, kFused, true, 3, false, ABBD>(a, name);
+  if (a.mode == kCollideOnly && a.tune == 0) return launch<LAYOUT, C, kCollideOnly, true, 0, false, ABBD>(a, name);
+  if (a.mode == kCollideOnly && a.tune == 3) return launch<LAYOUT, C, kCollideOnly, true, 3, false, ABBD>(a, name);
+  return kNoKernel;
+}
+
+template <int C>
+int pressure_outlets_of(const StepArgs &a, const NameBuf *name) {
+  if (!a.masked) return kNoKernel;
+  if (a.layout == 0) return pressure_outlets_in<C, 0>(a, name);
+#if LT_IS_3D
+  if (a.layout == 1) return pressure_outlets_in<C, 1>(a, name);
+#endif
+  return kNoKernel;
+}
+#endif
 
 #endif  // LT_ONE_STEP
 
@@ -469,6 +519,8 @@ int twice_3d(const StepArgs &a, const NameBuf *name) {
 
 int dispatch(const StepArgs &a, const NameBuf *name) {
   const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
+  // a constant-pressure outlet: part outlets has the kernels that apply boundaries (streaming alone applies none)
+  if (a.n_pout > 0 && a.mode != kStreamOnly) return LT_CAT(outlets_, LT_TAG)(a, name);
   if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
   if (coll == 8 || coll == 9) return LT_CAT(relax_, LT_TAG)(a, name);   // TRT, regularised: part relaxations
   if (a.mode == kFusedMany) {
@@ -637,6 +689,34 @@ int LT_CAT(relax_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
   if (a.coll == 8) return one_step_of<8>(a, name);
   if (a.coll == 9) return one_step_of<9>(a, name);
+  return kNoKernel;
+}
+#elif LT_PART_IS(outlets)
+// one-step kernels only: no many-step, 2-D, masked two-step or slab two-step launch takes this boundary
+int LT_CAT(outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
+  switch (a.coll) {
+    case 0: return pressure_outlets_of<0>(a, name);
+    case 1: return pressure_outlets_of<1>(a, name);
+#if LT_HAS_KBC
+    case 2: return pressure_outlets_of<2>(a, name);
+#endif
+    case 3: case 8: case 9: return LT_CAT(outlets2_, LT_TAG)(a, name);
+    case 5: case 7: return LT_CAT(outlets3_, LT_TAG)(a, name);
+    default: return kNoKernel;
+  }
+}
+#elif LT_PART_IS(outlets2)
+int LT_CAT(outlets2_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.coll == 3) return pressure_outlets_of<3>(a, name);
+  if (a.coll == 8) return pressure_outlets_of<8>(a, name);
+  if (a.coll == 9) return pressure_outlets_of<9>(a, name);
+  return kNoKernel;
+}
+#elif LT_PART_IS(outlets3)
+int LT_CAT(outlets3_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.coll == 5) return pressure_outlets_of<5>(a, name);
+  if (a.coll == 7) return pressure_outlets_of<7>(a, name);
   return kNoKernel;
 }
 #endif

@@ -1,10 +1,10 @@
 """Boundary conditions on the hot path: bounce-back, equilibrium inlet (pu), anti-bounce-back
-outlet -- the three ``Obstacle.boundaries`` returns (lettuce/ext/_flows/obstacle.py:108-122).
+outlet -- the three ``Obstacle.boundaries`` returns (lettuce/ext/_flows/obstacle.py:108-122) -- and the
+constant-pressure equilibrium outlet that the Obstacle names as the alternative to the last.
 
-All three live in this one module; ``Simulation`` orders boundaries by ``str(boundary)``,
+All four live in this one module; ``Simulation`` orders boundaries by ``str(boundary)``,
 i.e. by class path, and the class names alone reproduce the reference's order
-(AntiBounceBackOutlet < BounceBackBoundary < EquilibriumBoundaryPU).
-``EquilibriumOutletP`` is out of scope (commented out in Obstacle, its test is skipped).
+(AntiBounceBackOutlet < BounceBackBoundary < EquilibriumBoundaryPU < EquilibriumOutletP).
 """
 from typing import List, Optional
 
@@ -17,7 +17,7 @@ from .._flow import Boundary
 from ..native_desc import NativeBoundary
 from ._collision import BGKCollision
 
-__all__ = ["BounceBackBoundary", "EquilibriumBoundaryPU", "AntiBounceBackOutlet"]
+__all__ = ["BounceBackBoundary", "EquilibriumBoundaryPU", "AntiBounceBackOutlet", "EquilibriumOutletP"]
 
 
 class BounceBackBoundary(Boundary):
@@ -171,3 +171,59 @@ class AntiBounceBackOutlet(Boundary):
     def native_generator(self, index: int) -> "NativeBoundary":
         return NativeBoundary("abb_outlet", index,
                               params=lambda flow: {"axis": self.axis, "side": self.side, "present": self.present})
+
+
+class EquilibriumOutletP(AntiBounceBackOutlet):
+    """Equilibrium outlet with constant pressure (lettuce/ext/_boundary/equilibrium_outlet_p.py:12-91): every
+    node of the outlet plane gets feq(rho_outlet, u of the node one plane inside).
+
+    Derived from the anti-bounce-back outlet as in the reference, which gives it the plane and neighbour indices
+    (shifted on a z-slab, ``present`` on the rank that holds the plane)."""
+
+    def __init__(self, direction: List[int], flow: "Flow", rho_outlet: float = 1.0):
+        super().__init__(direction, flow)
+        self.context = flow.context
+        # a tensor of the context's dtype: rounded to fp32 on an fp32 context, and re-read at every call
+        self.rho_outlet = self.context.convert_to_tensor(rho_outlet)
+        self._cache = None
+
+    def __call__(self, flow: "Flow"):
+        if not self.present:
+            return flow.f
+        here = tuple([slice(None)] + self.index)
+        other = tuple([slice(None)] + self.neighbor)
+        rho = flow.rho()
+        u = flow.u()
+        rho_w = self.rho_outlet * torch.ones_like(rho[here])
+        u_w = u[other]
+        # in place, as the reference does it: the whole plane is rewritten whatever the nodes' indices in
+        # no_collision_mask, and Simulation's masked torch.where afterwards changes nothing
+        feq = flow.f
+        feq[here] = flow.equilibrium(flow, rho_w[..., None], u_w[..., None])[..., 0]
+        return flow.einsum("q,q->q", [feq, torch.ones_like(flow.f)])
+
+    def make_no_streaming_mask(self, f_shape, context: "Context"):
+        # every population but those leaving through the face (e_q . direction == 1) keeps its value
+        mask = context.zero_tensor(list(f_shape), dtype=bool)
+        if self.present:
+            mask[tuple([np.setdiff1d(np.arange(f_shape[0]), self.velocities)] + self.index)] = 1
+        return mask
+
+    def make_no_collision_mask(self, shape: List[int], context: "Context"):
+        mask = context.zero_tensor(shape, dtype=torch.bool)
+        if self.present:
+            mask[tuple(self.index)] = 1
+        return mask
+
+    def native_available(self) -> bool:
+        return True
+
+    def _engine_params(self, flow):
+        # the reference multiplies by the tensor at every call: read it again when it was replaced or written to
+        key = (id(self.rho_outlet), self.rho_outlet._version)
+        if self._cache is None or self._cache[0] != key:
+            self._cache = (key, float(self.rho_outlet.detach().cpu().double()))
+        return {"axis": self.axis, "side": self.side, "present": self.present, "rho_outlet": self._cache[1]}
+
+    def native_generator(self, index: int) -> "NativeBoundary":
+        return NativeBoundary("pressure_outlet", index, params=self._engine_params)

@@ -54,7 +54,7 @@ class NativeCollision:
 
 @dataclass
 class NativeBoundary:
-    kind: str                                  # 'bounce_back' | 'equilibrium' | 'abb_outlet'
+    kind: str                                  # 'bounce_back' | 'equilibrium' | 'abb_outlet' | 'pressure_outlet'
     index: int
     # engine parameters of this boundary for a given flow (dict for lettuce_amd._native.Plan)
     params: Optional[Callable[["Flow"], dict]] = None
