@@ -533,7 +533,112 @@ def bgk_bits_cases():
 
 
 # --------------------------------------------------------------------------- #
+# asymmetric: every collision beside BGK on the states of bgk_bits (rho 0.5 .. 1.5 and 1 / 20 .. 20), and KBC on a state
+# whose gamma has both signs and is 0 / 0 on a few nodes (tests/asymmetric_states.py, which also holds the generator
+# restated with the oracle's tables: asserted equal to the one above).  float64, the smallest grids, the carrier flow of
+# bits_run.  KBC and the regularised collision take tau from the flow's units, so the carrier's Reynolds number is set
+# to the one that gives the wanted tau; the tau the reference then used is stored.
+ASYM_GRID = {"D2Q9": [8, 12], "D3Q19": [4, 4, 6], "D3Q27": [4, 4, 6]}
+ASYM_PATCH = {"D2Q9": 8, "D3Q27": 4}          # nodes at rest in the branch state (a row of the grid, less its ends)
+ASYM_SEED = {"moderate": 9400, "wide": 9401}
+ASYM_CASES = (("moderate", 0.501, (1, 5)), ("wide", 0.7, (1,)), ("wide", 1.7, (1,)))
+BRANCH_TAUS = (0.51, 1.7)
+ASYM_ACCELERATION = (2e-3, -3e-3, 1e-3)
+
+
+def tests_module(name):
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    for path in (root, os.path.join(root, "tests")):
+        if path not in sys.path:
+            sys.path.insert(0, path)
+    return __import__(name)
+
+
+def carrier_with_tau(stencil, res, tau, dt="f64"):
+    """a TaylorGreenVortex whose units give relaxation_parameter_lu = tau (to the last bit or two: stored)"""
+    ctx = lt.Context(device="cpu", dtype=DT[dt], use_native=False)
+    probe = quiet(lt.TaylorGreenVortex, ctx, list(res), 100, 0.05, stencil)
+    re = 100 * (probe.units.relaxation_parameter_lu - 0.5) / (tau - 0.5)
+    flow = quiet(lt.TaylorGreenVortex, ctx, list(res), re, 0.05, stencil)
+    assert abs(flow.units.relaxation_parameter_lu - tau) < 1e-13
+    return flow
+
+
+def asym_collision(op, flow, tau):
+    d = flow.stencil.d
+    if op == "kbc":
+        return lt.KBCCollision()
+    if op.startswith("smagorinsky"):
+        return lt.SmagorinskyCollision(tau, {"smagorinsky_default": 0.17, "smagorinsky_strong": 1.0}[op])
+    if op == "trt":
+        return lt.TRTCollision(tau, 0.5 + (3.0 / 16.0) / (tau - 0.5))
+    if op == "regularized":
+        return lt.RegularizedCollision()
+    force = {"guo": lt.Guo, "shanchen": lt.ShanChen}[op](flow, tau, list(ASYM_ACCELERATION[:d]))
+    return lt.BGKCollision(tau, force=force)
+
+
+def asym_run(stencil, res, op, f0, tau, snapshots):
+    """(tau the reference used, the reference's collision of f0, {n: f after n steps})"""
+    torch.set_num_threads(1)
+    flow = carrier_with_tau(stencil, res, tau)
+    used = float(flow.units.relaxation_parameter_lu) if op in ("kbc", "regularized") else tau
+    flow.f = f0.clone()
+    collided = npy(asym_collision(op, flow, tau)(flow))
+    flow.f = f0.clone()
+    sim = quiet(lt.Simulation, flow, asym_collision(op, flow, tau), [])
+    out = {}
+    for i in range(1, max(snapshots) + 1):
+        quiet(sim, 1)
+        if i in snapshots:
+            out[i] = npy(flow.f)
+            assert np.isfinite(out[i]).all(), (op, tau, i)
+    torch.set_num_threads(8)
+    return used, collided, out
+
+
+def asymmetric_cases():
+    states = tests_module("asymmetric_states")
+    for sname, res in ASYM_GRID.items():
+        stencil = getattr(lt, sname)()
+        f0 = {}
+        for kind, seed in ASYM_SEED.items():
+            f0[kind] = asymmetric_state(stencil, res, kind, seed)
+            assert torch.equal(f0[kind], states.asymmetric_state(sname, res, kind, seed))
+        arrays = {"resolution": np.array(res), "seed_moderate": np.array(ASYM_SEED["moderate"]),
+                  "seed_wide": np.array(ASYM_SEED["wide"]), "f0_moderate": npy(f0["moderate"]), "f0_wide": npy(f0["wide"])}
+        if sname in ASYM_PATCH:
+            f0["branch"] = states.branch_case(sname, tuple(res), "f64", ASYM_PATCH[sname])
+            arrays["f0_branch"] = npy(f0["branch"])
+            arrays["patch_nodes"] = np.array(ASYM_PATCH[sname])
+        save(f"asymmetric_states_{sname.lower()}_f64", **arrays)
+        operators = ["smagorinsky_default", "smagorinsky_strong", "trt", "regularized", "guo", "shanchen"]
+        if sname in ASYM_PATCH:
+            operators.insert(0, "kbc")
+        for op in operators:
+            name = f"asymmetric_{op}_{sname.lower()}_f64"
+            if not wanted(name):
+                continue
+            out = {"acceleration": np.array(ASYM_ACCELERATION[:stencil.d])}
+            for kind, tau, snapshots in ASYM_CASES:
+                used, collided, snaps = asym_run(stencil, res, op, f0[kind], tau, snapshots)
+                out[f"{kind}_tau{tau}_tau_used"] = np.float64(used)
+                out[f"{kind}_tau{tau}_collided"] = collided
+                for n, f in snaps.items():
+                    out[f"{kind}_tau{tau}_f{n}"] = f
+            if op == "kbc":
+                for tau in BRANCH_TAUS:
+                    used, collided, snaps = asym_run(stencil, res, op, f0["branch"], tau, (1,))
+                    out[f"branch_tau{tau}_tau_used"] = np.float64(used)
+                    out[f"branch_tau{tau}_collided"] = collided
+                    out[f"branch_tau{tau}_f1"] = snaps[1]
+            save(name, **out)
+
+
+# --------------------------------------------------------------------------- #
 if __name__ == "__main__":
+    if not ONLY or any("asymmetric" in k or k in "asymmetric" for k in ONLY):
+        asymmetric_cases()
     if not ONLY or any("bgk_bits" in k or k in "bgk_bits" for k in ONLY):
         bgk_bits_cases()
     # cfg1 (examples/00_simplest_TGV.py): 128^2 fp64; keep only energies + a 100-step f

@@ -281,3 +281,15 @@ def test_a_body_force_drives_the_parabolic_channel_profile():
     assert err < 5e-3
     at_rest, _ = channel(ctx(), force_class=None, steps=50)
     assert parabola_error(at_rest, applied=False) == pytest.approx(1.0, abs=1e-12)
+
+
+# --------------------------------------------------------------------------- densities far from 1
+@pytest.mark.parametrize("lat", ["D2Q9", "D3Q19", "D3Q27"])
+@pytest.mark.parametrize("scheme", ["guo", "shanchen"])
+def test_mirror_on_the_asymmetric_states_against_the_reference(scheme, lat):
+    """rho in 0.5 .. 1.5 at tau = 0.501 (1 and 5 steps) and in 1 / 20 .. 20 at tau = 0.7 and 1.7 (tests/golden/asymmetric_*,
+    oracle/gen_golden.py): the CPU path the engine tests of these states compare with"""
+    from test_gpu_asymmetric_operators import _op, fixture_runs
+    for what, got, want in fixture_runs(_op(f"{scheme}-bgk", "force", lat, scheme=scheme, operator="bgk"), scheme):
+        print(what, end=": ")
+        close(got, want, "f64")

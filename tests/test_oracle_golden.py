@@ -369,3 +369,54 @@ def test_the_reference_vectors_are_the_kernels_arithmetic_but_for_rho_in_the_tai
         m = golden(f"bgk_bits_many_d2q9_{dt}")
         for n in (4, 5, 10):
             np.testing.assert_array_equal(bgk_arithmetic.steps(m["f0"], lat, float(m["tau"]), n, None), m[f"f{n}"])
+
+
+# --------------------------------------------------------------------------- KBC away from rho = 1 and on its stabiliser
+@pytest.mark.parametrize("lat", ["D2Q9", "D3Q27"])
+def test_kbc_on_the_asymmetric_states(lat):
+    """rho in 0.5 .. 1.5 at tau = 0.501 (1 and 5 steps) and in 1 / 20 .. 20 at tau = 0.7 and 1.7"""
+    import asymmetric_states as st
+    g, s = golden(f"asymmetric_kbc_{lat.lower()}_f64"), golden(f"asymmetric_states_{lat.lower()}_f64")
+    res = [int(r) for r in s["resolution"]]
+    L = orc.LATTICES[lat]
+    for kind, tau, steps in (("moderate", 0.501, (1, 5)), ("wide", 0.7, (1,)), ("wide", 1.7, (1,))):
+        f0 = st.asymmetric_state(lat, res, kind, int(s[f"seed_{kind}"]))
+        assert f0.numpy().tobytes() == s[f"f0_{kind}"].tobytes()
+        key = f"{kind}_tau{tau}"
+        sim = orc.OracleSimulation(L, f0.clone(), "kbc", float(g[key + "_tau_used"]))
+        close(sim._collision(sim.f), g[key + "_collided"], "f64")
+        done = 0
+        for n in steps:
+            sim.step(n - done)
+            done = n
+            close(sim.f, g[f"{key}_f{n}"], "f64")
+
+
+@pytest.mark.parametrize("tau", [0.51, 1.7])
+@pytest.mark.parametrize("lat", ["D2Q9", "D3Q27"])
+def test_kbc_stabiliser_lines_against_the_reference(lat, tau):
+    """The branch state (asymmetric_states.py): gamma of both signs, and nodes at rest with 0 / 0.  The oracle takes
+    `gamma < 1e-15 -> 2` and `isnan -> 2` where the reference does -- on D3Q27 too, where no other vector reaches either
+    line -- on every node outside the excluded set (empty on these grids), nodes with sum_h == 0 included."""
+    import asymmetric_states as st
+    g, s = golden(f"asymmetric_kbc_{lat.lower()}_f64"), golden(f"asymmetric_states_{lat.lower()}_f64")
+    res, count = tuple(int(r) for r in s["resolution"]), int(s["patch_nodes"])
+    f0 = st.branch_case(lat, res, "f64", count)
+    assert f0.numpy().tobytes() == s["f0_branch"].tobytes()
+    ref = st.branch_reference(lat, res, tau, count)
+    keep = ~ref["excluded"].numpy()
+    gamma, sum_h = st.kbc_gamma(f0, tau)
+    taken = st.stabilised(gamma).numpy()
+    assert (taken & keep & (sum_h != 0).numpy()).sum() >= 2 and (sum_h == 0).sum() == count and keep.all()
+    sim = orc.OracleSimulation(orc.LATTICES[lat], f0.clone(), "kbc", float(g[f"branch_tau{tau}_tau_used"]))
+    collided = sim._collision(sim.f).numpy()
+    close(collided[:, keep], g[f"branch_tau{tau}_collided"][:, keep], "f64")
+    assert (collided[:, (sum_h == 0).numpy()] == f0.numpy()[:, (sum_h == 0).numpy()]).all()
+    # without the first line the oracle would be far off on the stabilised nodes
+    e, w = orc.lattice_tensors(orc.LATTICES[lat], torch.float64)
+    feq = orc.quadratic_equilibrium(orc.density(f0), orc.velocity(f0, e), e, w)
+    ds = orc._kbc_shear_part(f0, e) - orc._kbc_shear_part(feq, e)
+    raw = (f0 - 1. / (2 * tau) * (2 * ds + gamma * (f0 - feq - ds))).numpy()
+    nodes = taken & (sum_h != 0).numpy()
+    assert np.abs(raw - g[f"branch_tau{tau}_collided"])[:, nodes].max() > 1e-4
+    close(sim.step(1), g[f"branch_tau{tau}_f1"], "f64")

@@ -244,3 +244,15 @@ def test_slab_driver_refuses_an_engine_without_set_trt():
     flow = lt.TaylorGreenVortex(context, slab.extended_resolution, 100, 0.05, lt.D3Q19(), slab=slab)
     with pytest.raises(lt.LettuceException, match="has no trt collision"):
         lt.SlabSimulation(flow, lt.TRTCollision(0.8, 1.1), slab, engine=Engine())
+
+
+# --------------------------------------------------------------------------- densities far from 1
+@pytest.mark.parametrize("lat", ["D2Q9", "D3Q19", "D3Q27"])
+@pytest.mark.parametrize("operator", ["trt", "regularized"])
+def test_mirror_on_the_asymmetric_states_against_the_reference(operator, lat):
+    """rho in 0.5 .. 1.5 at tau = 0.501 (1 and 5 steps) and in 1 / 20 .. 20 at tau = 0.7 and 1.7 (tests/golden/asymmetric_*,
+    oracle/gen_golden.py): the CPU path the engine tests of these states compare with"""
+    from test_gpu_asymmetric_operators import _op, fixture_runs
+    for what, got, want in fixture_runs(_op(operator, "relaxation", lat, operator=operator), operator):
+        print(what, end=": ")
+        close(got, want, "f64")

@@ -173,3 +173,16 @@ def test_native_context_refuses_a_force_or_another_iteration_count():
     once.iterations = 1
     with pytest.raises(NativeEngineError, match="SmagorinskyCollision"):
         lt.Simulation(flow, once, [])
+
+
+# --------------------------------------------------------------------------- densities far from 1
+@pytest.mark.parametrize("lat", ["D2Q9", "D3Q19", "D3Q27"])
+@pytest.mark.parametrize("kind,constant", [("default", 0.17), ("strong", 1.0)])
+def test_mirror_on_the_asymmetric_states_against_the_reference(kind, constant, lat):
+    """rho in 0.5 .. 1.5 at tau = 0.501 (1 and 5 steps) and in 1 / 20 .. 20 at tau = 0.7 and 1.7 (tests/golden/asymmetric_*,
+    oracle/gen_golden.py): the CPU path the engine tests of these states compare with"""
+    from test_gpu_asymmetric_operators import _op, fixture_runs
+    op = _op(f"smagorinsky-{kind}", "smagorinsky", lat, constant=constant)
+    for what, got, want in fixture_runs(op, f"smagorinsky_{kind}"):
+        print(what, end=": ")
+        close(got, want, "f64")
