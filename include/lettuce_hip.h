@@ -61,12 +61,15 @@ enum lt_stencil { LT_D2Q9 = 0, LT_D3Q19 = 1, LT_D3Q27 = 2, LT_D1Q3 = 3, LT_D3Q15
 enum lt_dtype { LT_F32 = 0, LT_F64 = 1 };
 /* lettuce/ext/_collision/no_collision.py:9-17, bgk_collision.py:12-35, kbc_collision.py:11-166,
  * smagorinsky_collision.py:7-36 (every stencil; the constant: lt_plan_set_smagorinsky), trt_collision.py:6-27 (every
- * stencil; `tau` is tau_plus, tau_minus: lt_plan_set_trt), regularized_collision.py:8-44 (every stencil).  4-7 are not
+ * stencil; `tau` is tau_plus, tau_minus: lt_plan_set_trt), regularized_collision.py:8-44 (every stencil),
+ * mrt_collision.py:6-33 (D2Q9 and D3Q27; transform and rates: lt_plan_set_mrt).  4-7 are not
  * collisions: inside the library a body force adds 4 to the plan's value (lt_plan_set_force) */
 enum lt_collision {
   LT_COLLISION_NONE = 0, LT_COLLISION_BGK = 1, LT_COLLISION_KBC = 2, LT_COLLISION_SMAGORINSKY = 3,
-  LT_COLLISION_TRT = 8, LT_COLLISION_REGULARIZED = 9
+  LT_COLLISION_TRT = 8, LT_COLLISION_REGULARIZED = 9, LT_COLLISION_MRT = 10
 };
+/* the moment transforms of an MRT plan (lettuce/util/moments.py:147-274, 369-579): those with an equilibrium of their own */
+enum lt_mrt_transform { LT_MRT_D2Q9_DELLAR = 1, LT_MRT_D2Q9_LALLEMAND = 2, LT_MRT_D3Q27_HERMITE = 3 };
 /* lettuce/ext/_boundary/bounce_back_boundary.py:10-32, equilibrium_boundary_pu.py:13-46,
  * anti_bounce_back_outlet.py:13-109 */
 enum lt_boundary_kind {
@@ -434,6 +437,20 @@ int lt_plan_set_smagorinsky(lt_plan *plan, double constant);
  * lt_resident_advance keep the one-step kernel; the explicit multi-step entry points and lt_plan_two_step_admitted
  * return LT_ERR_UNSUPPORTED with a reason that names the collision. */
 int lt_plan_set_trt(lt_plan *plan, double tau_minus);
+/* Transform and relaxation rates of a plan with LT_COLLISION_MRT: m = M f, m_i <- m_i - (1 / relaxation[i]) (m_i -
+ * meq_i(m)), f = M^-1 m, with M and meq of `transform` (lt_mrt_transform) and `count` = q rates in the order of the
+ * transform's moments.  The plan rounds each rate to its scalar type and forms the reciprocal there, as the reference
+ * does on every call (mrt_collision.py:18-24); the rates of the conserved moments (rho, j) are checked and not used.
+ * Read at every launch, so both may change between calls.  The `tau` argument of lt_run, lt_collide and the other entry
+ * points is NOT read by an MRT plan.  LT_ERR_INVALID (plan unchanged) on a plan of another collision, for a transform
+ * of the other lattice, count != q, a null pointer and a rate that is not finite and > 0; a run or collide of an MRT
+ * plan before the first successful call returns LT_ERR_INVALID as well.  lt_plan_create answers LT_ERR_UNSUPPORTED for
+ * LT_COLLISION_MRT on a lattice other than D2Q9 / D3Q27.  MRT has every one-step kernel BGK has (masks, both layouts,
+ * packed plane launches, up to three outlets, the constant-pressure outlet), no body force and no launch of several
+ * steps: lt_run, lt_continue and lt_resident_advance keep one update per launch, lt_plan_set_two_step(plan, 1, ...),
+ * the explicit multi-step entry points and lt_plan_two_step_admitted return LT_ERR_UNSUPPORTED with a reason that
+ * names the collision. */
+int lt_plan_set_mrt(lt_plan *plan, int transform, const double *relaxation, int count);
 /* A uniform body force on a plan with LT_COLLISION_BGK or LT_COLLISION_SMAGORINSKY.  acceleration: `dims` values in
  * lattice units, logical order x, y, z.  A colliding node (no_collision_mask == 0) then does
  *   u*   = j / rho + (ueq_scale * a) / rho

@@ -33,6 +33,10 @@ COLLISION_IDS = {"none": 0, "bgk": 1, "kbc": 2, "smagorinsky": 3}
 # the collisions behind them in lt_collision (4-7 are not collisions: a body force adds 4 inside the library); a mapping
 # of its own, which Plan consults next to COLLISION_IDS
 MORE_COLLISION_IDS = {"trt": 8, "regularized": 9}
+# ... and MRT behind those, again a mapping of its own: the two above stay what they were
+MRT_COLLISION_IDS = {"mrt": 10}
+# lt_mrt_transform, by the class name of the moment transform (lettuce_amd/moments.py)
+MRT_TRANSFORM_IDS = {"D2Q9Dellar": 1, "D2Q9Lallemand": 2, "D3Q27Hermite": 3}
 BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3, "pressure_outlet": 4}
 LAYOUT_REFERENCE, LAYOUT_SLAB = 0, 1
 
@@ -103,6 +107,7 @@ SYMBOLS = {
     "lt_plan_set_two_step": (ctypes.c_int, [_vp, _i32, _i32]),
     "lt_plan_set_smagorinsky": (ctypes.c_int, [_vp, _dbl]),
     "lt_plan_set_trt": (ctypes.c_int, [_vp, _dbl]),
+    "lt_plan_set_mrt": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(ctypes.c_double), _i32]),
     "lt_plan_set_force": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _dbl, _dbl]),
     "lt_stream_collide_twice_planes": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp]),
     "lt_stream_collide_twice_planes_packed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp, _vp, _vp]),
@@ -252,7 +257,8 @@ class Plan:
                                     f"(available: {sorted(STENCIL_IDS)})")
         if dtype not in DTYPE_IDS:
             raise NativeEngineError(f"dtype {dtype} has no HIP kernels (float32/float64 only)")
-        if collision not in COLLISION_IDS and collision not in MORE_COLLISION_IDS:
+        ids = {**COLLISION_IDS, **MORE_COLLISION_IDS, **MRT_COLLISION_IDS}
+        if collision not in ids:
             raise NativeEngineError(f"collision {collision!r} has no HIP kernels")
         if len(boundaries) > LT_MAX_BOUNDARIES:
             raise NativeEngineError(f"{len(boundaries)} boundaries; the engine takes "
@@ -273,7 +279,7 @@ class Plan:
         desc.abi_version = LT_ABI_VERSION
         desc.stencil = STENCIL_IDS[stencil]
         desc.dtype = DTYPE_IDS[dtype]
-        desc.collision = COLLISION_IDS[collision] if collision in COLLISION_IDS else MORE_COLLISION_IDS[collision]
+        desc.collision = ids[collision]
         desc.layout = layout
         desc.ghost_planes = ghost_planes
         desc.dims = self.d
@@ -733,6 +739,17 @@ class Plan:
     def set_trt(self, tau_minus: float = 1.0):
         """tau_minus of a TRT plan (lt_plan_set_trt): read at every launch, so it may change between calls like tau"""
         self._check(self.lib.lt_plan_set_trt(self._handle, float(tau_minus)))
+
+    def set_mrt(self, transform_name: str, rates):
+        """Transform (the class name of one of the three engine transforms of lettuce_amd/moments.py) and the q
+        relaxation rates of an MRT plan (lt_plan_set_mrt): read at every launch, so both may change between calls; the
+        ``tau`` of the calls is not read."""
+        if transform_name not in MRT_TRANSFORM_IDS:
+            raise NativeEngineError(f"moment transform {transform_name!r} has no HIP kernels "
+                                    f"(available: {sorted(MRT_TRANSFORM_IDS)})")
+        values = [float(s) for s in rates]
+        array = (ctypes.c_double * max(1, len(values)))(*values)
+        self._check(self.lib.lt_plan_set_mrt(self._handle, MRT_TRANSFORM_IDS[transform_name], array, len(values)))
 
     def set_force(self, acceleration=None, ueq_scale: float = 0.5, source_scale: float = 0.0):
         """A uniform body force on a BGK / Smagorinsky plan, read at every launch like tau: ``acceleration`` in lattice

@@ -203,6 +203,11 @@ class _NativeStepper:
             tau_minus = float(self.collision.tau_minus(flow))
             self.plan.set_trt(tau_minus)
             key = (tau, tau_minus)
+        if self.collision.rates is not None:
+            # MRT: the rates are re-read per batch (one copy from the device) and handed to the plan with the transform
+            rates = tuple(self.collision.rates(flow))
+            self.plan.set_mrt(self.collision.transform, rates)
+            key = (tau, self.collision.transform, rates)
         if self.collision.force is not None:
             # a body force: acceleration and scales are re-read per batch too; a changed force starts from flow.f
             force = self.collision.force.plan_args()

@@ -440,6 +440,7 @@ class SlabSimulation:
         self._constant = desc.constant      # Smagorinsky: re-read per batch like tau (else None)
         self._tau_minus = desc.tau_minus    # TRT: re-read per batch like tau (else None)
         self._force = desc.force            # body force: re-read per batch as well (else None)
+        self._mrt = (desc.transform, desc.rates) if desc.rates is not None else None   # MRT: the rates likewise
         # boundaries: same ordering and masks as Simulation (built on the extended slab, then cut
         # to this rank's planes + one ghost plane per side and laid out z-slowest)
         from ._simulation import build_masks
@@ -476,6 +477,10 @@ class SlabSimulation:
             raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
         if self._tau_minus is not None and not hasattr(engine, "set_trt"):
             raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
+        if self._mrt is not None:
+            if not hasattr(engine, "set_mrt"):
+                raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
+            engine.set_mrt(self._mrt[0], self._mrt[1](self.flow))     # now: the two-step driver asks the engine below
         if self._force is not None:
             if not hasattr(engine, "set_force"):
                 raise LettuceException(f"engine {type(engine).__name__} has no body force")
@@ -730,6 +735,8 @@ class SlabSimulation:
             self.engine.set_smagorinsky(float(self._constant(self.flow)))
         if self._tau_minus is not None:
             self.engine.set_trt(float(self._tau_minus(self.flow)))
+        if self._mrt is not None:
+            self.engine.set_mrt(self._mrt[0], self._mrt[1](self.flow))
         if self._force is not None:
             self.engine.set_force(*self._force.plan_args())
         cur, nxt, carried = self._start_batch(tau)

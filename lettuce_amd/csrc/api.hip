@@ -132,6 +132,14 @@ struct lt_plan {
   int n_cu = 0;              // compute units of the plan's device
   double smagorinsky = 0.17; // Smagorinsky constant (lt_plan_set_smagorinsky); the reference's default
   double tau_minus = 1.0;    // TRT: relaxation time of the antisymmetric part (lt_plan_set_trt); the reference's default
+  // MRT (lt_plan_set_mrt): the transform (lt_mrt_transform; 0 = not set yet) and the relaxation rates of its q moments
+  struct Mrt {
+    int transform = 0;
+    double rates[27] = {};
+    bool operator==(const Mrt &o) const {
+      return transform == o.transform && std::equal(rates, rates + 27, o.rates);
+    }
+  } mrt;
   // uniform body force (lt_plan_set_force): read at every launch like tau.  forced: the kernels with COLL = 4 + collision
   struct Force {
     bool on = false;
@@ -194,7 +202,7 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau, smagorinsky, tau_minus; int masked, tune, shift, residency; Force force; } gkey = {};
+  struct { void *a, *b; double tau, smagorinsky, tau_minus; int masked, tune, shift, residency; Force force; Mrt mrt; } gkey = {};
 };
 
 namespace {
@@ -527,7 +535,11 @@ int masked_two_step_axis(const lt_plan *p) {
 bool masked_two_step_ok(const lt_plan *p) { return masked_two_step_axis(p) >= 0; }
 bool canary_ok(lt_plan *p);
 // the kernels' COLL of the plan: its collision, + 4 with a body force
-int kernel_coll(const lt_plan *p) { return p->desc.collision | (p->force.on ? 4 : 0); }
+// (MRT: 10, and 11 with Lallemand's transform -- Dellar and Hermite are told apart by the lattice)
+int kernel_coll(const lt_plan *p) {
+  if (p->desc.collision == LT_COLLISION_MRT) return p->mrt.transform == LT_MRT_D2Q9_LALLEMAND ? 11 : 10;
+  return p->desc.collision | (p->force.on ? 4 : 0);
+}
 const char *const kForceMultiStep = "a body force (lt_plan_set_force) has the one-step kernels and the plain two-step sweep "
                                     "of periodic D3Q19 fp32 plans without masks only: no many-step, 2-D, masked, role-wave "
                                     "or slab two-step kernel takes it";
@@ -565,6 +577,13 @@ const char *relaxation_refuses(const lt_plan *p, int mode) {
                "plans without masks only: no many-step, 2-D, masked, role-wave, edge, packed or signalling two-step "
                "kernel takes it";
 }
+// MRT: the one-step kernels only (unit.inc, part mrt)
+const char *const kMrtMultiStep = "the MRT collision has the one-step kernels only: no two-step, many-step or "
+                                  "two-ghost-plane slab kernel takes it";
+const char *mrt_refuses(const lt_plan *p, int mode) {
+  return p->desc.collision == LT_COLLISION_MRT && (mode == lt::kFusedMany || mode == lt::kFusedTwice) ? kMrtMultiStep
+                                                                                                      : nullptr;
+}
 const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
                                       "edge, packed or signalling launches): slabs keep the one-step kernels";
 
@@ -594,6 +613,11 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
     return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
   if (const char *why = pressure_outlet_refuses(p, mode))
     return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
+  if (const char *why = mrt_refuses(p, mode))
+    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
+  const bool mrt = p->desc.collision == LT_COLLISION_MRT;
+  if (mrt && mode != lt::kStreamOnly && p->mrt.transform == 0)
+    return fail(LT_ERR_INVALID, "the plan's collision is MRT: lt_plan_set_mrt must give the transform and the rates first");
   if (mode == lt::kFusedMany && (p->desc.ghost_planes || (p->masked && p->n_abb > 1)))
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: no slabs, at most one anti-bounce-back outlet");
   if (mode == lt::kFusedTwice) {
@@ -615,7 +639,7 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   }
   if (p->desc.n_boundaries > 0 && !p->masked)
     return fail(LT_ERR_INVALID, "plan has boundaries but lt_plan_set_masks was not called");
-  if (mode != lt::kStreamOnly && p->desc.collision != LT_COLLISION_NONE && !(tau > 0.0))
+  if (mode != lt::kStreamOnly && p->desc.collision != LT_COLLISION_NONE && !mrt && !(tau > 0.0))
     return fail(LT_ERR_INVALID, "relaxation time tau = %g", tau);
   lt::StepArgs a;
   memset(&a, 0, sizeof a);
@@ -626,6 +650,8 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   a.tau = tau > 0.0 ? tau : 1.0;
   a.smagorinsky = p->smagorinsky;
   a.tau_minus = p->tau_minus;
+  a.mrt_transform = p->mrt.transform;
+  std::copy(p->mrt.rates, p->mrt.rates + 27, a.mrt_rates);
   a.accel[0] = p->force.a[0]; a.accel[1] = p->force.a[1]; a.accel[2] = p->force.a[2];
   a.ueq_scale = p->force.ueq_scale; a.source_scale = p->force.source_scale;
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
@@ -692,7 +718,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
   }
   const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.smagorinsky == p->smagorinsky &&
                     p->gkey.tau_minus == p->tau_minus &&
-                    p->gkey.force == p->force &&
+                    p->gkey.force == p->force && p->gkey.mrt == p->mrt &&
                     p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
                     p->gkey.shift == p->shift;
   if (!same) {
@@ -712,7 +738,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->smagorinsky, p->tau_minus, p->masked, p->tune, p->shift, p->residency, p->force};
+    p->gkey = {cur, other, tau, p->smagorinsky, p->tau_minus, p->masked, p->tune, p->shift, p->residency, p->force, p->mrt};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -742,6 +768,10 @@ bool two_step_possible(lt_plan *p, const char **why) {
     return false;
   }
   if (const char *refused = pressure_outlet_refuses(p, lt::kFusedTwice)) {
+    *why = refused;
+    return false;
+  }
+  if (const char *refused = mrt_refuses(p, lt::kFusedTwice)) {
     *why = refused;
     return false;
   }
@@ -803,6 +833,8 @@ bool two_step_wanted(lt_plan *p) {
   if (p->force.on) return false;
   // TRT, regularised: never automatic either, for the same reason
   if (is_relaxation(p)) return false;
+  // MRT has no two-step kernel
+  if (p->desc.collision == LT_COLLISION_MRT) return false;
   // (Smagorinsky, D3Q19 fp32: bit-identical to two one-step launches and 0.279-0.309 against 0.409-0.475 ms per
   // update at 256^3, every sample below every sample of the one-step pair: automatic like BGK)
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
@@ -936,7 +968,9 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->mas
 // 2-D kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
 // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
-  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on || is_relaxation(p) || p->n_pout > 0) return false;
+  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on || is_relaxation(p) || p->n_pout > 0 ||
+      p->desc.collision == LT_COLLISION_MRT)
+    return false;
   if (p->masked && p->n_abb > 1) return false;
   if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
   lt::StepArgs a;
@@ -1134,12 +1168,14 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   if (d->stencil < 0 || d->stencil > 4) return fail(LT_ERR_UNSUPPORTED, "stencil %d", d->stencil);
   if (d->dtype < 0 || d->dtype > 1) return fail(LT_ERR_UNSUPPORTED, "dtype %d (fp32/fp64 only)", d->dtype);
   if ((d->collision < 0 || d->collision > LT_COLLISION_SMAGORINSKY) && d->collision != LT_COLLISION_TRT &&
-      d->collision != LT_COLLISION_REGULARIZED)
+      d->collision != LT_COLLISION_REGULARIZED && d->collision != LT_COLLISION_MRT)
     return fail(LT_ERR_UNSUPPORTED, "collision %d", d->collision);
   const Unit unit = kUnits[2 * d->stencil + d->dtype];
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   if (d->collision == LT_COLLISION_KBC && d->stencil != LT_D2Q9 && d->stencil != LT_D3Q27)
     return fail(LT_ERR_UNSUPPORTED, "KBC collision exists for D2Q9 and D3Q27 only");
+  if (d->collision == LT_COLLISION_MRT && d->stencil != LT_D2Q9 && d->stencil != LT_D3Q27)
+    return fail(LT_ERR_UNSUPPORTED, "MRT collision exists for D2Q9 (Dellar, Lallemand) and D3Q27 (Hermite) only");
   if (d->layout != LT_LAYOUT_REFERENCE && d->layout != LT_LAYOUT_SLAB)
     return fail(LT_ERR_INVALID, "layout %d", d->layout);
   if (d->layout == LT_LAYOUT_SLAB && unit.d != 3) return fail(LT_ERR_UNSUPPORTED, "slab layout is 3-D only");
@@ -1811,6 +1847,27 @@ int lt_plan_set_trt(lt_plan *p, double tau_minus) {
   return LT_OK;
 }
 
+int lt_plan_set_mrt(lt_plan *p, int transform, const double *relaxation, int count) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (p->desc.collision != LT_COLLISION_MRT)
+    return fail(LT_ERR_INVALID, "the plan's collision is %d, not MRT", p->desc.collision);
+  if (transform != LT_MRT_D2Q9_DELLAR && transform != LT_MRT_D2Q9_LALLEMAND && transform != LT_MRT_D3Q27_HERMITE)
+    return fail(LT_ERR_INVALID, "MRT transform %d (1 Dellar, 2 Lallemand, 3 Hermite)", transform);
+  if ((transform == LT_MRT_D3Q27_HERMITE) != (p->desc.stencil == LT_D3Q27))
+    return fail(LT_ERR_INVALID, "MRT transform %d belongs to %s, the plan's lattice has %d velocities", transform,
+                transform == LT_MRT_D3Q27_HERMITE ? "D3Q27" : "D2Q9", p->unit.q);
+  if (!relaxation) return fail(LT_ERR_INVALID, "null relaxation rates");
+  if (count != p->unit.q)
+    return fail(LT_ERR_INVALID, "%d relaxation rates, the transform has %d moments", count, p->unit.q);
+  for (int i = 0; i < count; ++i)
+    if (!(relaxation[i] > 0.0) || !std::isfinite(relaxation[i]))
+      return fail(LT_ERR_INVALID, "MRT relaxation rate %d = %g (finite and > 0)", i, relaxation[i]);
+  p->mrt.transform = transform;
+  std::fill(p->mrt.rates, p->mrt.rates + 27, 0.0);
+  std::copy(relaxation, relaxation + count, p->mrt.rates);
+  return LT_OK;
+}
+
 int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, double source_scale) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (p->desc.collision != LT_COLLISION_BGK && p->desc.collision != LT_COLLISION_SMAGORINSKY)
@@ -1833,6 +1890,7 @@ int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, 
 int lt_plan_set_two_step(lt_plan *p, int32_t mode, int32_t planes_per_workgroup) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "two-step mode %d", mode);
+  if (mode == 1 && p->desc.collision == LT_COLLISION_MRT) return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kMrtMultiStep);
   const int sweep = p->unit.d == 2 ? p->n1 : p->n2;          // extent of the sweep axis
   if (planes_per_workgroup < 0 ||
       (planes_per_workgroup > 0 && !p->desc.ghost_planes && sweep % planes_per_workgroup != 0))

@@ -28,7 +28,8 @@ struct StepArgs {
   const unsigned *nsm_bits;
   const void *bt;        // BoundaryTable<T>* (device)
   int nb;
-  int layout, coll, mode, masked, shift, tune;   // coll: lt_collision (0-3, 8, 9), + 4 with a body force (the kernels' COLL)
+  int layout, coll, mode, masked, shift, tune;   // coll: lt_collision (0-3, 8, 9), + 4 with a body force; MRT: 10, or 11
+                                                 // with Lallemand's transform (the kernels' COLL)
   int strip;             // kFusedTwice on 2-D lattices: columns per workgroup (512 / 256 / 128 / 64)
   int abb_axis;          // kFusedTwice with masks: memory axis of the plan's outlet (2 without one)
   int n_abb;             // anti-bounce-back outlets of the plan
@@ -43,6 +44,10 @@ struct StepArgs {
   const void *ghost_lo, *ghost_hi; // kFusedTwice edge launch: received halo messages to read the planes beyond the cuts from (or null)
   int interior_begin, interior_end;   // first interior plane, one past the last
   hipStream_t stream;
+  // MRT (coll 10, 11; lt_plan_set_mrt): the transform (lt_mrt_transform; 0: no MRT) and the relaxation rates s_i of its
+  // q moments, as the caller gave them (the units form 1 / s_i in the plan's scalar type)
+  int mrt_transform;
+  double mrt_rates[27];
 };
 
 struct AuxArgs {
@@ -107,7 +112,7 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 // What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
 // on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
 // collision) and outlets (plans with a constant-pressure outlet), every unit, sweeps and smagorinsky (3-D
-// units), roles (units with a role-wave sweep).  Declared for every unit, defined where the Makefile builds the part.
+// units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
   int aux_##tag(const AuxArgs &);                              \
@@ -119,7 +124,9 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
   int outlets3_##tag(const StepArgs &, const NameBuf *);       \
   int twice_##tag(const StepArgs &, const NameBuf *);          \
   int smag_##tag(const StepArgs &, const NameBuf *);           \
-  int roles_##tag(const StepArgs &, const NameBuf *);
+  int roles_##tag(const StepArgs &, const NameBuf *);          \
+  int mrt_##tag(const StepArgs &, const NameBuf *);            \
+  int mrt_outlets_##tag(const StepArgs &, const NameBuf *);
 LT_UNITS(LT_DECLARE_UNIT)
 
 // returns -1 when the combination has no instantiated kernel, else the hipError_t of the launch

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "lattice.hpp"
+#include "mrt.hpp"
 #include "twostep_roles.hpp"
 
 namespace lt {
@@ -106,6 +107,13 @@ struct KParamsF : KParams<T> {
   T accel[3];                // acceleration along the MEMORY axes a0, a1, a2 (the units permute it; 0 beyond the lattice's d)
   T shift[3];                // ueq_scale * accel (Guo 1/2, Shan-Chen force.tau): u* = j / rho + shift / rho
   T source_scale;            // Guo: 1 - 1 / (2 force.tau), Shan-Chen: 0
+};
+
+// The parameters of a kernel with the multiple-relaxation-time collision (COLL 10, 11; mrt.hpp): KParams and, behind it,
+// the reciprocal relaxation rates of the q moments.  A type of its own for the same reason.
+template <typename T>
+struct KParamsM : KParams<T> {
+  T r[kMrtMaxQ];             // r_i = 1 / s_i, formed in T (unit.inc); 0 beyond the lattice's q
 };
 
 // ---- constants the reference builds from cs = 1/np.sqrt(3.0) (lettuce/_stencil.py:17) ----
@@ -895,6 +903,7 @@ __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, in
         if constexpr (COLL == 8) collide_trt<T, S, LAYOUT, 1, 0>(g, p.beta, p.smag_c2);
         if constexpr (COLL == 9) collide_regularized<T, S, LAYOUT, 1, 0>(g, p.smag_c2);
         if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(g, p);
+        if constexpr (COLL == 10 || COLL == 11) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, 1, 0>(g, p.r);
       }
       for (int t = 1; t < slot; ++t) {
         const int kind = p.bt->kind[t];
@@ -1068,6 +1077,7 @@ __device__ __forceinline__ void lbm_body(const P &p) {
         if constexpr (COLL == 8) collide_trt<T, S, LAYOUT, 1, 0>(f, p.beta, p.smag_c2);
         if constexpr (COLL == 9) collide_regularized<T, S, LAYOUT, 1, 0>(f, p.smag_c2);
         if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(f, p);
+        if constexpr (COLL == 10 || COLL == 11) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, 1, 0>(f, p.r);
       }
       if constexpr (MASKED)
         apply_boundaries<T, S, LAYOUT, STREAM, 1, 0, COLL, ABBD>(p, b, c0, c1, c2, own, f, lane_slot, lane_rho, lane_j);
@@ -1113,6 +1123,16 @@ template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, 
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsF<T> p) {
   static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
   static_assert(COLL == 5 || COLL == 7, "a body force exists for BGK (5) and Smagorinsky (7)");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
+}
+
+// ... with the multiple-relaxation-time collision (COLL 10: Dellar on D2Q9, Hermite on D3Q27; 11: Lallemand): the same
+// body on KParamsM
+template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
+          int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+__global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsM<T> p) {
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  static_assert(COLL == 10 || COLL == 11, "MRT is collision 10 (Dellar / Hermite) or 11 (Lallemand)");
   lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 

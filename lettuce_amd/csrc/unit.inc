@@ -17,6 +17,8 @@
 #define LT_IS_3D (LT_FIELD(d, LT_UNIT) == 3)
 #define LT_HAS_KBC LT_FIELD(kbc, LT_UNIT)
 #define LT_HAS_ROLES LT_FIELD(roles, LT_UNIT)
+// the lattices of the moment transforms with an equilibrium of their own (mrt.hpp): D2Q9 and D3Q27
+#define LT_HAS_MRT (LT_FIELD(q, LT_UNIT) == 9 || LT_FIELD(q, LT_UNIT) == 27)
 
 // LT_PART names the object of the unit that is being built (Makefile: build/inst<N>_<tag>.o):
 //   main (inst_)          dispatch(), the auxiliary kernels and the three entry points api.hip calls; the one-step
@@ -44,6 +46,10 @@
 //   outlets2 (inst8_)     ... Smagorinsky, TRT and the regularised collision
 //   outlets3 (inst9_)     ... BGK and Smagorinsky with a body force -- three objects, because the chain of depth 2 inlines
 //                         the gather and the collision three times and one object per unit would be the longest job
+//   mrt (inst10_)         units with LT_HAS_MRT: the multiple-relaxation-time collision (the kernels' COLL = 10: Dellar on
+//                         D2Q9, Hermite on D3Q27; 11: Lallemand on D2Q9) -- every one-step variant BGK has, on a parameter
+//                         block of their own (KParamsM); no launch of several steps
+//   mrt_outlets (inst11_) ... and its kernels of plans with a constant-pressure outlet
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -54,7 +60,9 @@
 #define LT_PART_outlets 7
 #define LT_PART_outlets2 8
 #define LT_PART_outlets3 9
-#define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3))
+#define LT_PART_mrt 10
+#define LT_PART_mrt_outlets 11
+#define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
 #define LT_ONE_STEP 1
@@ -74,11 +82,14 @@
 #elif LT_PART_IS(relaxations)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 1
-#elif LT_PART_IS_OUTLETS
+#elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2 or outlets3"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt or mrt_outlets"
+#endif
+#if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
+#error "the MRT collision exists on D2Q9 and D3Q27"
 #endif
 
 namespace lt {
@@ -99,7 +110,8 @@ constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
 // The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
 // to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
 template <int COLL>
-using ParamsOf = std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>;
+using ParamsOf = std::conditional_t<COLL == 10 || COLL == 11, KParamsM<T>,
+                                    std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>>;
 template <class P>
 P params_of(const StepArgs &a, int n2) {
   P p{};
@@ -148,6 +160,12 @@ void set_force(KParamsF<T> &p, const StepArgs &a) {
   p.source_scale = (T)a.source_scale;
 }
 
+// the rates of an MRT plan (lt_plan_set_mrt): r_i = 1 / s_i with both the rate and the quotient in T -- the reference
+// converts the rates to the context's dtype and divides there on every call (mrt_collision.py:18-24)
+void set_mrt(KParamsM<T> &p, const StepArgs &a) {
+  for (int i = 0; i < kMrtMaxQ; ++i) p.r[i] = i < S::Q ? T(1) / (T)a.mrt_rates[i] : T(0);
+}
+
 // Kernel names, as lt_plan_kernel_name reports them: the kernel's identifier and its template arguments behind the
 // scalar type and the lattice, "lbm2m_kernel<float, lt::D3Q19, 0, 1, 64, 8, 2>".  An argument wrapped in elided() is a
 // trailing one that the name leaves out while it has its default (0 / false).
@@ -191,6 +209,7 @@ int launch(const StepArgs &a, const NameBuf *name) {
   P p = params_of<P>(a, a.n2);
   p.nvec_total = (unsigned)((long long)p.nv0 * a.n1 * a.planes);
   if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
+  if constexpr (COLL == 10 || COLL == 11) set_mrt(p, a);
   p.abb0_slot = a.n0 % 64 == 0 ? a.abb0_slot : 0;
   if (p.nvec_total == 0) return 0;
   const unsigned grid = (p.nvec_total + kThreads - 1) / kThreads;
@@ -233,7 +252,7 @@ int launch(const StepArgs &a, const NameBuf *name) {
 
 // The one-step kernels of collision C, fused and collide-only: main has them for 0 (none), 1 (BGK) and, with
 // LT_HAS_KBC, 2; Smagorinsky (3) has every variant BGK has, and so have BGK and Smagorinsky with a body force (5, 7),
-// TRT (8) and the regularised collision (9).
+// TRT (8), the regularised collision (9) and MRT (10, 11).
 // The order matters where the conditions overlap: the outlet depths before the rest, packed before the plain slab set.
 template <int C>
 int one_step_of(const StepArgs &a, const NameBuf *name) {
@@ -523,6 +542,9 @@ int dispatch(const StepArgs &a, const NameBuf *name) {
   if (a.n_pout > 0 && a.mode != kStreamOnly) return LT_CAT(outlets_, LT_TAG)(a, name);
   if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
   if (coll == 8 || coll == 9) return LT_CAT(relax_, LT_TAG)(a, name);   // TRT, regularised: part relaxations
+#if LT_HAS_MRT
+  if (coll == 10 || coll == 11) return LT_CAT(mrt_, LT_TAG)(a, name);   // MRT: part mrt
+#endif
   if (a.mode == kFusedMany) {
     if (coll == 0) return many_of<0>(a, name);
     if (coll == 1) return many_of<1>(a, name);
@@ -703,6 +725,9 @@ int LT_CAT(outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
 #endif
     case 3: case 8: case 9: return LT_CAT(outlets2_, LT_TAG)(a, name);
     case 5: case 7: return LT_CAT(outlets3_, LT_TAG)(a, name);
+#if LT_HAS_MRT
+    case 10: case 11: return LT_CAT(mrt_outlets_, LT_TAG)(a, name);
+#endif
     default: return kNoKernel;
   }
 }
@@ -717,6 +742,24 @@ int LT_CAT(outlets2_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
 int LT_CAT(outlets3_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.coll == 5) return pressure_outlets_of<5>(a, name);
   if (a.coll == 7) return pressure_outlets_of<7>(a, name);
+  return kNoKernel;
+}
+#elif LT_PART_IS(mrt)
+// one-step kernels only; the transform picks the kernels' COLL (api.hip, kernel_coll)
+int LT_CAT(mrt_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
+  if (a.coll == 10) return one_step_of<10>(a, name);
+#if !LT_IS_3D
+  if (a.coll == 11) return one_step_of<11>(a, name);
+#endif
+  return kNoKernel;
+}
+#elif LT_PART_IS(mrt_outlets)
+int LT_CAT(mrt_outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.coll == 10) return pressure_outlets_of<10>(a, name);
+#if !LT_IS_3D
+  if (a.coll == 11) return pressure_outlets_of<11>(a, name);
+#endif
   return kNoKernel;
 }
 #endif

@@ -1,5 +1,5 @@
-"""Collision operators on the hot path: BGK, KBC (D2Q9 / D3Q27), Smagorinsky, TRT, regularised (every lattice) and
-NoCollision.
+"""Collision operators on the hot path: BGK, KBC (D2Q9 / D3Q27), Smagorinsky, TRT, regularised (every lattice), MRT
+(D2Q9 / D3Q27) and NoCollision.
 
 Each ``__call__`` is a pure whole-field function ``flow -> tensor`` usable outside a
 ``Simulation`` (the reference's tests call ``collision(flow)`` directly).  On a native context
@@ -7,8 +7,9 @@ and for the flow's grid-shaped state it is one launch of the engine's collide ke
 otherwise the reference's torch expressions are evaluated.  BGK and Smagorinsky take a body force
 (``force=Guo(...)`` / ``ShanChen(...)``, ext/_force.py), on the engine when its acceleration is uniform.
 TRT and the regularised collision are on the engine for every lattice as well (one-step kernels; the plain two-step
-sweep on D3Q19 fp32); neither takes a force, as in the reference.  MRT is out of scope: it needs
-the reference's Transform classes.
+sweep on D3Q19 fp32); neither takes a force, as in the reference.  MRT takes a moment transform of
+``lettuce_amd.moments``: with D2Q9Dellar, D2Q9Lallemand or D3Q27Hermite it is on the engine (one-step kernels), with any
+other transform it stays on the torch path.
 """
 import warnings
 from typing import AnyStr, Optional
@@ -21,13 +22,14 @@ from ._force import Force
 from ..util import LettuceException
 
 __all__ = ["BGKCollision", "KBCCollision", "KBCCollision2D", "KBCCollision3D", "NoCollision",
-           "SmagorinskyCollision", "TRTCollision", "RegularizedCollision"]
+           "SmagorinskyCollision", "TRTCollision", "RegularizedCollision", "MRTCollision"]
 
 
-def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None):
+def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None, mrt=None):
     """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``constant``: the
     Smagorinsky constant, ``tau_minus``: TRT's second relaxation time, ``force``: the collision's body force (a Force
-    or None) -- per-launch settings of the kind's one plan, handed over before every collide."""
+    or None), ``mrt``: (transform name, rates) of MRT -- per-launch settings of the kind's one plan, handed over before
+    every collide."""
     if flow._engine_plan(flow.f) is None:
         return None
     plans = flow.__dict__.setdefault("_collision_plans", {})
@@ -39,6 +41,8 @@ def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None):
         plans[kind].set_smagorinsky(constant)
     if tau_minus is not None:
         plans[kind].set_trt(tau_minus)
+    if mrt is not None:
+        plans[kind].set_mrt(*mrt)
     if kind in ("bgk", "smagorinsky"):
         if force is None:
             plans[kind].set_force(None)
@@ -321,6 +325,52 @@ class RegularizedCollision(Collision):
             self._prepare(flow)
             return self.tau
         return NativeCollision("regularized", tau=tau)
+
+
+class MRTCollision(Collision):
+    """Multiple relaxation times (lettuce/ext/_collision/mrt_collision.py:6-33): the moments ``transform.transform(f)``
+    relax towards ``transform.equilibrium`` with one rate each, m_i <- m_i - (m_i - meq_i) / s_i.  The transform may be
+    any ``lettuce_amd.moments.Transform``.  ``relaxation_parameters`` becomes a tensor of the context's dtype and is read
+    on every call, as in the reference.
+
+    On the engine for exactly the three transforms with an equilibrium of their own, each on its own lattice; a subclass
+    may override the equilibrium and therefore does not count."""
+
+    def __init__(self, transform: "Transform", relaxation_parameters: list, context: "Context"):
+        self.transform = transform
+        self.relaxation_parameters = context.convert_to_tensor(relaxation_parameters)
+
+    def _native_transform(self) -> Optional[str]:
+        """the engine's name of the transform, or None"""
+        from ..moments import D2Q9Dellar, D2Q9Lallemand, D3Q27Hermite
+        cls = type(self.transform)
+        if cls not in (D2Q9Dellar, D2Q9Lallemand, D3Q27Hermite):
+            return None
+        if type(self.transform.stencil) not in cls.supported_stencils:
+            return None
+        return cls.__name__
+
+    def _rates(self):
+        """the q rates as floats: one device-to-host copy"""
+        return tuple(float(s) for s in self.relaxation_parameters.tolist())
+
+    def __call__(self, flow: "Flow") -> torch.Tensor:
+        name = self._native_transform()
+        if name is not None:
+            out = _engine_collide(flow, "mrt", 1.0, mrt=(name, self._rates()))
+            if out is not None:
+                return out
+        m = self.transform.transform(flow.f)
+        meq = self.transform.equilibrium(m, flow)
+        rates = 1 / self.relaxation_parameters
+        m = m - rates.reshape([-1] + [1] * flow.stencil.d) * (m - meq)
+        return self.transform.inverse_transform(m)
+
+    def native_available(self) -> bool:
+        return self._native_transform() is not None
+
+    def native_generator(self) -> "NativeCollision":
+        return NativeCollision("mrt", transform=self._native_transform(), rates=lambda flow: self._rates())
 
 
 class NoCollision(Collision):

@@ -34,7 +34,7 @@ class NativeForce:
 
 @dataclass
 class NativeCollision:
-    kind: str                                  # 'none' | 'bgk' | 'kbc' | 'smagorinsky' | 'trt' | 'regularized'
+    kind: str                                  # 'none' | 'bgk' | 'kbc' | 'smagorinsky' | 'trt' | 'regularized' | 'mrt'
     # relaxation time used for the next batch of steps; evaluated per call because the
     # reference re-reads collision.tau on every invocation
     # (lettuce/cuda_native/ext/_collision/bgk_collision.py:30)
@@ -50,6 +50,12 @@ class NativeCollision:
     tau_minus: Optional[Callable[["Flow"], float]] = None
     # 'bgk' / 'smagorinsky': the body force of the collision, or None
     force: Optional[NativeForce] = None
+    # 'mrt': the class name of the moment transform ('D2Q9Dellar' | 'D2Q9Lallemand' | 'D3Q27Hermite') and its q
+    # relaxation rates as a tuple of floats (hashable: part of the steppers' carry key), evaluated per batch like tau
+    # (the reference reads collision.relaxation_parameters on every call, lettuce/ext/_collision/mrt_collision.py:24;
+    # `tau` is not read); None for the other kinds
+    transform: Optional[str] = None
+    rates: Optional[Callable[["Flow"], Tuple[float, ...]]] = None
 
 
 @dataclass
