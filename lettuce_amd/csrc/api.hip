@@ -163,7 +163,7 @@ struct lt_plan {
   double *partial = nullptr;
   int masked = 0;
   int n_abb = 0;             // anti-bounce-back outlets of the plan
-  int n_pout = 0;            // constant-pressure outlets of the plan (one-step kernels only: pressure_outlet_refuses)
+  int n_pout = 0;            // constant-pressure outlets of the plan (one-step kernels only: multi_step_refusal)
   int abb_depth = 0;         // how deep an outlet's neighbour must be rebuilt (lt_plan_create)
   int nsm_confined = 1;      // the no-streaming bits are exactly those of the plan's outlet (lt_plan_set_masks)
   int inlet_faces_outlet = 1;  // outlet along a0: every node of the opposite face is an equilibrium node
@@ -534,67 +534,71 @@ int masked_two_step_axis(const lt_plan *p) {
 }
 bool masked_two_step_ok(const lt_plan *p) { return masked_two_step_axis(p) >= 0; }
 bool canary_ok(lt_plan *p);
-// the kernels' COLL of the plan: its collision, + 4 with a body force
-// (MRT: 10, and 11 with Lallemand's transform -- Dellar and Hermite are told apart by the lattice)
+// the kernels' COLL of the plan (dispatch.hpp, kColl*): its collision, | kCollForce with a body force; MRT by its
+// transform (Dellar and Hermite are told apart by the lattice)
 int kernel_coll(const lt_plan *p) {
-  if (p->desc.collision == LT_COLLISION_MRT) return p->mrt.transform == LT_MRT_D2Q9_LALLEMAND ? 11 : 10;
-  return p->desc.collision | (p->force.on ? 4 : 0);
+  if (p->desc.collision == LT_COLLISION_MRT)
+    return p->mrt.transform == LT_MRT_D2Q9_LALLEMAND ? lt::kCollMrtLallemand : lt::kCollMrt;
+  return p->desc.collision | (p->force.on ? lt::kCollForce : 0);
 }
+static_assert(lt::kCollNone == LT_COLLISION_NONE && lt::kCollBgk == LT_COLLISION_BGK && lt::kCollKbc == LT_COLLISION_KBC &&
+              lt::kCollSmagorinsky == LT_COLLISION_SMAGORINSKY && lt::kCollTrt == LT_COLLISION_TRT &&
+              lt::kCollRegularized == LT_COLLISION_REGULARIZED && lt::kCollMrt == LT_COLLISION_MRT,
+              "the kernels' collision numbers are the ABI's where the ABI has the operator");
+
+// ---- which plans have a launch of several steps ----
 const char *const kForceMultiStep = "a body force (lt_plan_set_force) has the one-step kernels and the plain two-step sweep "
                                     "of periodic D3Q19 fp32 plans without masks only: no many-step, 2-D, masked, role-wave "
                                     "or slab two-step kernel takes it";
 const char *const kForceSmagorinskyTwice = "Smagorinsky with a body force (lt_plan_set_force) does not fit the two-step "
                                            "sweep's occupancy step without scratch: it keeps the one-step kernel";
-// why a plan with a body force has no launch of several steps in `mode` (nullptr: it may have one)
-const char *force_refuses(const lt_plan *p, int mode) {
-  if (!p->force.on) return nullptr;
-  if (mode == lt::kFusedMany) return kForceMultiStep;
-  if (mode == lt::kFusedTwice) {
-    if (p->unit.d != 3 || p->masked || p->desc.ghost_planes || p->desc.stencil != LT_D3Q19 || p->desc.dtype != LT_F32)
-      return kForceMultiStep;
+const char *const kTrtMultiStep = "the TRT collision has the one-step kernels and the plain two-step sweep of periodic D3Q19 "
+                                  "fp32 plans without masks only: no many-step, 2-D, masked, role-wave, edge, packed or "
+                                  "signalling two-step kernel takes it";
+const char *const kRegularizedMultiStep = "the regularised collision has the one-step kernels and the plain two-step sweep "
+                                          "of periodic D3Q19 fp32 plans without masks only: no many-step, 2-D, masked, "
+                                          "role-wave, edge, packed or signalling two-step kernel takes it";
+// (refused by name, not through the admission tests of the masked two-step kernels, which were written for the
+// anti-bounce-back outlet's no-streaming bits)
+const char *const kPressureOutletMultiStep = "a constant-pressure outlet (EquilibriumOutletP) has the one-step kernels only: "
+                                             "no masked two-step, 2-D two-step, many-step or two-ghost-plane slab kernel "
+                                             "takes it";
+const char *const kMrtMultiStep = "the MRT collision has the one-step kernels only: no two-step, many-step or "
+                                  "two-ghost-plane slab kernel takes it";
+const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
+                                      "edge, packed or signalling launches): slabs keep the one-step kernels";
+// (step() says "two steps per launch with" in front of it, the admission "two steps per launch: ")
+const char *const kMaskedTwoStep = "boundaries: at most one anti-bounce-back outlet, at the last plane of the slowest memory "
+                                   "axis (periodic plans only) or at an end of the contiguous axis opposite a face of "
+                                   "equilibrium nodes; no-streaming bits exactly that outlet's";
+
+// Why the plan has no launch of `mode` (kFusedTwice, kFusedMany; nullptr for any other), or nullptr: its collision and
+// its kinds of boundary allow one.  The one place that keeps a collision or a boundary kind from the launches of several
+// steps: step(), two_step_possible() and many_step_wanted() ask here, the first reason wins.  What depends on the grid
+// -- tiling, addressing, the unit's kernels, the canary -- stays with those.
+const char *multi_step_refusal(const lt_plan *p, int mode) {
+  if (mode != lt::kFusedTwice && mode != lt::kFusedMany) return nullptr;
+  const bool twice = mode == lt::kFusedTwice;
+  // what a body force, TRT and the regularised collision have beside the one-step kernels (unit.inc, parts forced and
+  // relaxations): the plain two-step sweep of periodic D3Q19 fp32 plans without masks
+  const bool plain_sweep = twice && p->unit.d == 3 && !p->masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
+                           p->desc.dtype == LT_F32;
+  if (p->force.on) {
+    if (!plain_sweep) return kForceMultiStep;
     lt::StepArgs a;
     memset(&a, 0, sizeof a);
     a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = lt::kFusedTwice;
     if (!has_kernel(p->unit, a)) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
   }
+  if (p->desc.collision == LT_COLLISION_TRT && !plain_sweep) return kTrtMultiStep;
+  if (p->desc.collision == LT_COLLISION_REGULARIZED && !plain_sweep) return kRegularizedMultiStep;
+  if (p->n_pout > 0) return kPressureOutletMultiStep;                  // the one-step kernels only (unit.inc, part outlets)
+  if (p->desc.collision == LT_COLLISION_MRT) return kMrtMultiStep;     // the one-step kernels only (unit.inc, part mrt)
+  if (twice && p->desc.ghost_planes && p->desc.collision == LT_COLLISION_SMAGORINSKY) return kSmagorinskySlabs;
+  // masks: their admission, and on a slab an outlet only along the rows
+  if (twice && p->masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0)))
+    return kMaskedTwoStep;
   return nullptr;
-}
-// TRT and the regularised collision: the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 plans
-// without masks (unit.inc, part relaxations).  nullptr: `mode` may have a launch for the plan
-bool is_relaxation(const lt_plan *p) {
-  return p->desc.collision == LT_COLLISION_TRT || p->desc.collision == LT_COLLISION_REGULARIZED;
-}
-const char *relaxation_refuses(const lt_plan *p, int mode) {
-  if (!is_relaxation(p) || (mode != lt::kFusedMany && mode != lt::kFusedTwice)) return nullptr;
-  const bool trt = p->desc.collision == LT_COLLISION_TRT;
-  if (mode == lt::kFusedTwice && p->unit.d == 3 && !p->masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
-      p->desc.dtype == LT_F32)
-    return nullptr;
-  return trt ? "the TRT collision has the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 plans "
-               "without masks only: no many-step, 2-D, masked, role-wave, edge, packed or signalling two-step kernel "
-               "takes it"
-             : "the regularised collision has the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 "
-               "plans without masks only: no many-step, 2-D, masked, role-wave, edge, packed or signalling two-step "
-               "kernel takes it";
-}
-// MRT: the one-step kernels only (unit.inc, part mrt)
-const char *const kMrtMultiStep = "the MRT collision has the one-step kernels only: no two-step, many-step or "
-                                  "two-ghost-plane slab kernel takes it";
-const char *mrt_refuses(const lt_plan *p, int mode) {
-  return p->desc.collision == LT_COLLISION_MRT && (mode == lt::kFusedMany || mode == lt::kFusedTwice) ? kMrtMultiStep
-                                                                                                      : nullptr;
-}
-const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
-                                      "edge, packed or signalling launches): slabs keep the one-step kernels";
-
-// The constant-pressure outlet (LT_BOUNDARY_PRESSURE_OUTLET) has the one-step kernels only (unit.inc, part outlets).
-// Refused by name, not through the admission tests of the masked two-step kernels, which were written for the
-// anti-bounce-back outlet's no-streaming bits
-const char *const kPressureOutletMultiStep = "a constant-pressure outlet (EquilibriumOutletP) has the one-step kernels only: "
-                                             "no masked two-step, 2-D two-step, many-step or two-ghost-plane slab kernel "
-                                             "takes it";
-const char *pressure_outlet_refuses(const lt_plan *p, int mode) {
-  return p->n_pout > 0 && (mode == lt::kFusedMany || mode == lt::kFusedTwice) ? kPressureOutletMultiStep : nullptr;
 }
 
 int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long pb, long long pe,
@@ -607,14 +611,14 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   if (p->desc.ghost_planes && (pb < 1 || pe > p->n2 - 1) && mode != lt::kCollideOnly && pe > pb)
     return fail(LT_ERR_INVALID, "streaming from ghost planes: range [%lld, %lld) must stay in [1, %d)",
                 pb, pe, p->n2 - 1);
-  if (const char *why = force_refuses(p, mode))
-    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
-  if (const char *why = relaxation_refuses(p, mode))
-    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
-  if (const char *why = pressure_outlet_refuses(p, mode))
-    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
-  if (const char *why = mrt_refuses(p, mode))
-    return fail(LT_ERR_UNSUPPORTED, "%s per launch: %s", mode == lt::kFusedMany ? "several steps" : "two steps", why);
+  // the plan has no such launch (its two reasons about slabs and masks: behind the checks of the call's range below)
+  const char *const why = multi_step_refusal(p, mode);
+  const bool after_range = why == kSmagorinskySlabs || why == kMaskedTwoStep;
+  const auto refuse = [&] {
+    return fail(LT_ERR_UNSUPPORTED, why == kMaskedTwoStep ? "%s per launch with %s" : "%s per launch: %s",
+                mode == lt::kFusedMany ? "several steps" : "two steps", why);
+  };
+  if (why && !after_range) return refuse();
   const bool mrt = p->desc.collision == LT_COLLISION_MRT;
   if (mrt && mode != lt::kStreamOnly && p->mrt.transform == 0)
     return fail(LT_ERR_INVALID, "the plan's collision is MRT: lt_plan_set_mrt must give the transform and the rates first");
@@ -628,13 +632,7 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
       return fail(LT_ERR_INVALID, "two-step range [%lld, %lld) must stay in [2, %d)", pb, pe, p->n2 - 2);
     if (!p->desc.ghost_planes && (pb != 0 || pe != p->n2))
       return fail(LT_ERR_INVALID, "periodic plan: the two-step launch covers all planes");
-    if (p->desc.ghost_planes && p->desc.collision == LT_COLLISION_SMAGORINSKY)
-      return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kSmagorinskySlabs);
-    if (p->masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0)))
-      return fail(LT_ERR_UNSUPPORTED, "two steps per launch with boundaries: at most one anti-bounce-back outlet, at the "
-                                      "last plane of the slowest memory axis (periodic plans only) or at an end of "
-                                      "the contiguous axis opposite a face of equilibrium nodes; no-streaming bits "
-                                      "exactly that outlet's");
+    if (why) return refuse();
     if (p->masked && !p->canary_running && !canary_ok(p)) return fail(LT_ERR_UNSUPPORTED, "%s", p->canary_msg);
   }
   if (p->desc.n_boundaries > 0 && !p->masked)
@@ -759,19 +757,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
 bool two_step_possible(lt_plan *p, const char **why) {
   const char *dummy;
   if (!why) why = &dummy;
-  if (const char *refused = force_refuses(p, lt::kFusedTwice)) {
-    *why = refused;
-    return false;
-  }
-  if (const char *refused = relaxation_refuses(p, lt::kFusedTwice)) {
-    *why = refused;
-    return false;
-  }
-  if (const char *refused = pressure_outlet_refuses(p, lt::kFusedTwice)) {
-    *why = refused;
-    return false;
-  }
-  if (const char *refused = mrt_refuses(p, lt::kFusedTwice)) {
+  if (const char *refused = multi_step_refusal(p, lt::kFusedTwice)) {
     *why = refused;
     return false;
   }
@@ -788,16 +774,6 @@ bool two_step_possible(lt_plan *p, const char **why) {
     *why = p->masked ? "with boundaries the two-step kernel addresses with 32-bit offsets: q * nodes * sizeof(scalar) (BGK, "
                        "reference layout: nodes * sizeof(scalar)) must stay below 4 GiB"
                      : "a plane of the grid exceeds the two-step kernel's 32-bit in-plane offsets";
-    return false;
-  }
-  if (p->masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0))) {
-    *why = "boundaries: at most one anti-bounce-back outlet, at the last plane of the slowest memory axis (periodic "
-           "plans only) or at an end of the contiguous axis opposite a face of equilibrium nodes; no-streaming bits "
-           "exactly that outlet's";
-    return false;
-  }
-  if (p->desc.ghost_planes && p->desc.collision == LT_COLLISION_SMAGORINSKY) {
-    *why = kSmagorinskySlabs;
     return false;
   }
   lt::StepArgs a;
@@ -818,25 +794,30 @@ bool two_step_possible(lt_plan *p, const char **why) {
   return true;
 }
 
+// The plans whose two-step launch lt_run takes only when asked (lt_plan_set_two_step(plan, 1, ...)), never by itself
+bool two_step_never_automatic(const lt_plan *p) {
+  // KBC inside the masked two-step kernel agrees with the one-step kernel at rounding level only (hipcc contracts
+  // its multiply-adds differently in the two inlining contexts): never automatic, so that the result of n steps
+  // does not depend on how the caller splits them into batches
+  if (p->desc.collision == LT_COLLISION_KBC) return true;
+  // a body force: never automatic (the forced two-step sweep has not been measured against two one-step launches,
+  // DESIGN.md section 7)
+  if (p->force.on) return true;
+  // TRT, regularised: never automatic either, for the same reason
+  if (p->desc.collision == LT_COLLISION_TRT || p->desc.collision == LT_COLLISION_REGULARIZED) return true;
+  // MRT has no two-step kernel
+  // (Smagorinsky, D3Q19 fp32: bit-identical to two one-step launches and 0.279-0.309 against 0.409-0.475 ms per
+  // update at 256^3, every sample below every sample of the one-step pair: automatic like BGK, DESIGN.md section 7)
+  return p->desc.collision == LT_COLLISION_MRT;
+}
+
 // Does lt_run pair its fused steps?  "automatic" also asks for the streaming regime (populations beyond the
 // caches), where halving the HBM passes pays.
 bool two_step_wanted(lt_plan *p) {
   if (p->two_step == 0 || p->desc.ghost_planes) return false;
   if (!two_step_possible(p, nullptr)) return false;
   if (p->two_step == 1) return true;
-  // KBC inside the masked two-step kernel agrees with the one-step kernel at rounding level only (hipcc contracts
-  // its multiply-adds differently in the two inlining contexts): never automatic, so that the result of n steps
-  // does not depend on how the caller splits them into batches
-  if (p->desc.collision == LT_COLLISION_KBC) return false;
-  // a body force: never automatic (the forced two-step sweep has not been measured against two one-step launches,
-  // DESIGN.md section 7); lt_plan_set_two_step(plan, 1, ...) takes it
-  if (p->force.on) return false;
-  // TRT, regularised: never automatic either, for the same reason
-  if (is_relaxation(p)) return false;
-  // MRT has no two-step kernel
-  if (p->desc.collision == LT_COLLISION_MRT) return false;
-  // (Smagorinsky, D3Q19 fp32: bit-identical to two one-step launches and 0.279-0.309 against 0.409-0.475 ms per
-  // update at 256^3, every sample below every sample of the one-step pair: automatic like BGK, DESIGN.md section 7)
+  if (two_step_never_automatic(p)) return false;
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
   return bytes > (128ll << 20);
 }
@@ -968,9 +949,7 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->mas
 // 2-D kernel wins because it amortises EIGHT steps per launch, which the LDS does not allow in 3-D (K = 3 needs the
 // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
-  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || p->force.on || is_relaxation(p) || p->n_pout > 0 ||
-      p->desc.collision == LT_COLLISION_MRT)
-    return false;
+  if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || multi_step_refusal(p, lt::kFusedMany) != nullptr) return false;
   if (p->masked && p->n_abb > 1) return false;
   if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
   lt::StepArgs a;

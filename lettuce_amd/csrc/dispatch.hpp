@@ -9,6 +9,15 @@ namespace lt {
 
 enum StepMode { kFused = 0, kCollideOnly = 1, kStreamOnly = 2, kFusedTwice = 3, kFusedMany = 4 };
 
+// The kernels' collision number (their COLL, StepArgs::coll): lt_collision where the ABI has the operator, kCollForce
+// added to BGK and Smagorinsky with a body force (5, 7), and the MRT transforms apart.  TRT and the regularised
+// collision are 8 and 9, MRT 10 and 11, so that none of them carries the force bit by accident.
+constexpr int kCollNone = 0, kCollBgk = 1, kCollKbc = 2, kCollSmagorinsky = 3, kCollForce = 4, kCollTrt = 8,
+              kCollRegularized = 9, kCollMrt = 10, kCollMrtLallemand = 11;
+constexpr bool coll_mrt(int coll) { return coll == kCollMrt || coll == kCollMrtLallemand; }
+constexpr bool coll_forced(int coll) { return coll == (kCollBgk | kCollForce) || coll == (kCollSmagorinsky | kCollForce); }
+constexpr int coll_base(int coll) { return coll_forced(coll) ? coll & ~kCollForce : coll; }   // the collision under the force
+
 struct StepArgs {
   const void *in;
   void *out;
@@ -28,8 +37,8 @@ struct StepArgs {
   const unsigned *nsm_bits;
   const void *bt;        // BoundaryTable<T>* (device)
   int nb;
-  int layout, coll, mode, masked, shift, tune;   // coll: lt_collision (0-3, 8, 9), + 4 with a body force; MRT: 10, or 11
-                                                 // with Lallemand's transform (the kernels' COLL)
+  int layout, coll, mode, masked, shift, tune;   // coll: the kernels' COLL, one of the kColl* numbers above (with a body
+                                                 // force: | kCollForce)
   int strip;             // kFusedTwice on 2-D lattices: columns per workgroup (512 / 256 / 128 / 64)
   int abb_axis;          // kFusedTwice with masks: memory axis of the plan's outlet (2 without one)
   int n_abb;             // anti-bounce-back outlets of the plan

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dispatch.hpp"
 #include "lattice.hpp"
 #include "mrt.hpp"
 #include "twostep_roles.hpp"
@@ -70,8 +71,8 @@ struct KParams {
   unsigned nvec_total;       // threads doing work: nv0 * n1 * planes
   T tau_inv;                 // BGK: 1/tau
   T beta, inv_beta;          // KBC: 1/(2 tau), 1/beta; TRT reads beta as 1/(2 tau_plus)
-  T tau, smag_c2;            // Smagorinsky: tau and the squared constant.  smag_c2 is the collision's own scalar: TRT
-                             // (COLL 8) reads it as 1/(2 tau_minus), the regularised collision (COLL 9) as 1 - 1/tau
+  T tau, smag_c2;            // Smagorinsky: tau and the squared constant.  smag_c2 is the collision's own scalar: what
+                             // it means to TRT and the regularised collision is said once, at collide_node
   const unsigned char *node; // [N] boundary index | 0x80 if any no-streaming bit (or null)
   const unsigned *nsm_bits;  // [N] bit q set: population q keeps its value (or null)
   const BoundaryTable<T> *bt;
@@ -862,6 +863,22 @@ __device__ __forceinline__ void abb_apply(const KParams<T> &p, int slot, T rn, c
   else abb_apply_ax<T, S, LAYOUT, 2, VEC, k>(side, rn, jn, f);
 }
 
+// ---- the collision of a kernel ------------------------------------------------------------
+// The collision with number COLL (dispatch.hpp, kColl*) on node k of f: the one place that says which function a
+// number means and which fields of the parameter block P it reads.  smag_c2 is the collision's own scalar (unit.inc,
+// params_of): Smagorinsky's squared constant, TRT's 1 / (2 tau_minus) beside beta = 1 / (2 tau_plus), the regularised
+// collision's 1 - 1 / tau.  A body force and MRT read their own blocks (KParamsF, KParamsM).  kCollNone: nothing.
+template <typename T, class S, int LAYOUT, int VEC, int k, int COLL, class P>
+__device__ __forceinline__ void collide_node(T (&f)[S::Q][VEC], const P &p) {
+  if constexpr (COLL == kCollBgk) collide_bgk<T, S, LAYOUT, VEC, k>(f, p.tau_inv);
+  if constexpr (COLL == kCollKbc) collide_kbc<T, S, LAYOUT, VEC, k>(f, p.beta, p.inv_beta);
+  if constexpr (COLL == kCollSmagorinsky) collide_smagorinsky<T, S, LAYOUT, VEC, k>(f, p.tau, p.smag_c2);
+  if constexpr (COLL == kCollTrt) collide_trt<T, S, LAYOUT, VEC, k>(f, p.beta, p.smag_c2);
+  if constexpr (COLL == kCollRegularized) collide_regularized<T, S, LAYOUT, VEC, k>(f, p.smag_c2);
+  if constexpr (coll_forced(COLL)) collide_forced<T, S, LAYOUT, VEC, k, coll_base(COLL)>(f, p);
+  if constexpr (coll_mrt(COLL)) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, VEC, k>(f, p.r);
+}
+
 // (rho, j) of the node (c0, c1, c2), as Flow.rho()/Flow.u() would see it when the AntiBounceBackOutlet with
 // index `slot` is evaluated: after collision (which conserves both) and after the boundaries with a lower
 // index (anti_bounce_back_outlet.py:77-80).  DEPTH = how many OTHER outlets with a lower index may touch
@@ -896,15 +913,7 @@ __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, in
         touched = touched || (ax == 0 ? c0 : (ax == 1 ? c1 : c2)) == p.bt->plane[t];
       }
     if (touched) {
-      if (b == 0) {
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(g, p.tau_inv);
-        if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(g, p.beta, p.inv_beta);
-        if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(g, p.tau, p.smag_c2);
-        if constexpr (COLL == 8) collide_trt<T, S, LAYOUT, 1, 0>(g, p.beta, p.smag_c2);
-        if constexpr (COLL == 9) collide_regularized<T, S, LAYOUT, 1, 0>(g, p.smag_c2);
-        if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(g, p);
-        if constexpr (COLL == 10 || COLL == 11) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, 1, 0>(g, p.r);
-      }
+      if (b == 0) collide_node<T, S, LAYOUT, 1, 0, COLL>(g, p);
       for (int t = 1; t < slot; ++t) {
         const int kind = p.bt->kind[t];
         if (kind == kAbbOutlet || (POUT && kind == kPressureOutlet)) {
@@ -1070,15 +1079,7 @@ __device__ __forceinline__ void lbm_body(const P &p) {
     [&] {
       int b = 0;
       if constexpr (MASKED) b = nd & 0x7f;
-      if (b == 0) {
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(f, p.tau_inv);
-        if constexpr (COLL == 2) collide_kbc<T, S, LAYOUT, 1, 0>(f, p.beta, p.inv_beta);
-        if constexpr (COLL == 3) collide_smagorinsky<T, S, LAYOUT, 1, 0>(f, p.tau, p.smag_c2);
-        if constexpr (COLL == 8) collide_trt<T, S, LAYOUT, 1, 0>(f, p.beta, p.smag_c2);
-        if constexpr (COLL == 9) collide_regularized<T, S, LAYOUT, 1, 0>(f, p.smag_c2);
-        if constexpr ((COLL & 4) != 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(f, p);
-        if constexpr (COLL == 10 || COLL == 11) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, 1, 0>(f, p.r);
-      }
+      if (b == 0) collide_node<T, S, LAYOUT, 1, 0, COLL>(f, p);
       if constexpr (MASKED)
         apply_boundaries<T, S, LAYOUT, STREAM, 1, 0, COLL, ABBD>(p, b, c0, c1, c2, own, f, lane_slot, lane_rho, lane_j);
     }();
@@ -1122,7 +1123,7 @@ template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, 
           int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsF<T> p) {
   static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
-  static_assert(COLL == 5 || COLL == 7, "a body force exists for BGK (5) and Smagorinsky (7)");
+  static_assert(coll_forced(COLL), "a body force exists for BGK (5) and Smagorinsky (7)");
   lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 
@@ -1132,7 +1133,7 @@ template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, 
           int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsM<T> p) {
   static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
-  static_assert(COLL == 10 || COLL == 11, "MRT is collision 10 (Dellar / Hermite) or 11 (Lallemand)");
+  static_assert(coll_mrt(COLL), "MRT is collision 10 (Dellar / Hermite) or 11 (Lallemand)");
   lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 
@@ -1197,7 +1198,7 @@ template <typename T, class S, int LAYOUT, int COLL, int T0_, int T1, int NPT = 
 __global__ void __launch_bounds__((SCHED == 0 ? (TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64
                                               : RoleWaves<TwoStep<T, S, T0_, T1>::NI, TwoStep<T, S, T0_, T1>::NO>::THREADS))
 lbm2_kernel(const KParams<T> p, const int seg_len) {
-  static_assert((COLL & 4) == 0, "kernels with a body force take KParamsF");
+  static_assert(!coll_forced(COLL), "kernels with a body force take KParamsF");
 #include "twostep_sweep.inc"
 }
 
@@ -1209,7 +1210,7 @@ template <typename T, class S, int LAYOUT, int COLL, int T0_, int T1, int NPT = 
           int NPB = NPT, int SCHED = 0>
 __global__ void __launch_bounds__((TwoStep<T, S, T0_, T1>::NI / NPT + 63) / 64 * 64)
 lbm2_kernel(const KParamsF<T> p, const int seg_len) {
-  static_assert(COLL == 5 || COLL == 7, "a body force exists for BGK (5) and Smagorinsky (7)");
+  static_assert(coll_forced(COLL), "a body force exists for BGK (5) and Smagorinsky (7)");
 #include "twostep_sweep.inc"
 }
 
@@ -1273,10 +1274,7 @@ lbm_many_kernel(const KParams<T> p, const int K) {
   auto wrap = [](int x, int n) { x %= n; return x < 0 ? x + n : x; };
   const int g0 = wrap(t0 - halo + i0, p.n0), g1 = wrap(t1 - halo + i1, p.n1);
   const unsigned own = (unsigned)g1 * (unsigned)p.n0 + (unsigned)g0;
-  auto collide = [&](T (&f)[S::Q][1]) {
-    if constexpr (COLL == 1) collide_bgk<T, S, 0, 1, 0>(f, p.tau_inv);
-    if constexpr (COLL == 2) collide_kbc<T, S, 0, 1, 0>(f, p.beta, p.inv_beta);
-  };
+  auto collide = [&](T (&f)[S::Q][1]) { collide_node<T, S, 0, 1, 0, COLL>(f, p); };
   // ---- boundaries (MASKED) ----
   int bidx = 0;
   unsigned bits = 0;

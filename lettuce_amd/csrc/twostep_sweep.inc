@@ -9,9 +9,10 @@
   constexpr int T0 = B::T0, H0 = B::H0, NI = B::NI, NO = B::NO;
   constexpr int NU = B::template count<LAYOUT, 1>(), NC = B::template count<LAYOUT, 0>(),
                 ND = B::template count<LAYOUT, -1>();
-  static_assert(COLL == 0 || COLL == 1 || COLL == 3 || COLL == 5 || COLL == 7 || COLL == 8 || COLL == 9,
+  static_assert(COLL == kCollNone || COLL == kCollBgk || COLL == kCollSmagorinsky || coll_forced(COLL) || COLL == kCollTrt ||
+                    COLL == kCollRegularized,
                 "two-step kernel: streaming only, BGK or Smagorinsky, the latter two also with a body force, TRT, regularised");
-  static_assert((COLL != 3 && (COLL & 4) == 0 && COLL < 8) || (SCHED == 0 && MODE == 0),
+  static_assert(COLL == kCollNone || COLL == kCollBgk || (SCHED == 0 && MODE == 0),
                 "Smagorinsky, body force, TRT, regularised: the plain one-role sweep only");
   __shared__ T lds_u[4][NU][NI];
   __shared__ T lds_c[3][NC][NI];
@@ -129,7 +130,7 @@
       };
       auto fill = [&](int r, int r3, auto set) {
         T (&src)[S::Q][1] = decltype(set)::value == 0 ? set0 : set1;
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
+        collide_node<T, S, LAYOUT, 1, 0, COLL>(src, p);
         if (in_a) {
           static_for<S::Q>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
@@ -169,8 +170,7 @@
         });
       };
       auto emit = [&](int k2) {
-        if constexpr (COLL == 1)
-          static_for<CPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, CPB, decltype(kc)::value>(f, p.tau_inv); });
+        static_for<CPB>([&](auto kc) { collide_node<T, S, LAYOUT, CPB, decltype(kc)::value, COLL>(f, p); });
         static_for<S::Q>([&](auto qc) {
           constexpr int q = decltype(qc)::value;
           T *base = p.out + ((long long)q * p.No + (long long)((unsigned)k2 * plane_nodes));
@@ -225,16 +225,7 @@
   // r = index of the plane relative to s - 1; r3 = r % 3
   auto compute_a = [&](int r, int r3) {
     if (in_a) {
-      if constexpr (COLL == 1)
-        static_for<NPT>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau_inv); });
-      if constexpr (COLL == 3)
-        static_for<NPT>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.tau, p.smag_c2); });
-      if constexpr (COLL == 8)
-        static_for<NPT>([&](auto kc) { collide_trt<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.beta, p.smag_c2); });
-      if constexpr (COLL == 9)
-        static_for<NPT>([&](auto kc) { collide_regularized<T, S, LAYOUT, NPT, decltype(kc)::value>(pre, p.smag_c2); });
-      if constexpr ((COLL & 4) != 0)
-        static_for<NPT>([&](auto kc) { collide_forced<T, S, LAYOUT, NPT, decltype(kc)::value, (COLL & 3)>(pre, p); });
+      static_for<NPT>([&](auto kc) { collide_node<T, S, LAYOUT, NPT, decltype(kc)::value, COLL>(pre, p); });
       static_for<S::Q>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         constexpr int e2 = M::e(q, 2), rank = crossing_rank<S, LAYOUT, q>();
@@ -265,16 +256,7 @@
   };
   auto collide_b = [&]() {
     if (in_b) {
-      if constexpr (COLL == 1)
-        static_for<NPB>([&](auto kc) { collide_bgk<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau_inv); });
-      if constexpr (COLL == 3)
-        static_for<NPB>([&](auto kc) { collide_smagorinsky<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.tau, p.smag_c2); });
-      if constexpr (COLL == 8)
-        static_for<NPB>([&](auto kc) { collide_trt<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.beta, p.smag_c2); });
-      if constexpr (COLL == 9)
-        static_for<NPB>([&](auto kc) { collide_regularized<T, S, LAYOUT, NPB, decltype(kc)::value>(f, p.smag_c2); });
-      if constexpr ((COLL & 4) != 0)
-        static_for<NPB>([&](auto kc) { collide_forced<T, S, LAYOUT, NPB, decltype(kc)::value, (COLL & 3)>(f, p); });
+      static_for<NPB>([&](auto kc) { collide_node<T, S, LAYOUT, NPB, decltype(kc)::value, COLL>(f, p); });
     }
   };
   // packing: this workgroup writes halo messages (PACK kernels; a launch that covers a whole slab runs the
@@ -371,7 +353,7 @@
       // the others are neither stored nor (dead code to the compiler) computed.
       auto collide_into_lds = [&](T (&src)[S::Q][1], int r, int r3, auto keep) {
         constexpr int KEEP = decltype(keep)::value;
-        if constexpr (COLL == 1) collide_bgk<T, S, LAYOUT, 1, 0>(src, p.tau_inv);
+        collide_node<T, S, LAYOUT, 1, 0, COLL>(src, p);
         if (in_a) {
           static_for<S::Q>([&](auto qc) {
             constexpr int q = decltype(qc)::value;

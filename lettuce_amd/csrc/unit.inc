@@ -32,10 +32,10 @@
 //                         kernel's SCHED = 1) -- that schedule wants another scheduler setting than the one-role kernels
 //   smagorinsky (inst4_)  3-D units: the one-step kernels of the Smagorinsky collision -- an object of its own so that
 //                         the build takes no longer than before (D3Q27 fp32 with its KBC kernels is the longest job)
-//   forced (inst5_)       every unit: the kernels with a body force (the kernels' COLL = 5: BGK, 7: Smagorinsky) -- every
+//   forced (inst5_)       every unit: the kernels with a body force (the kernels' COLL | kCollForce: BGK, Smagorinsky) -- every
 //                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; objects
 //                         of their own, so that the objects of the unforced kernels are what they were
-//   relaxations (inst6_)  every unit: the TRT and the regularised collision (the kernels' COLL = 8 and 9) -- every
+//   relaxations (inst6_)  every unit: the TRT and the regularised collision (kCollTrt, kCollRegularized) -- every
 //                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; again
 //                         objects of their own: the earlier objects stay what they were and none of these is the longest job
 //   outlets (inst7_)      every unit: the one-step kernels of plans with a constant-pressure outlet (EquilibriumOutletP;
@@ -46,9 +46,9 @@
 //   outlets2 (inst8_)     ... Smagorinsky, TRT and the regularised collision
 //   outlets3 (inst9_)     ... BGK and Smagorinsky with a body force -- three objects, because the chain of depth 2 inlines
 //                         the gather and the collision three times and one object per unit would be the longest job
-//   mrt (inst10_)         units with LT_HAS_MRT: the multiple-relaxation-time collision (the kernels' COLL = 10: Dellar on
-//                         D2Q9, Hermite on D3Q27; 11: Lallemand on D2Q9) -- every one-step variant BGK has, on a parameter
-//                         block of their own (KParamsM); no launch of several steps
+//   mrt (inst10_)         units with LT_HAS_MRT: the multiple-relaxation-time collision (kCollMrt: Dellar on D2Q9,
+//                         Hermite on D3Q27; kCollMrtLallemand: Lallemand on D2Q9) -- every one-step variant BGK has, on
+//                         a parameter block of their own (KParamsM); no launch of several steps
 //   mrt_outlets (inst11_) ... and its kernels of plans with a constant-pressure outlet
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
@@ -110,8 +110,7 @@ constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
 // The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
 // to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
 template <int COLL>
-using ParamsOf = std::conditional_t<COLL == 10 || COLL == 11, KParamsM<T>,
-                                    std::conditional_t<(COLL & 4) != 0, KParamsF<T>, KParams<T>>>;
+using ParamsOf = std::conditional_t<coll_mrt(COLL), KParamsM<T>, std::conditional_t<coll_forced(COLL), KParamsF<T>, KParams<T>>>;
 template <class P>
 P params_of(const StepArgs &a, int n2) {
   P p{};
@@ -131,10 +130,10 @@ P params_of(const StepArgs &a, int n2) {
   p.inv_beta = (T)(1. / beta);
   p.tau = (T)a.tau;
   p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
-  // the collision's own scalar (kernels.hpp, KParams): TRT 1 / (2 tau_minus) beside beta = 1 / (2 tau_plus)
+  // the collision's own scalar (kernels.hpp, collide_node): TRT 1 / (2 tau_minus) beside beta = 1 / (2 tau_plus)
   // (trt_collision.py:22,25), the regularised collision 1 - 1 / tau (regularized_collision.py:42)
-  if (a.coll == 8) p.smag_c2 = (T)(1.0 / (2.0 * a.tau_minus));
-  if (a.coll == 9) p.smag_c2 = (T)(1.0 - 1.0 / a.tau);
+  if (a.coll == kCollTrt) p.smag_c2 = (T)(1.0 / (2.0 * a.tau_minus));
+  if (a.coll == kCollRegularized) p.smag_c2 = (T)(1.0 - 1.0 / a.tau);
   p.node = a.node;
   p.nsm_bits = a.nsm_bits;
   p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
@@ -196,7 +195,7 @@ int kernel_name(const NameBuf &out, const char *kernel, A... args) {
 template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
 int launch(const StepArgs &a, const NameBuf *name) {
   constexpr bool STREAM = MODE != kCollideOnly, COLLIDE = MODE != kStreamOnly;
-  constexpr bool OCC4 = (COLL == 2 && MASKED && sizeof(T) == 4 && S::Q == 27 && ABBD == 0);
+  constexpr bool OCC4 = (COLL == kCollKbc && MASKED && sizeof(T) == 4 && S::Q == 27 && ABBD == 0);
   using P = ParamsOf<COLL>;
   if (name)
     return kernel_name(*name, OCC4 ? "lbm_kernel_occ4" : "lbm_kernel", LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE,
@@ -208,8 +207,8 @@ int launch(const StepArgs &a, const NameBuf *name) {
     kern = lbm_kernel<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK, ABBD>;
   P p = params_of<P>(a, a.n2);
   p.nvec_total = (unsigned)((long long)p.nv0 * a.n1 * a.planes);
-  if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
-  if constexpr (COLL == 10 || COLL == 11) set_mrt(p, a);
+  if constexpr (coll_forced(COLL)) set_force<LAYOUT>(p, a);
+  if constexpr (coll_mrt(COLL)) set_mrt(p, a);
   p.abb0_slot = a.n0 % 64 == 0 ? a.abb0_slot : 0;
   if (p.nvec_total == 0) return 0;
   const unsigned grid = (p.nvec_total + kThreads - 1) / kThreads;
@@ -324,8 +323,9 @@ int pressure_outlets_of(const StepArgs &a, const NameBuf *name) {
 template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
 int launch_twice(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 3 && T0 > 0 &&
-                (COLL == 0 || COLL == 1 ||
-                 ((COLL == 3 || COLL == 5 || COLL == 8 || COLL == 9) && S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
+                (COLL == kCollNone || COLL == kCollBgk ||
+                 ((COLL == kCollSmagorinsky || COLL == (kCollBgk | kCollForce) || COLL == kCollTrt || COLL == kCollRegularized) &&
+                  S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
     using B = TwoStep<T, S, T0, T1>;
     if (name) return kernel_name(*name, "lbm2_kernel", LAYOUT, COLL, T0, T1, 1, MODE, 1, elided(SCHED));
     // in-plane byte offsets are 32-bit in the kernel
@@ -339,7 +339,7 @@ int launch_twice(const StepArgs &a, const NameBuf *name) {
     p.p_end = a.p_begin + a.planes;
     p.p_begin2 = a.p_begin2;
     p.p_end2 = a.p_begin2 + a.planes2;
-    if constexpr ((COLL & 4) != 0) set_force<LAYOUT>(p, a);
+    if constexpr (coll_forced(COLL)) set_force<LAYOUT>(p, a);
     p.nb = a.shift == 3 ? 1 : (a.shift == 4 ? 2 : 0);   // A/B: 1 = no XCD-aware renumbering of the workgroups, 2 = per segment layer
     // MODE 2: the edge workgroups first, each adds 1 to *signal (kernels.hpp, KParams)
     p.signal = MODE == 2 ? a.signal : nullptr;
@@ -364,46 +364,46 @@ int sweep(const StepArgs &a, const NameBuf *name) {
   if constexpr (R > 0) {
 #if LT_PART_IS(roles)
     // BGK with separate producer and consumer waves, where they won their A/B (DESIGN.md section 7)
-    if (a.layout == 0) return launch_twice<0, 1, W, R, 0, 1>(a, name);
-    return launch_twice<1, 1, W, R, 0, 1>(a, name);
+    if (a.layout == 0) return launch_twice<0, kCollBgk, W, R, 0, 1>(a, name);
+    return launch_twice<1, kCollBgk, W, R, 0, 1>(a, name);
 #elif LT_PART_IS(forced)
     // with a body force: plain sweeps of periodic plans (no packing, no signalling launch)
     if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
-    if (a.layout == 0 && a.coll == 5) return launch_twice<0, 5, W, R>(a, name);
-    if (a.layout == 1 && a.coll == 5) return launch_twice<1, 5, W, R>(a, name);
+    if (a.layout == 0 && a.coll == (kCollBgk | kCollForce)) return launch_twice<0, kCollBgk | kCollForce, W, R>(a, name);
+    if (a.layout == 1 && a.coll == (kCollBgk | kCollForce)) return launch_twice<1, kCollBgk | kCollForce, W, R>(a, name);
     // (Smagorinsky with a force, COLL 7: 168 VGPRs and 84-92 bytes of scratch per lane under every scheduler setting
     // where the unforced sweep has 168 and none -- not built, the plan keeps the one-step kernel: DESIGN.md section 4)
 #elif LT_PART_IS(relaxations)
     // TRT and the regularised collision: plain sweeps of periodic plans (no packing, no signalling launch)
     if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
-    if (a.layout == 0 && a.coll == 8) return launch_twice<0, 8, W, R>(a, name);
-    if (a.layout == 1 && a.coll == 8) return launch_twice<1, 8, W, R>(a, name);
-    if (a.layout == 0 && a.coll == 9) return launch_twice<0, 9, W, R>(a, name);
-    if (a.layout == 1 && a.coll == 9) return launch_twice<1, 9, W, R>(a, name);
+    if (a.layout == 0 && a.coll == kCollTrt) return launch_twice<0, kCollTrt, W, R>(a, name);
+    if (a.layout == 1 && a.coll == kCollTrt) return launch_twice<1, kCollTrt, W, R>(a, name);
+    if (a.layout == 0 && a.coll == kCollRegularized) return launch_twice<0, kCollRegularized, W, R>(a, name);
+    if (a.layout == 1 && a.coll == kCollRegularized) return launch_twice<1, kCollRegularized, W, R>(a, name);
 #else
     // the unmasked two-step launches of a 3-D unit
     const int coll = a.coll;
 #if LT_HAS_ROLES
     // the plain BGK sweep: part roles; shift policy 6 runs the one-role schedule (A/B)
-    if (coll == 1 && a.shift != 6 && (a.layout == 0 || !(a.pack_lo || a.pack_hi || a.signal)))
+    if (coll == kCollBgk && a.shift != 6 && (a.layout == 0 || !(a.pack_lo || a.pack_hi || a.signal)))
       return LT_CAT(roles_, LT_TAG)(a, name);
 #endif
-    if (a.layout == 0 && coll == 0) return launch_twice<0, 0, W, R>(a, name);
-    if (a.layout == 0 && coll == 1) return launch_twice<0, 1, W, R>(a, name);
-    if (a.layout == 0 && coll == 3) return launch_twice<0, 3, W, R>(a, name);
+    if (a.layout == 0 && coll == kCollNone) return launch_twice<0, kCollNone, W, R>(a, name);
+    if (a.layout == 0 && coll == kCollBgk) return launch_twice<0, kCollBgk, W, R>(a, name);
+    if (a.layout == 0 && coll == kCollSmagorinsky) return launch_twice<0, kCollSmagorinsky, W, R>(a, name);
     // Smagorinsky has the plain sweep only: no edge launch with packing, no signalling launch
-    if (coll == 3 && (a.pack_lo || a.pack_hi || a.signal)) return kNoKernel;
+    if (coll == kCollSmagorinsky && (a.pack_lo || a.pack_hi || a.signal)) return kNoKernel;
     if (a.layout == 1 && (a.pack_lo || a.pack_hi)) {     // slab edge launch with fused halo packing
-      if (coll == 0) return launch_twice<1, 0, W, R, 1>(a, name);
-      if (coll == 1) return launch_twice<1, 1, W, R, 1>(a, name);
+      if (coll == kCollNone) return launch_twice<1, kCollNone, W, R, 1>(a, name);
+      if (coll == kCollBgk) return launch_twice<1, kCollBgk, W, R, 1>(a, name);
     }
     if (a.layout == 1 && a.signal) {                     // whole slab, edge workgroups first
-      if (coll == 0) return launch_twice<1, 0, W, R, 2>(a, name);
-      if (coll == 1) return launch_twice<1, 1, W, R, 2>(a, name);
+      if (coll == kCollNone) return launch_twice<1, kCollNone, W, R, 2>(a, name);
+      if (coll == kCollBgk) return launch_twice<1, kCollBgk, W, R, 2>(a, name);
     }
-    if (a.layout == 1 && coll == 0) return launch_twice<1, 0, W, R>(a, name);
-    if (a.layout == 1 && coll == 1) return launch_twice<1, 1, W, R>(a, name);
-    if (a.layout == 1 && coll == 3) return launch_twice<1, 3, W, R>(a, name);
+    if (a.layout == 1 && coll == kCollNone) return launch_twice<1, kCollNone, W, R>(a, name);
+    if (a.layout == 1 && coll == kCollBgk) return launch_twice<1, kCollBgk, W, R>(a, name);
+    if (a.layout == 1 && coll == kCollSmagorinsky) return launch_twice<1, kCollSmagorinsky, W, R>(a, name);
 #endif
   }
   return kNoKernel;
@@ -420,13 +420,13 @@ int launch_twice_masked(const StepArgs &a, const NameBuf *name) {
   // BGK / streaming on tiles of 8 rows (4 for D3Q27 fp32).  KBC inside this kernel (256 VGPRs, spills: not faster
   // than one update per launch) and 4-row fp64 tiles of D3Q19 (slower than one update per launch) lost their A/B
   // (DESIGN.md section 4)
-  if constexpr (S::D == 3 && T0 > 0 && (COLL == 0 || COLL == 1) && !(sizeof(T) == 8 && T1 == 4)) {
+  if constexpr (S::D == 3 && T0 > 0 && (COLL == kCollNone || COLL == kCollBgk) && !(sizeof(T) == 8 && T1 == 4)) {
     if constexpr (two_step_masked_lds<T, S, LAYOUT, T0, T1>() <= 160 * 1024) {
       using B = TwoStep<T, S, T0, T1>;
       if (name) return kernel_name(*name, "lbm2m_kernel", LAYOUT, COLL, T0, T1, AX);
       // (D3Q27: 26.7 GLUPS at 384^3 against 27.2 with one update per launch -- its 2 x 27 population bases spill;
       // D3Q19: 52-55 GLUPS at 384^3 / 512^3 against 38: profiles/r04y_large_obstacle.jsonl)
-      constexpr bool kHasBig = LAYOUT == 0 && COLL == 1 && S::Q <= 19;
+      constexpr bool kHasBig = LAYOUT == 0 && COLL == kCollBgk && S::Q <= 19;
       const long long pop_bytes = std::max(std::max(a.stride_in, a.stride_out), (long long)a.n0 * a.n1 * a.n2) * (long long)sizeof(T);
       const bool big = (long long)S::Q * pop_bytes >= (1ll << 32);
       if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 2 || !a.masked || a.planes < 2 || a.p_stride != 1 ||
@@ -458,7 +458,7 @@ int launch_twice_masked(const StepArgs &a, const NameBuf *name) {
 // lbm2d2m_kernel: api.hip admits the plan (masked_two_step_axis)
 template <int COLL, int W, bool MASKED>
 int launch_twice2d(const StepArgs &a, const NameBuf *name) {
-  if constexpr (S::D == 2 && (COLL == 0 || COLL == 1)) {
+  if constexpr (S::D == 2 && (COLL == kCollNone || COLL == kCollBgk)) {
     if (name) return kernel_name(*name, MASKED ? "lbm2d2m_kernel" : "lbm2d2_kernel", COLL, W);
     if (a.layout != 0 || (a.masked != 0) != MASKED || a.n0 % W != 0 || a.seg_len < (MASKED ? 2 : 1) ||
         a.n1 < (MASKED ? 3 : 1) || a.n2 != 1)
@@ -478,7 +478,7 @@ int launch_twice2d(const StepArgs &a, const NameBuf *name) {
 constexpr int kManyTile = 8, kManyMax = 8;
 template <int COLL, bool MASKED>
 int launch_many(const StepArgs &a, const NameBuf *name) {
-  if constexpr (S::D == 2 && (COLL != 2 || LT_HAS_KBC)) {
+  if constexpr (S::D == 2 && (COLL != kCollKbc || LT_HAS_KBC)) {
     using G = ManyStep2D<kManyTile, kManyTile, kManyMax>;
     if (name) return kernel_name(*name, "lbm_many_kernel", COLL, kManyTile, kManyTile, kManyMax, elided(MASKED));
     // plans with an outlet recompute one more ring: one step fewer per launch
@@ -526,10 +526,10 @@ int twice_3d(const StepArgs &a, const NameBuf *name) {
 #define LT_TRY_MASKED_TWICE(LAYOUT_, COLL_, AX_)                       \
   if (a.layout == LAYOUT_ && a.coll == COLL_ && a.abb_axis == AX_)     \
     return launch_twice_masked<LAYOUT_, COLL_, W, RM, AX_>(a, name);
-    LT_TRY_MASKED_TWICE(0, 0, 2) LT_TRY_MASKED_TWICE(0, 1, 2)
-    LT_TRY_MASKED_TWICE(0, 0, 0) LT_TRY_MASKED_TWICE(0, 1, 0)
-    LT_TRY_MASKED_TWICE(1, 0, 2) LT_TRY_MASKED_TWICE(1, 1, 2)
-    LT_TRY_MASKED_TWICE(1, 0, 0) LT_TRY_MASKED_TWICE(1, 1, 0)
+    LT_TRY_MASKED_TWICE(0, kCollNone, 2) LT_TRY_MASKED_TWICE(0, kCollBgk, 2)
+    LT_TRY_MASKED_TWICE(0, kCollNone, 0) LT_TRY_MASKED_TWICE(0, kCollBgk, 0)
+    LT_TRY_MASKED_TWICE(1, kCollNone, 2) LT_TRY_MASKED_TWICE(1, kCollBgk, 2)
+    LT_TRY_MASKED_TWICE(1, kCollNone, 0) LT_TRY_MASKED_TWICE(1, kCollBgk, 0)
 #undef LT_TRY_MASKED_TWICE
   }
   return kNoKernel;
@@ -537,18 +537,18 @@ int twice_3d(const StepArgs &a, const NameBuf *name) {
 #endif
 
 int dispatch(const StepArgs &a, const NameBuf *name) {
-  const int coll = a.mode == kStreamOnly ? 0 : a.coll;   // streaming does not depend on it
+  const int coll = a.mode == kStreamOnly ? kCollNone : a.coll;   // streaming does not depend on it
   // a constant-pressure outlet: part outlets has the kernels that apply boundaries (streaming alone applies none)
   if (a.n_pout > 0 && a.mode != kStreamOnly) return LT_CAT(outlets_, LT_TAG)(a, name);
-  if (coll & 4) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
-  if (coll == 8 || coll == 9) return LT_CAT(relax_, LT_TAG)(a, name);   // TRT, regularised: part relaxations
+  if (coll_forced(coll)) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
+  if (coll == kCollTrt || coll == kCollRegularized) return LT_CAT(relax_, LT_TAG)(a, name);   // part relaxations
 #if LT_HAS_MRT
-  if (coll == 10 || coll == 11) return LT_CAT(mrt_, LT_TAG)(a, name);   // MRT: part mrt
+  if (coll_mrt(coll)) return LT_CAT(mrt_, LT_TAG)(a, name);   // MRT: part mrt
 #endif
   if (a.mode == kFusedMany) {
-    if (coll == 0) return many_of<0>(a, name);
-    if (coll == 1) return many_of<1>(a, name);
-    if (coll == 2) return many_of<2>(a, name);
+    if (coll == kCollNone) return many_of<kCollNone>(a, name);
+    if (coll == kCollBgk) return many_of<kCollBgk>(a, name);
+    if (coll == kCollKbc) return many_of<kCollKbc>(a, name);
     return kNoKernel;
   }
   if (a.mode == kFusedTwice) {
@@ -556,29 +556,29 @@ int dispatch(const StepArgs &a, const NameBuf *name) {
     return twice_3d(a, name);
 #else
     if (S::D != 2 || a.layout != 0) return kNoKernel;
-    if (coll == 0) return strips_of<0>(a, name);
-    if (coll == 1) return strips_of<1>(a, name);
+    if (coll == kCollNone) return strips_of<kCollNone>(a, name);
+    if (coll == kCollBgk) return strips_of<kCollBgk>(a, name);
     return kNoKernel;
 #endif
   }
   if (a.mode == kStreamOnly) {      // the one kernel that does not collide: no check of the outlet depth
-    LT_TRY(0, 0, kStreamOnly, 0)
-    LT_TRY(0, 0, kStreamOnly, 1)
+    LT_TRY(0, kCollNone, kStreamOnly, 0)
+    LT_TRY(0, kCollNone, kStreamOnly, 1)
 #if LT_IS_3D
-    LT_TRY(1, 0, kStreamOnly, 0)
-    LT_TRY(1, 0, kStreamOnly, 1)
+    LT_TRY(1, kCollNone, kStreamOnly, 0)
+    LT_TRY(1, kCollNone, kStreamOnly, 1)
 #endif
     return kNoKernel;
   }
-  if (coll == 0) return one_step_of<0>(a, name);
-  if (coll == 1) return one_step_of<1>(a, name);
+  if (coll == kCollNone) return one_step_of<kCollNone>(a, name);
+  if (coll == kCollBgk) return one_step_of<kCollBgk>(a, name);
 #if LT_HAS_KBC
-  if (coll == 2) return one_step_of<2>(a, name);
+  if (coll == kCollKbc) return one_step_of<kCollKbc>(a, name);
 #endif
 #if LT_IS_3D
-  if (coll == 3) return LT_CAT(smag_, LT_TAG)(a, name);       // part smagorinsky
+  if (coll == kCollSmagorinsky) return LT_CAT(smag_, LT_TAG)(a, name);       // part smagorinsky
 #else
-  if (coll == 3) return one_step_of<3>(a, name);
+  if (coll == kCollSmagorinsky) return one_step_of<kCollSmagorinsky>(a, name);
 #endif
   return kNoKernel;
 }
@@ -696,12 +696,12 @@ int LT_CAT(twice_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return swee
 #elif LT_PART_IS(roles)
 int LT_CAT(roles_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep(a, name); }
 #elif LT_PART_IS(smagorinsky)
-int LT_CAT(smag_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_of<3>(a, name); }
+int LT_CAT(smag_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_of<kCollSmagorinsky>(a, name); }
 #elif LT_PART_IS(forced)
 int LT_CAT(forced_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
-  if (a.coll == 5) return one_step_of<5>(a, name);
-  if (a.coll == 7) return one_step_of<7>(a, name);
+  if (a.coll == (kCollBgk | kCollForce)) return one_step_of<kCollBgk | kCollForce>(a, name);
+  if (a.coll == (kCollSmagorinsky | kCollForce)) return one_step_of<kCollSmagorinsky | kCollForce>(a, name);
   return kNoKernel;
 }
 #elif LT_PART_IS(relaxations)
@@ -709,8 +709,8 @@ int LT_CAT(forced_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
 int LT_CAT(relax_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
   if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == 8) return one_step_of<8>(a, name);
-  if (a.coll == 9) return one_step_of<9>(a, name);
+  if (a.coll == kCollTrt) return one_step_of<kCollTrt>(a, name);
+  if (a.coll == kCollRegularized) return one_step_of<kCollRegularized>(a, name);
   return kNoKernel;
 }
 #elif LT_PART_IS(outlets)
@@ -718,47 +718,47 @@ int LT_CAT(relax_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
 int LT_CAT(outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
   switch (a.coll) {
-    case 0: return pressure_outlets_of<0>(a, name);
-    case 1: return pressure_outlets_of<1>(a, name);
+    case kCollNone: return pressure_outlets_of<kCollNone>(a, name);
+    case kCollBgk: return pressure_outlets_of<kCollBgk>(a, name);
 #if LT_HAS_KBC
-    case 2: return pressure_outlets_of<2>(a, name);
+    case kCollKbc: return pressure_outlets_of<kCollKbc>(a, name);
 #endif
-    case 3: case 8: case 9: return LT_CAT(outlets2_, LT_TAG)(a, name);
-    case 5: case 7: return LT_CAT(outlets3_, LT_TAG)(a, name);
+    case kCollSmagorinsky: case kCollTrt: case kCollRegularized: return LT_CAT(outlets2_, LT_TAG)(a, name);
+    case kCollBgk | kCollForce: case kCollSmagorinsky | kCollForce: return LT_CAT(outlets3_, LT_TAG)(a, name);
 #if LT_HAS_MRT
-    case 10: case 11: return LT_CAT(mrt_outlets_, LT_TAG)(a, name);
+    case kCollMrt: case kCollMrtLallemand: return LT_CAT(mrt_outlets_, LT_TAG)(a, name);
 #endif
     default: return kNoKernel;
   }
 }
 #elif LT_PART_IS(outlets2)
 int LT_CAT(outlets2_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.coll == 3) return pressure_outlets_of<3>(a, name);
-  if (a.coll == 8) return pressure_outlets_of<8>(a, name);
-  if (a.coll == 9) return pressure_outlets_of<9>(a, name);
+  if (a.coll == kCollSmagorinsky) return pressure_outlets_of<kCollSmagorinsky>(a, name);
+  if (a.coll == kCollTrt) return pressure_outlets_of<kCollTrt>(a, name);
+  if (a.coll == kCollRegularized) return pressure_outlets_of<kCollRegularized>(a, name);
   return kNoKernel;
 }
 #elif LT_PART_IS(outlets3)
 int LT_CAT(outlets3_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.coll == 5) return pressure_outlets_of<5>(a, name);
-  if (a.coll == 7) return pressure_outlets_of<7>(a, name);
+  if (a.coll == (kCollBgk | kCollForce)) return pressure_outlets_of<kCollBgk | kCollForce>(a, name);
+  if (a.coll == (kCollSmagorinsky | kCollForce)) return pressure_outlets_of<kCollSmagorinsky | kCollForce>(a, name);
   return kNoKernel;
 }
 #elif LT_PART_IS(mrt)
 // one-step kernels only; the transform picks the kernels' COLL (api.hip, kernel_coll)
 int LT_CAT(mrt_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == 10) return one_step_of<10>(a, name);
+  if (a.coll == kCollMrt) return one_step_of<kCollMrt>(a, name);
 #if !LT_IS_3D
-  if (a.coll == 11) return one_step_of<11>(a, name);
+  if (a.coll == kCollMrtLallemand) return one_step_of<kCollMrtLallemand>(a, name);
 #endif
   return kNoKernel;
 }
 #elif LT_PART_IS(mrt_outlets)
 int LT_CAT(mrt_outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.coll == 10) return pressure_outlets_of<10>(a, name);
+  if (a.coll == kCollMrt) return pressure_outlets_of<kCollMrt>(a, name);
 #if !LT_IS_3D
-  if (a.coll == 11) return pressure_outlets_of<11>(a, name);
+  if (a.coll == kCollMrtLallemand) return pressure_outlets_of<kCollMrtLallemand>(a, name);
 #endif
   return kNoKernel;
 }

@@ -24,8 +24,12 @@ def _units(text):
     return units
 
 
+def _hipcc():
+    return "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+
+
 def test_every_unit_names_the_same_kernel_for_every_selector(engine_library, tmp_path):
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc not available")
     libdir = os.path.dirname(engine_library)
@@ -44,3 +48,20 @@ def test_every_unit_names_the_same_kernel_for_every_selector(engine_library, tmp
             assert g == w, f"{unit}: line {i + 1} of its table is {g!r}, the fixture has {w!r}"
         assert len(got[unit]) == len(want[unit]), (unit, len(got[unit]), len(want[unit]))
     assert out.stdout == open(os.path.join(ROOT, "tests", "dispatch_table.txt")).read()
+
+
+def test_collision_numbers_and_their_predicates(tmp_path):
+    """dispatch.hpp's names for the kernels' collision numbers: tests/aux/collision_numbers.cpp holds every number, and
+    coll_forced / coll_mrt / coll_base of it, against the values written out (5 and 7 forced, on 1 and 3; 10 and 11 MRT;
+    8 and 9 neither), and the names against the ABI's lt_collision where they coincide.  Host code only."""
+    hipcc = _hipcc()
+    assert hipcc is not None, "the engine is built with hipcc"
+    exe = tmp_path / "collision_numbers"
+    subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-O1", "-Wall", "-Werror",
+                    "-I" + os.path.join(ROOT, "lettuce_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "aux", "collision_numbers.cpp"), "-o", str(exe)],
+                   check=True, capture_output=True, timeout=600)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(out.stdout)
+    assert out.returncode == 0, out.stdout
+    assert len(out.stdout.splitlines()) == 10 and "wrong" not in out.stdout

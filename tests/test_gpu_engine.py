@@ -701,8 +701,12 @@ def _check_masked_two_step(plan, f0, refused, res, seg, name="lbm2m_kernel"):
         seg = 2 if res[0] % 2 == 0 else 0
     plan.set_two_step(1, seg)
     if refused:
-        with pytest.raises(Exception, match="two steps per launch"):
+        # the masks' admission, as the launch words it and as lt_plan_two_step_admitted does
+        with pytest.raises(Exception, match="two steps per launch with boundaries: at most one anti-bounce-back outlet, at the "
+                                            "last plane of the slowest memory axis"):
             plan.stream_collide_twice(f, c, 0.7)
+        assert plan.two_step_admitted().startswith("two steps per launch: boundaries: at most one anti-bounce-back outlet, at "
+                                                   "the last plane of the slowest memory axis"), plan.two_step_admitted()
         return
     plan.stream_collide_twice(f, c, 0.7)
     torch.cuda.synchronize()

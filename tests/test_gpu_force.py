@@ -575,11 +575,14 @@ def test_multi_step_entry_points_name_the_force():
     two_d.set_two_step(1)
     two_d.set_many_step(1)
     f = dev(perturbed_state("D2Q9", [16, 128], torch.float64, 3))
-    for call in (lambda: two_d.stream_collide_many(f, torch.empty_like(f), tau, 4),
-                 lambda: two_d.stream_collide_twice(f, torch.empty_like(f), tau)):
+    reason = ("a body force (lt_plan_set_force) has the one-step kernels and the plain two-step sweep of periodic D3Q19 fp32 "
+              "plans without masks only: no many-step, 2-D, masked, role-wave or slab two-step kernel takes it")
+    for call, steps in ((lambda: two_d.stream_collide_many(f, torch.empty_like(f), tau, 4), "several steps"),
+                        (lambda: two_d.stream_collide_twice(f, torch.empty_like(f), tau), "two steps")):
         with pytest.raises(NativeEngineError, match="body force") as refusal:
             call()
         assert refusal.value.code == 2                               # LT_ERR_UNSUPPORTED
+        assert f"{steps} per launch: {reason}" in str(refusal.value), str(refusal.value)
     assert "body force" in two_d.two_step_admitted()
     for lat, dt, res in (("D3Q19", "f64", [5, 24, 96]), ("D3Q27", "f32", [6, 12, 128]), ("D3Q15", "f32", [6, 16, 128])):
         plan = forced_plan(lat, dt, res, "guo", "bgk")
