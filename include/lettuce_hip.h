@@ -82,6 +82,9 @@ enum lt_boundary_kind {
   LT_BOUNDARY_PRESSURE_OUTLET = 4
 };
 enum lt_layout { LT_LAYOUT_REFERENCE = 0, LT_LAYOUT_SLAB = 1 };
+/* lettuce/ext/_equilibrium/quadratic_equilibrium.py:11-25 (and quadratic_equilibrium_less_memory.py:14-30, the same
+ * arithmetic), incompressible_quadratic_equilibrium.py:10-26 (lt_plan_set_equilibrium; lt_equilibrium is a function) */
+enum lt_equilibrium_kind { LT_EQUILIBRIUM_QUADRATIC = 0, LT_EQUILIBRIUM_INCOMPRESSIBLE = 1 };
 #define LT_BOUNDARY_ABSENT 1
 
 /* One entry of Simulation.boundaries[1:] (lettuce/_simulation.py:57-58); entry i (0-based)
@@ -289,7 +292,8 @@ int lt_plan_set_deferred_stream(lt_plan *plan, int32_t on);
 int lt_macroscopic(lt_plan *plan, const void *f_dev, void *rho_dev, void *u_dev, void *stream);
 
 /* feq [q, *res] from rho [*res] and u [d, *res]
- * (QuadraticEquilibrium.__call__, lettuce/ext/_equilibrium/quadratic_equilibrium.py:11-25). */
+ * (QuadraticEquilibrium.__call__, lettuce/ext/_equilibrium/quadratic_equilibrium.py:11-25; the plan's equilibrium:
+ * lt_plan_set_equilibrium). */
 int lt_equilibrium(lt_plan *plan, const void *rho_dev, const void *u_dev, void *feq_dev,
                    void *stream);
 
@@ -470,6 +474,22 @@ int lt_plan_set_mrt(lt_plan *plan, int transform, const double *relaxation, int 
  * lt_plan_two_step_admitted return LT_ERR_UNSUPPORTED with a reason that names the force. */
 int lt_plan_set_force(lt_plan *plan, const double *acceleration /* dims values, or NULL */, double ueq_scale,
                       double source_scale);
+/* The equilibrium of the plan, lt_equilibrium_kind: LT_EQUILIBRIUM_QUADRATIC (what every plan has until this is called;
+ * rho0 is not read) or LT_EQUILIBRIUM_INCOMPRESSIBLE,
+ *   feq_q = w_q (rho + rho0 ((2 e_q.u - u.u) / (2 cs^2) + (e_q.u / cs^2)^2 / 2)),   u = j / rho
+ * (incompressible_quadratic_equilibrium.py:14-26; rho0 is rounded to the plan's scalar type once).  Kind and rho0 are
+ * read at every launch, so they may change between calls like tau: lt_collide, lt_stream_collide, lt_run, lt_continue
+ * (one update per launch), lt_equilibrium and lt_init_fneq evaluate this equilibrium.  The boundaries' populations
+ * (lt_boundary_desc.feq) are the caller's, whatever the kind.  A plan that never called this, or set kind 0, launches
+ * exactly what it launched before.  Kind 1 has the one-step kernels of no collision, BGK (with or without
+ * lt_plan_set_force), TRT and the regularised collision, every lattice and dtype, reference layout, with or without masks
+ * (bounce-back, equilibrium boundaries, anti-bounce-back outlets).  Refused, with the plan unchanged:
+ * LT_ERR_INVALID for an unknown kind, a non-finite rho0 and a null plan; LT_ERR_UNSUPPORTED for kind 1 on a plan with
+ * KBC, Smagorinsky or MRT, on a slab-layout plan and on a plan with a constant-pressure outlet.  A kind-1 plan has no launch of several steps: lt_run, lt_continue and lt_resident_advance
+ * keep one update per launch; lt_plan_set_two_step(plan, 1, ...), lt_plan_set_many_step(plan, 1), the explicit
+ * multi-step entry points and lt_plan_two_step_admitted return LT_ERR_UNSUPPORTED with a reason that names the
+ * equilibrium.  lt_plan_desc keeps its size and LT_ABI_VERSION its value. */
+int lt_plan_set_equilibrium(lt_plan *plan, int kind, double rho0);
 /* Population stride.  By default a population buffer is dense: population q starts q * nodes elements after
  * population 0 (the reference's [q, *res] tensor, lettuce/_flow.py:90).  With the q populations a power of two
  * apart (256^3 fp32: exactly 64 MiB) the q read and q write streams of a node meet in the same memory channels;

@@ -162,6 +162,19 @@ class Flow(ABC):
                                      device=f.device)
         return self._moment_plan
 
+    def _engine_equilibrium(self):
+        """``(kind, rho0)`` of this flow's equilibrium as the engine's plans take it (``Plan.set_equilibrium``), or None
+        when the engine has no kernel for it: every shortcut that evaluates feq on the engine then steps aside and the
+        torch expressions run.  Read late, on every use, like the relaxation time."""
+        eq = self.equilibrium
+        if eq is None or not eq.native_available():
+            return None
+        from ._native import EQUILIBRIUM_IDS
+        desc = eq.native_generator()
+        if getattr(desc, "kind", None) not in EQUILIBRIUM_IDS:
+            return None
+        return desc.plan_args()
+
     # ---- moments (lettuce/_flow.py:136-181) ---------------------------------------------------
     def rho(self, f: Optional[torch.Tensor] = None) -> torch.Tensor:
         """density, shape [1, *resolution]"""
@@ -281,7 +294,9 @@ def initialize_f_neq(flow: "Flow"):
     of u (lettuce/_flow.py:309-336; Krueger et al. 2017)."""
     d = flow.stencil.d
     plan = flow._engine_plan(flow.f) if d >= 2 else None
-    if plan is not None:
+    equilibrium = flow._engine_equilibrium()        # None: an equilibrium of the caller's, the torch expressions below
+    if plan is not None and equilibrium is not None:
+        plan.set_equilibrium(*equilibrium)
         # one launch of the engine (lt_init_fneq): the moments of the equilibrium populations, then
         # gradients, Pi1:Q and feq per node -- no [d, d, *res] / [q, *res] temporaries, no BLAS.
         # The reference's identity is built in torch's default dtype: an fp32-rounded cs^2.

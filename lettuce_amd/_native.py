@@ -37,6 +37,8 @@ MORE_COLLISION_IDS = {"trt": 8, "regularized": 9}
 MRT_COLLISION_IDS = {"mrt": 10}
 # lt_mrt_transform, by the class name of the moment transform (lettuce_amd/moments.py)
 MRT_TRANSFORM_IDS = {"D2Q9Dellar": 1, "D2Q9Lallemand": 2, "D3Q27Hermite": 3}
+# lt_equilibrium_kind, by the kind of a NativeEquilibrium
+EQUILIBRIUM_IDS = {"quadratic": 0, "incompressible": 1}
 BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3, "pressure_outlet": 4}
 LAYOUT_REFERENCE, LAYOUT_SLAB = 0, 1
 
@@ -109,6 +111,7 @@ SYMBOLS = {
     "lt_plan_set_trt": (ctypes.c_int, [_vp, _dbl]),
     "lt_plan_set_mrt": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(ctypes.c_double), _i32]),
     "lt_plan_set_force": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _dbl, _dbl]),
+    "lt_plan_set_equilibrium": (ctypes.c_int, [_vp, ctypes.c_int, _dbl]),
     "lt_stream_collide_twice_planes": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp]),
     "lt_stream_collide_twice_planes_packed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp, _vp, _vp]),
     "lt_stream_collide_twice_edges": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i32, _vp, _vp, _vp]),
@@ -763,6 +766,13 @@ class Plan:
             raise NativeEngineError(f"acceleration has {len(values)} components, the lattice {len(self.resolution)}")
         array = (ctypes.c_double * len(values))(*values)
         self._check(self.lib.lt_plan_set_force(self._handle, array, float(ueq_scale), float(source_scale)))
+
+    def set_equilibrium(self, kind: str = "quadratic", rho0: float = 1.0):
+        """The plan's equilibrium (lt_plan_set_equilibrium), read at every launch like tau: "quadratic" or
+        "incompressible" with its reference density ``rho0``.  collide, run, equilibrium and init_fneq evaluate it."""
+        if kind not in EQUILIBRIUM_IDS:
+            raise NativeEngineError(f"equilibrium {kind!r} has no HIP kernels (available: {sorted(EQUILIBRIUM_IDS)})")
+        self._check(self.lib.lt_plan_set_equilibrium(self._handle, EQUILIBRIUM_IDS[kind], float(rho0)))
 
     def set_two_step(self, mode: int = -1, planes_per_workgroup: int = 0):
         """lt_run pairs fused steps into two-step launches: -1 automatic, 0 never, 1 when supported"""

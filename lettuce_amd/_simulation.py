@@ -98,10 +98,16 @@ class _NativeStepper:
             problems.append(f"stencil '{lattice}' (kernels exist for {sorted(STENCIL_IDS)})")
         if ctx.dtype not in (torch.float32, torch.float64):
             problems.append(f"dtype {ctx.dtype} (float32/float64 only)")
-        if flow.equilibrium is not None and not flow.equilibrium.native_available():
+        equilibrium = flow._engine_equilibrium() if flow.equilibrium is not None else ("quadratic", 1.0)
+        if equilibrium is None:
             problems.append(f"equilibrium '{type(flow.equilibrium).__name__}'")
         if not sim.collision.native_available():
             problems.append(f"collision '{type(sim.collision).__name__}'")
+        elif equilibrium is not None and equilibrium[0] != "quadratic":
+            from .ext._collision import INCOMPRESSIBLE_COLLISIONS
+            if sim.collision.native_generator().kind not in INCOMPRESSIBLE_COLLISIONS:
+                problems.append(f"equilibrium '{type(flow.equilibrium).__name__}' with collision "
+                                f"'{type(sim.collision).__name__}' (its kernels: no collision, BGK, TRT, regularised)")
         for b in sim.boundaries[1:]:
             if not b.native_available():
                 problems.append(f"boundary '{type(b).__name__}'")
@@ -116,6 +122,8 @@ class _NativeStepper:
         self._entries = [b.plan_entry(flow) for b in self.boundaries]
         self.plan = Plan(lattice, ctx.dtype, self.collision.kind, flow.resolution, self._entries,
                          device=ctx.device)
+        if equilibrium[0] != "quadratic":
+            self.plan.set_equilibrium(*equilibrium)     # (the engine refuses a boundary it cannot pair with it, by name)
         if getattr(self.collision, "arithmetic", "exact") != "exact":
             raise NativeEngineError(f"{self.collision.arithmetic!r} arithmetic: the engine has only the reference's "
                                     f"(\"exact\"); fast arithmetic missed its bar (DESIGN.md section 4)")
@@ -213,6 +221,12 @@ class _NativeStepper:
             force = self.collision.force.plan_args()
             self.plan.set_force(*force)
             key = (key, force)
+        # the flow's equilibrium: kind and rho0 are re-read per batch too; a change starts from flow.f
+        equilibrium = flow._engine_equilibrium() if flow.equilibrium is not None else ("quadratic", 1.0)
+        if equilibrium is None:
+            raise NativeEngineError(f"the HIP engine has no kernel for equilibrium '{type(flow.equilibrium).__name__}'")
+        self.plan.set_equilibrium(*equilibrium)
+        key = (key, equilibrium)
         if self.plan.resident_enabled()[0]:
             try:
                 return self._batch_resident(k, tau, key)

@@ -407,6 +407,11 @@ class SlabSimulation:
     def __init__(self, flow, collision, slab: ZSlab, reporter=None, engine=None, group=None,
                  overlap: bool = True, comm_priority: int = -1, transport: str = "rccl",
                  copy_streams: Optional[int] = None):
+        # the slab kernels evaluate the quadratic equilibrium (lt_plan_set_equilibrium: reference layout only)
+        equilibrium = flow._engine_equilibrium() if flow.equilibrium is not None else ("quadratic", 1.0)
+        if equilibrium is None or equilibrium[0] != "quadratic":
+            raise LettuceException(f"equilibrium '{type(flow.equilibrium).__name__}' has no slab kernel: the slab "
+                                   f"simulations run the quadratic equilibrium only")
         if list(flow.resolution) != slab.extended_resolution:
             raise LettuceException(f"flow resolution {flow.resolution} != extended slab "
                                    f"{slab.extended_resolution}")

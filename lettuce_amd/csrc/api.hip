@@ -149,6 +149,10 @@ struct lt_plan {
              source_scale == o.source_scale;
     }
   } force;
+  // the equilibrium (lt_plan_set_equilibrium): lt_equilibrium_kind and, for the incompressible one, its rho0; read at
+  // every launch like tau
+  int equilibrium = LT_EQUILIBRIUM_QUADRATIC;
+  double rho0 = 1.0;
   int two_step = -1;         // lt_run: pair the fused steps (lbm2_kernel): -1 = automatic, 0 / 1
   int seg_len = 0;           // planes per workgroup of the two-step kernel, 0 = automatic
   int many = -1;             // lt_run: several steps per launch on small 2-D grids: -1 = automatic, 0 / 1
@@ -202,7 +206,7 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau, smagorinsky, tau_minus; int masked, tune, shift, residency; Force force; Mrt mrt; } gkey = {};
+  struct { void *a, *b; double tau, smagorinsky, tau_minus; int masked, tune, shift, residency; Force force; Mrt mrt; int equilibrium; double rho0; } gkey = {};
 };
 
 namespace {
@@ -539,7 +543,9 @@ bool canary_ok(lt_plan *p);
 int kernel_coll(const lt_plan *p) {
   if (p->desc.collision == LT_COLLISION_MRT)
     return p->mrt.transform == LT_MRT_D2Q9_LALLEMAND ? lt::kCollMrtLallemand : lt::kCollMrt;
-  return p->desc.collision | (p->force.on ? lt::kCollForce : 0);
+  // the incompressible equilibrium: the collisions that evaluate feq get kernels of their own (no collision does not)
+  const bool incompressible = p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE && p->desc.collision != LT_COLLISION_NONE;
+  return p->desc.collision | (p->force.on ? lt::kCollForce : 0) | (incompressible ? lt::kCollIncompressible : 0);
 }
 static_assert(lt::kCollNone == LT_COLLISION_NONE && lt::kCollBgk == LT_COLLISION_BGK && lt::kCollKbc == LT_COLLISION_KBC &&
               lt::kCollSmagorinsky == LT_COLLISION_SMAGORINSKY && lt::kCollTrt == LT_COLLISION_TRT &&
@@ -565,6 +571,8 @@ const char *const kPressureOutletMultiStep = "a constant-pressure outlet (Equili
                                              "takes it";
 const char *const kMrtMultiStep = "the MRT collision has the one-step kernels only: no two-step, many-step or "
                                   "two-ghost-plane slab kernel takes it";
+const char *const kIncompressibleMultiStep = "the incompressible equilibrium (lt_plan_set_equilibrium) has the one-step kernels "
+                                             "only: no two-step or many-step kernel takes it";
 const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
                                       "edge, packed or signalling launches): slabs keep the one-step kernels";
 // (step() says "two steps per launch with" in front of it, the admission "two steps per launch: ")
@@ -583,6 +591,7 @@ const char *multi_step_refusal(const lt_plan *p, int mode) {
   // relaxations): the plain two-step sweep of periodic D3Q19 fp32 plans without masks
   const bool plain_sweep = twice && p->unit.d == 3 && !p->masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
                            p->desc.dtype == LT_F32;
+  if (p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE) return kIncompressibleMultiStep;   // (unit.inc, part incompressible)
   if (p->force.on) {
     if (!plain_sweep) return kForceMultiStep;
     lt::StepArgs a;
@@ -652,6 +661,7 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   std::copy(p->mrt.rates, p->mrt.rates + 27, a.mrt_rates);
   a.accel[0] = p->force.a[0]; a.accel[1] = p->force.a[1]; a.accel[2] = p->force.a[2];
   a.ueq_scale = p->force.ueq_scale; a.source_scale = p->force.source_scale;
+  a.rho0 = p->rho0;
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
   a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = mode;
   a.masked = p->masked;
@@ -716,7 +726,8 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
   }
   const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.smagorinsky == p->smagorinsky &&
                     p->gkey.tau_minus == p->tau_minus &&
-                    p->gkey.force == p->force && p->gkey.mrt == p->mrt &&
+                    p->gkey.force == p->force && p->gkey.mrt == p->mrt && p->gkey.equilibrium == p->equilibrium &&
+                    p->gkey.rho0 == p->rho0 &&
                     p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
                     p->gkey.shift == p->shift;
   if (!same) {
@@ -736,7 +747,8 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->smagorinsky, p->tau_minus, p->masked, p->tune, p->shift, p->residency, p->force, p->mrt};
+    p->gkey = {cur, other, tau, p->smagorinsky, p->tau_minus, p->masked, p->tune, p->shift, p->residency, p->force, p->mrt,
+               p->equilibrium, p->rho0};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -1068,6 +1080,7 @@ int aux(lt_plan *p, int what, const void *f, void *rho, void *u, double *out, vo
   a.partial = p->partial; a.reduce_blocks = kReduceBlocks; a.out = out;
   a.n0 = p->n0; a.n1 = p->n1; a.n2 = what == 8 ? (p->interior_end - p->interior_begin) + 6 : p->n2;
   a.scale = scale; a.inv_dx = inv_dx; a.mask = mask;
+  a.equilibrium = p->equilibrium; a.rho0 = p->rho0;
   a.stream = static_cast<hipStream_t>(stream);
   const int r = p->unit.aux(a);
   if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no auxiliary kernel %d", what);
@@ -1802,6 +1815,8 @@ int lt_stream_collide_many(lt_plan *p, const void *f, void *out, double tau, int
 int lt_plan_set_many_step(lt_plan *p, int32_t mode) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "many-step mode %d", mode);
+  if (mode == 1 && p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
+    return fail(LT_ERR_UNSUPPORTED, "several steps per launch: %s", kIncompressibleMultiStep);
   p->many = mode;
   return LT_OK;
 }
@@ -1866,10 +1881,39 @@ int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, 
   return LT_OK;
 }
 
+int lt_plan_set_equilibrium(lt_plan *p, int kind, double rho0) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (kind != LT_EQUILIBRIUM_QUADRATIC && kind != LT_EQUILIBRIUM_INCOMPRESSIBLE)
+    return fail(LT_ERR_INVALID, "equilibrium kind %d (0 quadratic, 1 incompressible)", kind);
+  if (!std::isfinite(rho0)) return fail(LT_ERR_INVALID, "equilibrium: rho0 = %g must be finite", rho0);
+  if (kind == LT_EQUILIBRIUM_INCOMPRESSIBLE) {
+    const int c = p->desc.collision;
+    if (c == LT_COLLISION_KBC || c == LT_COLLISION_SMAGORINSKY)
+      return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium has kernels for no collision, BGK (with or without a "
+                                      "body force), TRT and the regularised collision; the plan's collision is %d (%s)", c,
+                  c == LT_COLLISION_KBC ? "KBC" : "Smagorinsky");
+    if (c == LT_COLLISION_MRT)
+      return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium and the MRT collision: an MRT transform carries its "
+                                      "own (quadratic) equilibrium moments");
+    if (p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
+      return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium has kernels for the reference layout only, not for "
+                                      "slab plans");
+    for (int i = 0; i < p->desc.n_boundaries; ++i)
+      if (p->desc.boundaries[i].kind == LT_BOUNDARY_PRESSURE_OUTLET)
+        return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium on a plan with a constant-pressure outlet "
+                                        "(EquilibriumOutletP): that boundary evaluates the quadratic equilibrium in the kernel");
+  }
+  p->equilibrium = kind;
+  p->rho0 = rho0;
+  return LT_OK;
+}
+
 int lt_plan_set_two_step(lt_plan *p, int32_t mode, int32_t planes_per_workgroup) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "two-step mode %d", mode);
   if (mode == 1 && p->desc.collision == LT_COLLISION_MRT) return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kMrtMultiStep);
+  if (mode == 1 && p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
+    return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kIncompressibleMultiStep);
   const int sweep = p->unit.d == 2 ? p->n1 : p->n2;          // extent of the sweep axis
   if (planes_per_workgroup < 0 ||
       (planes_per_workgroup > 0 && !p->desc.ghost_planes && sweep % planes_per_workgroup != 0))

@@ -14,8 +14,15 @@ enum StepMode { kFused = 0, kCollideOnly = 1, kStreamOnly = 2, kFusedTwice = 3, 
 // collision are 8 and 9, MRT 10 and 11, so that none of them carries the force bit by accident.
 constexpr int kCollNone = 0, kCollBgk = 1, kCollKbc = 2, kCollSmagorinsky = 3, kCollForce = 4, kCollTrt = 8,
               kCollRegularized = 9, kCollMrt = 10, kCollMrtLallemand = 11;
+// ... and kCollIncompressible added to the collisions that have kernels with the incompressible equilibrium
+// (lt_plan_set_equilibrium): BGK 17, BGK with a body force 21, TRT 24, the regularised collision 25.  Without the bit:
+// the quadratic equilibrium, so a zeroed StepArgs means what it meant.
+constexpr int kCollIncompressible = 16;
+constexpr bool coll_incompressible(int coll) { return (coll & kCollIncompressible) != 0; }
 constexpr bool coll_mrt(int coll) { return coll == kCollMrt || coll == kCollMrtLallemand; }
-constexpr bool coll_forced(int coll) { return coll == (kCollBgk | kCollForce) || coll == (kCollSmagorinsky | kCollForce); }
+constexpr bool coll_forced(int coll) {
+  return (coll & ~kCollIncompressible) == (kCollBgk | kCollForce) || coll == (kCollSmagorinsky | kCollForce);
+}
 constexpr int coll_base(int coll) { return coll_forced(coll) ? coll & ~kCollForce : coll; }   // the collision under the force
 
 struct StepArgs {
@@ -57,6 +64,9 @@ struct StepArgs {
   // q moments, as the caller gave them (the units form 1 / s_i in the plan's scalar type)
   int mrt_transform;
   double mrt_rates[27];
+  // the incompressible equilibrium (coll & 16, lt_plan_set_equilibrium): its reference density; the units round it to
+  // the plan's scalar type
+  double rho0;
 };
 
 struct AuxArgs {
@@ -75,6 +85,8 @@ struct AuxArgs {
   double *out;           // device scalar
   int n0, n1, n2;        // memory extents (what 5, 6)
   double scale, inv_dx;  // what 5: u_pu = scale * u_lu, 1 / dx_pu
+  int equilibrium;       // what 1, 7: lt_equilibrium_kind of the plan (0: quadratic) and, for kind 1, its rho0
+  double rho0;
   const unsigned char *mask;   // what 6, 9: no-mass mask or null
   int z_begin, nz_global;      // what 9: global index of the rank's first plane, planes of the whole grid
   long long u_stride;          // what 0: elements between the components of u (0 = N)
@@ -120,7 +132,8 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 
 // What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
 // on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
-// collision) and outlets (plans with a constant-pressure outlet), every unit, sweeps and smagorinsky (3-D
+// collision) and outlets (plans with a constant-pressure outlet) and incompressible (the kernels of the incompressible
+// equilibrium), every unit, sweeps and smagorinsky (3-D
 // units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
@@ -135,7 +148,9 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
   int smag_##tag(const StepArgs &, const NameBuf *);           \
   int roles_##tag(const StepArgs &, const NameBuf *);          \
   int mrt_##tag(const StepArgs &, const NameBuf *);            \
-  int mrt_outlets_##tag(const StepArgs &, const NameBuf *);
+  int mrt_outlets_##tag(const StepArgs &, const NameBuf *);    \
+  int incompressible_##tag(const StepArgs &, const NameBuf *); \
+  int incompressible_aux_##tag(const AuxArgs &);
 LT_UNITS(LT_DECLARE_UNIT)
 
 // returns -1 when the combination has no instantiated kernel, else the hipError_t of the launch

@@ -117,6 +117,17 @@ struct KParamsM : KParams<T> {
   T r[kMrtMaxQ];             // r_i = 1 / s_i, formed in T (unit.inc); 0 beyond the lattice's q
 };
 
+// The parameters of a kernel with the incompressible equilibrium (COLL & 16; dispatch.hpp, kCollIncompressible): KParams
+// -- with a body force KParamsF -- and, behind it, the equilibrium's reference density.  Types of their own once more.
+template <typename T>
+struct KParamsI : KParams<T> {
+  T rho0;                    // rho0 of IncompressibleQuadraticEquilibrium, rounded to T once on the host (unit.inc)
+};
+template <typename T>
+struct KParamsFI : KParamsF<T> {
+  T rho0;
+};
+
 // ---- constants the reference builds from cs = 1/np.sqrt(3.0) (lettuce/_stencil.py:17) ----
 // cs**2 evaluates to 0.33333333333333337 in double; keep that value, not 1/3.
 constexpr double kCs = 0.57735026918962584;   // 1/sqrt(3) rounded to double
@@ -353,18 +364,72 @@ __device__ __forceinline__ void for_each_feq(T rho, const T (&u)[3], T uxu, F &&
   });
 }
 
+// IncompressibleQuadraticEquilibrium (lettuce/ext/_equilibrium/incompressible_quadratic_equilibrium.py:14-26):
+//   feq_q = w_q (rho + rho0 ((2 e_q.u - u.u) / (2 cs^2) + (e_q.u / cs^2)^2 / 2)),
+// with u = j / rho as the reference has it.  The three functions above once more, every operation rounded on its own.
+template <typename T, class S, int LAYOUT, int q>
+__device__ __forceinline__ T feq_inc_q(T rho, T rho0, const T (&u)[3], T uxu) {
+#pragma clang fp contract(off)
+  const T exu = dot_e<S, LAYOUT, q>(u);
+  const T a = div_cs<0>(T(2) * exu - uxu);
+  const T b = div_cs<1>(exu);
+  return T(S::W[q]) * (rho + rho0 * (a + T(0.5) * (b * b)));
+}
+
+// population q and its opposite o (q < o) together: the quadratic term is shared, as in feq_pair
+template <typename T, class S, int LAYOUT, int q>
+__device__ __forceinline__ void feq_inc_pair(T rho, T rho0, const T (&u)[3], T uxu, T &fq, T &fo) {
+#pragma clang fp contract(off)
+  const T exu = dot_e<S, LAYOUT, q>(u);
+  const T b = div_cs<1>(exu);
+  const T h = T(0.5) * (b * b);
+  const T two = T(2) * exu;
+  const T aq = div_cs<0>(two - uxu);
+  const T ao = div_cs<0>(-two - uxu);
+  fq = T(S::W[q]) * (rho + rho0 * (aq + h));
+  fo = T(S::W[q]) * (rho + rho0 * (ao + h));
+}
+
+// fn(q, feq_q) for every q, in the order of for_each_feq
+template <typename T, class S, int LAYOUT, class F>
+__device__ __forceinline__ void for_each_feq_inc(T rho, T rho0, const T (&u)[3], T uxu, F &&fn) {
+  static_for<S::Q>([&](auto qc) {
+    constexpr int q = decltype(qc)::value;
+    constexpr int o = S::OPP[q];
+    if constexpr (q == o) {
+      fn(qc, feq_inc_q<T, S, LAYOUT, q>(rho, rho0, u, uxu));
+    } else if constexpr (q < o) {
+      T a, b;
+      feq_inc_pair<T, S, LAYOUT, q>(rho, rho0, u, uxu, a, b);
+      fn(qc, a);
+      fn(std::integral_constant<int, o>{}, b);
+    }
+  });
+}
+
 // ---- collisions ---------------------------------------------------------------------------
-template <typename T, class S, int LAYOUT, int VEC, int k>
-__device__ __forceinline__ void collide_bgk(T (&f)[S::Q][VEC], T tau_inv) {
+// EQ (last and defaulted, with rho0 behind the collision's scalars): 0 = the quadratic equilibrium, 1 = the
+// incompressible one, which does not conserve momentum (sum_q e_q feq_q = rho0 u): where a kernel reads a neighbour's
+// moments after its collision, it collides that neighbour (neighbour_moments).
+template <typename T, class S, int LAYOUT, int VEC, int k, int EQ = 0>
+__device__ __forceinline__ void collide_bgk(T (&f)[S::Q][VEC], T tau_inv, T rho0 = T(0)) {
   T rho, j[3], u[3];
   moments<T, S, LAYOUT, VEC, k>(f, rho, j);
   u[0] = j[0] / rho; u[1] = j[1] / rho; u[2] = j[2] / rho;
   const T uxu = square_norm<S, LAYOUT>(u);
-  for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+  if constexpr (EQ == 0) {
+    for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
 #pragma clang fp contract(off)
-    constexpr int q = decltype(qc)::value;
-    f[q][k] = f[q][k] - tau_inv * (f[q][k] - feq);
-  });
+      constexpr int q = decltype(qc)::value;
+      f[q][k] = f[q][k] - tau_inv * (f[q][k] - feq);
+    });
+  } else {
+    for_each_feq_inc<T, S, LAYOUT>(rho, rho0, u, uxu, [&](auto qc, T feq) {
+#pragma clang fp contract(off)
+      constexpr int q = decltype(qc)::value;
+      f[q][k] = f[q][k] - tau_inv * (f[q][k] - feq);
+    });
+  }
 }
 
 // KBC.  The reference forms s(f) and s(feq) from the second moments m/rho of f and of feq
@@ -578,15 +643,15 @@ __device__ __forceinline__ void collide_smagorinsky(T (&f)[S::Q][VEC], T tau, T 
 // them.  The rest population has sm = 0.  rho, u and feq are BGK's, bit for bit.  The reference divides by 2.0 * tau
 // where a and b are reciprocals formed once on the host in double: compared with the reference at rounding level.  No
 // contraction by the compiler (every kernel this is inlined into returns the same bits).
-template <typename T, class S, int LAYOUT, int VEC, int k>
-__device__ __forceinline__ void collide_trt(T (&f)[S::Q][VEC], T a, T b) {
+template <typename T, class S, int LAYOUT, int VEC, int k, int EQ = 0>
+__device__ __forceinline__ void collide_trt(T (&f)[S::Q][VEC], T a, T b, T rho0 = T(0)) {
 #pragma clang fp contract(off)
   T rho, j[3], u[3];
   moments<T, S, LAYOUT, VEC, k>(f, rho, j);
   u[0] = j[0] / rho; u[1] = j[1] / rho; u[2] = j[2] / rho;
   const T uxu = square_norm<S, LAYOUT>(u);
   T held = T(0);                                  // feq_q while for_each_feq forms feq_o (it hands out q, then o)
-  for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+  const auto relax = [&](auto qc, T feq) {
 #pragma clang fp contract(off)
     constexpr int q = decltype(qc)::value;
     constexpr int o = S::OPP[q];
@@ -602,7 +667,9 @@ __device__ __forceinline__ void collide_trt(T (&f)[S::Q][VEC], T a, T b) {
       f[o][k] = f[o][k] - (spa + smb);
       f[q][k] = f[q][k] - (spa - smb);
     }
-  });
+  };
+  if constexpr (EQ == 0) for_each_feq<T, S, LAYOUT>(rho, u, uxu, relax);
+  else for_each_feq_inc<T, S, LAYOUT>(rho, rho0, u, uxu, relax);
 }
 
 // Regularised collision of Latt and Chopard (lettuce/ext/_collision/regularized_collision.py:17-44): the
@@ -614,8 +681,8 @@ __device__ __forceinline__ void collide_trt(T (&f)[S::Q][VEC], T a, T b) {
 // in double: compared with the reference at rounding level.  rho, u and feq are BGK's, bit for bit; the equilibria
 // take the registers of f once the differences are summed, so nothing but the six moments is held beside them.  No
 // contraction by the compiler; the one multiply-add per population is written as fma_t.
-template <typename T, class S, int LAYOUT, int VEC, int k>
-__device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c) {
+template <typename T, class S, int LAYOUT, int VEC, int k, int EQ = 0>
+__device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c, T rho0 = T(0)) {
 #pragma clang fp contract(off)
   T rho, j[3], u[3];
   moments<T, S, LAYOUT, VEC, k>(f, rho, j);
@@ -623,7 +690,7 @@ __device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c) {
   const T uxu = square_norm<S, LAYOUT>(u);
   T xx = T(0), yy = T(0), zz = T(0), xy = T(0), xz = T(0), yz = T(0);
   T first = T(0);                                 // f_q - feq_q while for_each_feq forms feq_o
-  for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
+  const auto moments_of = [&](auto qc, T feq) {
 #pragma clang fp contract(off)
     constexpr int q = decltype(qc)::value;
     constexpr int o = S::OPP[q];
@@ -641,7 +708,9 @@ __device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c) {
       if constexpr (ex * ez > 0) xz += v; else if constexpr (ex * ez < 0) xz -= v;
       if constexpr (ey * ez > 0) yz += v; else if constexpr (ey * ez < 0) yz -= v;
     }
-  });
+  };
+  if constexpr (EQ == 0) for_each_feq<T, S, LAYOUT>(rho, u, uxu, moments_of);
+  else for_each_feq_inc<T, S, LAYOUT>(rho, rho0, u, uxu, moments_of);
   T tr = xx;
   if constexpr (S::D > 1) tr = tr + yy;
   if constexpr (S::D > 2) tr = tr + zz;
@@ -680,10 +749,11 @@ __device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c) {
 // one per population, and the sweep has none to spare.  Compared with the reference at rounding level.  No
 // contraction by the compiler (every kernel this is inlined into returns the same bits); the multiply-adds of the
 // source term are written as fma_t.
-template <typename T, class S, int LAYOUT, int VEC, int k, int BASE>
-__device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF<T> &p) {
+template <typename T, class S, int LAYOUT, int VEC, int k, int BASE, int EQ = 0>
+__device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF<T> &p, T rho0 = T(0)) {
 #pragma clang fp contract(off)
   static_assert(BASE == 1 || BASE == 3, "a body force exists for BGK and Smagorinsky");
+  static_assert(EQ == 0 || BASE == 1, "the incompressible equilibrium exists under BGK with a force, not Smagorinsky");
   using M = MemMap<S, LAYOUT>;
   T rho, j[3], u[3];
   moments<T, S, LAYOUT, VEC, k>(f, rho, j);
@@ -711,7 +781,12 @@ __device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF
     });
     return fma_t(p.source_scale, T(S::W[q]) * t, relaxed);
   };
-  if constexpr (BASE == 1) {
+  if constexpr (BASE == 1 && EQ == 1) {
+    for_each_feq_inc<T, S, LAYOUT>(rho, rho0, u, uxu, [&](auto qc, T feq) {
+      constexpr int q = decltype(qc)::value;
+      f[q][k] = with_source(qc, f[q][k] - p.tau_inv * (f[q][k] - feq));
+    });
+  } else if constexpr (BASE == 1) {
     for_each_feq<T, S, LAYOUT>(rho, u, uxu, [&](auto qc, T feq) {
       constexpr int q = decltype(qc)::value;
       f[q][k] = with_source(qc, f[q][k] - p.tau_inv * (f[q][k] - feq));
@@ -875,7 +950,12 @@ __device__ __forceinline__ void collide_node(T (&f)[S::Q][VEC], const P &p) {
   if constexpr (COLL == kCollSmagorinsky) collide_smagorinsky<T, S, LAYOUT, VEC, k>(f, p.tau, p.smag_c2);
   if constexpr (COLL == kCollTrt) collide_trt<T, S, LAYOUT, VEC, k>(f, p.beta, p.smag_c2);
   if constexpr (COLL == kCollRegularized) collide_regularized<T, S, LAYOUT, VEC, k>(f, p.smag_c2);
-  if constexpr (coll_forced(COLL)) collide_forced<T, S, LAYOUT, VEC, k, coll_base(COLL)>(f, p);
+  if constexpr (coll_forced(COLL) && !coll_incompressible(COLL)) collide_forced<T, S, LAYOUT, VEC, k, coll_base(COLL)>(f, p);
+  // ... with the incompressible equilibrium (KParamsI / KParamsFI: rho0)
+  if constexpr (COLL == (kCollBgk | kCollIncompressible)) collide_bgk<T, S, LAYOUT, VEC, k, 1>(f, p.tau_inv, p.rho0);
+  if constexpr (COLL == (kCollTrt | kCollIncompressible)) collide_trt<T, S, LAYOUT, VEC, k, 1>(f, p.beta, p.smag_c2, p.rho0);
+  if constexpr (COLL == (kCollRegularized | kCollIncompressible)) collide_regularized<T, S, LAYOUT, VEC, k, 1>(f, p.smag_c2, p.rho0);
+  if constexpr (COLL == (kCollBgk | kCollForce | kCollIncompressible)) collide_forced<T, S, LAYOUT, VEC, k, kCollBgk, 1>(f, p, p.rho0);
   if constexpr (coll_mrt(COLL)) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, VEC, k>(f, p.r);
 }
 
@@ -944,7 +1024,9 @@ __device__ __forceinline__ void neighbour_moments(const P &p, int c0, int c1, in
   }
   // a body force adds momentum in the collision (a per step with BGK; with Smagorinsky an amount that depends on the
   // node's tau_eff): the moments are those of the collided populations
-  if constexpr ((COLL & 4) != 0) {
+  if constexpr (coll_incompressible(COLL)) {   // ... and so does the incompressible equilibrium (sum_q e_q feq_q = rho0 u)
+    if (b == 0) collide_node<T, S, LAYOUT, 1, 0, COLL>(g, p);
+  } else if constexpr ((COLL & 4) != 0) {
     if (b == 0) collide_forced<T, S, LAYOUT, 1, 0, (COLL & 3)>(g, p);
   }
   moments<T, S, LAYOUT, 1, 0>(g, rho, j);
@@ -1057,7 +1139,8 @@ __device__ __forceinline__ void lbm_body(const P &p) {
   int lane_slot = 0;
   T lane_rho = T(1), lane_j[3] = {T(0), T(0), T(0)};
   // (not with a body force: the neighbour's collision changes its momentum -- neighbour_moments collides it)
-  if constexpr (COLLIDE && MASKED && ABBD == 0 && (COLL & 4) == 0) {   // (COLL 8 and 9 conserve rho and j, as 1-3 do)
+  // (nor with the incompressible equilibrium, for the same reason)
+  if constexpr (COLLIDE && MASKED && ABBD == 0 && (COLL & 4) == 0 && !coll_incompressible(COLL)) {   // (COLL 8 and 9 conserve rho and j, as 1-3 do)
     if (p.abb0_slot != 0) {
       const int slot = p.abb0_slot, plane = p.bt->plane[slot];
       const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -1134,6 +1217,23 @@ template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, 
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsM<T> p) {
   static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
   static_assert(coll_mrt(COLL), "MRT is collision 10 (Dellar / Hermite) or 11 (Lallemand)");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
+}
+
+// ... with the incompressible equilibrium (COLL = 16 + the collision: BGK 17, BGK with a body force 21, TRT 24, the
+// regularised collision 25): the same body on KParamsI / KParamsFI
+template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
+          int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+__global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsI<T> p) {
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  static_assert(coll_incompressible(COLL) && !coll_forced(COLL), "the incompressible equilibrium is COLL & 16");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
+}
+template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
+          int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+__global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsFI<T> p) {
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  static_assert(coll_incompressible(COLL) && coll_forced(COLL), "BGK with a body force and the incompressible equilibrium is COLL 21");
   lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 
@@ -1449,6 +1549,25 @@ __global__ void __launch_bounds__(kThreads) equilibrium_kernel(const T *__restri
   });
 }
 
+// ... and IncompressibleQuadraticEquilibrium.__call__ (rho0 in the plan's scalar type)
+template <typename T, class S, int LAYOUT>
+__global__ void __launch_bounds__(kThreads) equilibrium_inc_kernel(const T *__restrict__ rho_in,
+                                                                   const T *__restrict__ u_in,
+                                                                   T *__restrict__ feq_out,
+                                                                   long long N, T rho0) {
+  using M = MemMap<S, LAYOUT>;
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= N) return;
+  const T rho = rho_in[i];
+  T u[3] = {T(0), T(0), T(0)};
+#pragma unroll
+  for (int a = 0; a < S::D; ++a) u[M::memory(a)] = u_in[(long long)a * N + i];
+  const T uxu = square_norm<S, LAYOUT>(u);
+  for_each_feq_inc<T, S, LAYOUT>(rho, rho0, u, uxu, [&](auto qc, T v) {
+    feq_out[(long long)decltype(qc)::value * N + i] = v;
+  });
+}
+
 // periodic index of a shifted coordinate: a modulo n in [0, n) for every extent n >= 1 and any shift, as
 // torch.roll wraps (an extent of 1 or 2 is smaller than the stencil's reach of 3)
 __device__ __forceinline__ int wrap_index(int a, int n) {
@@ -1463,63 +1582,18 @@ template <typename T, class S>
 __global__ void __launch_bounds__(kThreads) fneq_kernel(const T *__restrict__ rho_in, const T *__restrict__ u_in,
                                                        T *__restrict__ f_out, int n0, int n1, int n2, T tau,
                                                        T eye_cs2) {
-#pragma clang fp contract(off)
-  using M = MemMap<S, 0>;
-  constexpr int D = S::D;
-  const long long N = (long long)n0 * n1 * n2;
-  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= N) return;
-  const int c0 = (int)(i % n0), c1 = (int)((i / n0) % n1), c2 = (int)(i / ((long long)n0 * n1));
-  const T w6[6] = {T(-1. / 60.), T(3. / 20.), T(-3. / 4.), T(3. / 4.), T(-3. / 20.), T(1. / 60.)};
-  const int sh[6] = {3, 2, 1, -1, -2, -3};
-  T grad[D][D];                                   // [component a][logical axis b]
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    const int m = D - 1 - b;                      // memory axis of logical axis b
-    long long at[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      int a0 = c0, a1 = c1, a2 = c2;
-      if (m == 0) { a0 = c0 - sh[k]; a0 = wrap_index(a0, n0); }
-      if (m == 1) { a1 = c1 - sh[k]; a1 = wrap_index(a1, n1); }
-      if (m == 2) { a2 = c2 - sh[k]; a2 = wrap_index(a2, n2); }
-      at[k] = ((long long)a2 * n1 + a1) * n0 + a0;
-    }
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      const T *uc = u_in + (long long)a * N;
-      T r = w6[0] * uc[at[0]];
-#pragma unroll
-      for (int k = 1; k < 6; ++k) r = r + w6[k] * uc[at[k]];
-      grad[a][b] = r;
-    }
-  }
-  const T rho = rho_in[i];
-  const T scale = (T(1.0) * tau) * rho;
-  const T cs2 = (T)kCs2;
-  T pi[D][D];
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) pi[a][b] = scale * grad[a][b] / cs2;
-  T u[3] = {T(0), T(0), T(0)};
-#pragma unroll
-  for (int a = 0; a < D; ++a) u[M::memory(a)] = u_in[(long long)a * N + i];
-  const T uxu = square_norm<S, 0>(u);
-  for_each_feq<T, S, 0>(rho, u, uxu, [&](auto qc, T feq) {
-    constexpr int q = decltype(qc)::value;
-    T acc = T(0);
-    static_for<D>([&](auto ac) {
-      constexpr int a = decltype(ac)::value;
-      static_for<D>([&](auto bc) {
-        constexpr int b = decltype(bc)::value;
-        constexpr int ee = S::E[q][a] * S::E[q][b];
-        const T qab = a == b ? T(ee) - eye_cs2 : T(ee);
-        acc = acc + pi[a][b] * qab;
-      });
-    });
-    f_out[(long long)q * N + i] = feq - T(S::W[q]) * acc;
-  });
+#define LT_FNEQ_FOR_EACH_FEQ for_each_feq<T, S, 0>(rho, u, uxu,
+#include "fneq_body.inc"
+#undef LT_FNEQ_FOR_EACH_FEQ
+}
+// ... with the incompressible equilibrium (rho0 in the plan's scalar type)
+template <typename T, class S>
+__global__ void __launch_bounds__(kThreads) fneq_inc_kernel(const T *__restrict__ rho_in, const T *__restrict__ u_in,
+                                                           T *__restrict__ f_out, int n0, int n1, int n2, T tau,
+                                                           T eye_cs2, T rho0) {
+#define LT_FNEQ_FOR_EACH_FEQ for_each_feq_inc<T, S, 0>(rho, rho0, u, uxu,
+#include "fneq_body.inc"
+#undef LT_FNEQ_FOR_EACH_FEQ
 }
 
 // maximum that propagates NaN like torch.max: a NaN on either side wins and then stays (`m > acc` alone is false

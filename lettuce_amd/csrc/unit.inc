@@ -50,6 +50,11 @@
 //                         Hermite on D3Q27; kCollMrtLallemand: Lallemand on D2Q9) -- every one-step variant BGK has, on
 //                         a parameter block of their own (KParamsM); no launch of several steps
 //   mrt_outlets (inst11_) ... and its kernels of plans with a constant-pressure outlet
+//   incompressible (inst12_)  every unit: the kernels of the incompressible equilibrium (the kernels' COLL |
+//                         kCollIncompressible: BGK, BGK with a body force, TRT, the regularised collision) -- the
+//                         one-step variants of the reference layout, on parameter
+//                         blocks of their own (KParamsI, KParamsFI), and the equilibrium and f_neq kernels; no launch of
+//                         several steps.  Objects of their own again: every other plan launches what it launched before
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -62,6 +67,7 @@
 #define LT_PART_outlets3 9
 #define LT_PART_mrt 10
 #define LT_PART_mrt_outlets 11
+#define LT_PART_incompressible 12
 #define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
@@ -82,11 +88,11 @@
 #elif LT_PART_IS(relaxations)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 1
-#elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt)
+#elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt or mrt_outlets"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets or incompressible"
 #endif
 #if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
 #error "the MRT collision exists on D2Q9 and D3Q27"
@@ -110,7 +116,10 @@ constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
 // The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
 // to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
 template <int COLL>
-using ParamsOf = std::conditional_t<coll_mrt(COLL), KParamsM<T>, std::conditional_t<coll_forced(COLL), KParamsF<T>, KParams<T>>>;
+using ParamsOfQuadratic = std::conditional_t<coll_mrt(COLL), KParamsM<T>, std::conditional_t<coll_forced(COLL), KParamsF<T>, KParams<T>>>;
+template <int COLL>
+using ParamsOf = std::conditional_t<coll_incompressible(COLL), std::conditional_t<coll_forced(COLL), KParamsFI<T>, KParamsI<T>>,
+                                    ParamsOfQuadratic<COLL>>;
 template <class P>
 P params_of(const StepArgs &a, int n2) {
   P p{};
@@ -132,8 +141,8 @@ P params_of(const StepArgs &a, int n2) {
   p.smag_c2 = (T)(a.smagorinsky * a.smagorinsky);   // smagorinsky_collision.py:32: constant ** 2 in double
   // the collision's own scalar (kernels.hpp, collide_node): TRT 1 / (2 tau_minus) beside beta = 1 / (2 tau_plus)
   // (trt_collision.py:22,25), the regularised collision 1 - 1 / tau (regularized_collision.py:42)
-  if (a.coll == kCollTrt) p.smag_c2 = (T)(1.0 / (2.0 * a.tau_minus));
-  if (a.coll == kCollRegularized) p.smag_c2 = (T)(1.0 - 1.0 / a.tau);
+  if ((a.coll & ~kCollIncompressible) == kCollTrt) p.smag_c2 = (T)(1.0 / (2.0 * a.tau_minus));
+  if ((a.coll & ~kCollIncompressible) == kCollRegularized) p.smag_c2 = (T)(1.0 - 1.0 / a.tau);
   p.node = a.node;
   p.nsm_bits = a.nsm_bits;
   p.bt = static_cast<const BoundaryTable<T> *>(a.bt);
@@ -209,6 +218,8 @@ int launch(const StepArgs &a, const NameBuf *name) {
   p.nvec_total = (unsigned)((long long)p.nv0 * a.n1 * a.planes);
   if constexpr (coll_forced(COLL)) set_force<LAYOUT>(p, a);
   if constexpr (coll_mrt(COLL)) set_mrt(p, a);
+  // the incompressible equilibrium's rho0: rounded once, as a Python float times a tensor of the plan's dtype is
+  if constexpr (coll_incompressible(COLL)) p.rho0 = (T)a.rho0;
   p.abb0_slot = a.n0 % 64 == 0 ? a.abb0_slot : 0;
   if (p.nvec_total == 0) return 0;
   const unsigned grid = (p.nvec_total + kThreads - 1) / kThreads;
@@ -275,6 +286,23 @@ int one_step_of(const StepArgs &a, const NameBuf *name) {
 #endif
   return kNoKernel;
 }
+
+#if LT_PART_IS(incompressible)
+// The one-step kernels of collision C with the incompressible equilibrium: every variant of the reference layout that
+// one_step_of has (lt_plan_set_equilibrium refuses slab plans and the constant-pressure outlet)
+template <int C>
+int one_step_incompressible_of(const StepArgs &a, const NameBuf *name) {
+  if (a.n_pout > 0 || a.pack_lo || a.pack_hi) return kNoKernel;
+#if LT_IS_3D
+  LT_TRY_THREE_AXES(C, kFused) LT_TRY_THREE_AXES(C, kCollideOnly)
+#endif
+  if (a.abb_depth > 1) return kNoKernel;
+  LT_TRY_TWO_OUTLETS(0, C, kFused) LT_TRY_TWO_OUTLETS(0, C, kCollideOnly)
+  LT_COLLISION_SET(0, C, 0)
+  LT_COLLISION_SET(0, C, 1)
+  return kNoKernel;
+}
+#endif
 
 #if LT_PART_IS_OUTLETS
 // Plans with a constant-pressure outlet, alone or beside anti-bounce-back outlets: masked kernels that apply boundaries
@@ -538,6 +566,7 @@ int twice_3d(const StepArgs &a, const NameBuf *name) {
 
 int dispatch(const StepArgs &a, const NameBuf *name) {
   const int coll = a.mode == kStreamOnly ? kCollNone : a.coll;   // streaming does not depend on it
+  if (coll_incompressible(coll)) return LT_CAT(incompressible_, LT_TAG)(a, name);   // part incompressible
   // a constant-pressure outlet: part outlets has the kernels that apply boundaries (streaming alone applies none)
   if (a.n_pout > 0 && a.mode != kStreamOnly) return LT_CAT(outlets_, LT_TAG)(a, name);
   if (coll_forced(coll)) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
@@ -585,6 +614,8 @@ int dispatch(const StepArgs &a, const NameBuf *name) {
 
 template <int LAYOUT>
 int aux_impl(const AuxArgs &a) {
+  // feq with another equilibrium than the quadratic one: part incompressible
+  if (a.equilibrium != 0 && (a.what == 1 || a.what == 7)) return LT_CAT(incompressible_aux_, LT_TAG)(a);
   const T *f = static_cast<const T *>(a.f);
   const unsigned grid = (unsigned)((a.N + kThreads - 1) / kThreads);
   switch (a.what) {
@@ -752,6 +783,39 @@ int LT_CAT(mrt_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
 #if !LT_IS_3D
   if (a.coll == kCollMrtLallemand) return one_step_of<kCollMrtLallemand>(a, name);
 #endif
+  return kNoKernel;
+}
+#elif LT_PART_IS(incompressible)
+// one-step kernels only; a.coll carries kCollIncompressible (api.hip, kernel_coll)
+int LT_CAT(incompressible_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
+  if (a.coll == (kCollBgk | kCollIncompressible)) return one_step_incompressible_of<kCollBgk | kCollIncompressible>(a, name);
+  if (a.coll == (kCollBgk | kCollForce | kCollIncompressible))
+    return one_step_incompressible_of<kCollBgk | kCollForce | kCollIncompressible>(a, name);
+  if (a.coll == (kCollTrt | kCollIncompressible)) return one_step_incompressible_of<kCollTrt | kCollIncompressible>(a, name);
+  if (a.coll == (kCollRegularized | kCollIncompressible))
+    return one_step_incompressible_of<kCollRegularized | kCollIncompressible>(a, name);
+  return kNoKernel;
+}
+
+// lt_equilibrium (what 1) and lt_init_fneq (what 7) of a plan with the incompressible equilibrium, reference layout
+int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
+  if (a.equilibrium != 1 || a.layout != 0) return kNoKernel;
+  const unsigned grid = (unsigned)((a.N + kThreads - 1) / kThreads);
+  if (a.what == 1) {
+    hipLaunchKernelGGL((equilibrium_inc_kernel<T, S, 0>), dim3(grid), dim3(kThreads), 0, a.stream,
+                       static_cast<const T *>(a.rho), static_cast<const T *>(a.u),
+                       const_cast<T *>(static_cast<const T *>(a.f)), a.N, (T)a.rho0);
+    return (int)hipGetLastError();
+  }
+  if constexpr (S::D >= 2) {
+    if (a.what == 7) {
+      hipLaunchKernelGGL((fneq_inc_kernel<T, S>), dim3(grid), dim3(kThreads), 0, a.stream, static_cast<const T *>(a.rho),
+                         static_cast<const T *>(a.u), const_cast<T *>(static_cast<const T *>(a.f)), a.n0, a.n1, a.n2,
+                         (T)a.scale, (T)a.inv_dx, (T)a.rho0);
+      return (int)hipGetLastError();
+    }
+  }
   return kNoKernel;
 }
 #elif LT_PART_IS(mrt_outlets)

@@ -25,6 +25,12 @@ __all__ = ["BGKCollision", "KBCCollision", "KBCCollision2D", "KBCCollision3D", "
            "SmagorinskyCollision", "TRTCollision", "RegularizedCollision", "MRTCollision"]
 
 
+# the collisions that evaluate flow.equilibrium (MRT relaxes towards its transform's own equilibrium moments), and those
+# of them with kernels for the incompressible equilibrium (lt_plan_set_equilibrium)
+FEQ_COLLISIONS = ("bgk", "kbc", "smagorinsky", "trt", "regularized")
+INCOMPRESSIBLE_COLLISIONS = ("none", "bgk", "trt", "regularized")
+
+
 def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None, mrt=None):
     """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``constant``: the
     Smagorinsky constant, ``tau_minus``: TRT's second relaxation time, ``force``: the collision's body force (a Force
@@ -32,11 +38,18 @@ def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None, 
     every collide."""
     if flow._engine_plan(flow.f) is None:
         return None
+    # the flow's equilibrium is a property of the plan, handed over like the other settings.  An equilibrium the engine
+    # has no kernel for, or none under this collision: the torch expressions (the caller's)
+    equilibrium = flow._engine_equilibrium() if kind in FEQ_COLLISIONS else ("quadratic", 1.0)
+    if equilibrium is None or (equilibrium[0] != "quadratic" and kind not in INCOMPRESSIBLE_COLLISIONS):
+        return None
     plans = flow.__dict__.setdefault("_collision_plans", {})
     if kind not in plans:
         from .._native import Plan
         plans[kind] = Plan(type(flow.stencil).__name__, flow.context.dtype, kind, flow.resolution,
                            device=flow.f.device)
+    if kind in FEQ_COLLISIONS:
+        plans[kind].set_equilibrium(*equilibrium)
     if constant is not None:
         plans[kind].set_smagorinsky(constant)
     if tau_minus is not None:

@@ -14,7 +14,15 @@ __all__ = ["NativeEquilibrium", "NativeCollision", "NativeBoundary", "NativeForc
 
 @dataclass
 class NativeEquilibrium:
-    kind: str = "quadratic"
+    """The equilibrium of the engine's plans (``lt_plan_set_equilibrium``).  ``rho0`` is read late, per call and per
+    batch like ``tau``: the reference reads ``equilibrium.rho0`` on every call
+    (lettuce/ext/_equilibrium/incompressible_quadratic_equilibrium.py:22)."""
+    kind: str = "quadratic"                    # 'quadratic' | 'incompressible'
+    rho0: Optional[Callable[[], float]] = None         # 'incompressible': its reference density; None for 'quadratic'
+
+    def plan_args(self) -> Tuple[str, float]:
+        """the arguments of ``Plan.set_equilibrium`` now (hashable: part of the steppers' carry key)"""
+        return (self.kind, 1.0 if self.rho0 is None else float(self.rho0()))
 
 
 @dataclass
