@@ -362,6 +362,28 @@ int lt_slab_enstrophy(lt_plan *plan, const void *u_ext_dev, double u_scale, doub
 int lt_slab_mass_interior(lt_plan *plan, const void *f_dev, const uint8_t *no_mass_mask_dev, int32_t z_begin,
                           int32_t nz_global, double *out_dev, void *stream);
 
+/* EnergySpectrum observable (lettuce/ext/_reporter/observable_reporter.py:71-108) without its [*res, K] wave mask:
+ *   out_dev[n] = scale * sum over the modes of bin n of sum_a 0.5 * (re_a^2 + im_a^2),  n < n_bins.
+ * uhat_dev holds the d complex fields [d][*res] of the plan's grid, interleaved (re, im), in the plan's dtype: the full
+ * transform of the velocity field (torch.view_as_real(torch.fft.fftn(u, dim = <the last d axes>))), every mode counted
+ * as the reference counts it.  Index i on an axis of extent n has the integer wavenumber k = i < (n + 1) / 2 ? i : i - n
+ * (np.fft.fftfreq(n, d = 1 / n), odd n too; each axis in its own extent).  With m = sum_a k_a^2 the bin of a mode is 0
+ * for m = 0 and else the n >= 1 with n^2 - n < m <= n^2 + n: the reference's n - 0.5 < |k| <= n + 0.5, squared and so
+ * decided in integers.  The reference has n_bins = isqrt(max m) (its int(max |k|)); modes whose bin is >= n_bins are
+ * dropped, as the reference drops them.  Squares and sums are fp64 from the first operation (fp32 inputs promote
+ * exactly); scale (1 / norm^2) is applied once per bin.
+ * Fixed summation order, no floating-point atomics: the first launch has ceil(N / chunk) <= LT_SPECTRUM_BLOCKS
+ * workgroups, each over a contiguous range of `chunk` modes (N / LT_SPECTRUM_BLOCKS rounded up to whole passes of 256,
+ * 1024 modes or more) with a table of bins per wave in LDS, and writes partial_scratch_dev [workgroups][n_bins]; the second sums the
+ * workgroups in index order.  Two calls on the same input give the same bits.  partial_scratch_dev is caller-owned:
+ * LT_SPECTRUM_BLOCKS * n_bins doubles always suffice.  out_dev: n_bins doubles.
+ * LT_ERR_UNSUPPORTED: 1-D plans, the slab layout or ghost planes, n_bins > LT_SPECTRUM_MAX_BINS (four tables of doubles
+ * in 64 KiB of LDS; 768^3 has 665 bins).  LT_ERR_INVALID: a null pointer, n_bins < 1. */
+#define LT_SPECTRUM_BLOCKS 1024
+#define LT_SPECTRUM_MAX_BINS 2048
+int lt_energy_spectrum(lt_plan *plan, const void *uhat_dev, double scale, int32_t n_bins, double *partial_scratch_dev,
+                       double *out_dev, void *stream);
+
 /* Introspection for tests and benchmarks. */
 int lt_plan_kernel_info(lt_plan *plan, int32_t *vec_width, int32_t *threads_per_block,
                         int64_t *blocks_per_launch);

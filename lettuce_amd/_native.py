@@ -25,6 +25,8 @@ __all__ = ["NativeEngineError", "load_library", "library_path", "Plan", "STENCIL
 
 LT_ABI_VERSION = 2
 LT_MAX_BOUNDARIES = 127
+SPECTRUM_BLOCKS = 1024          # LT_SPECTRUM_BLOCKS: rows of lt_energy_spectrum's scratch
+SPECTRUM_MAX_BINS = 2048        # LT_SPECTRUM_MAX_BINS: the most bins its kernel takes
 LT_MAX_Q = 27
 
 STENCIL_IDS = {"D2Q9": 0, "D3Q19": 1, "D3Q27": 2, "D1Q3": 3, "D3Q15": 4}
@@ -95,6 +97,7 @@ SYMBOLS = {
     "lt_init_fneq": (ctypes.c_int, [_vp, _vp, _vp, _dbl, _dbl, _vp, _vp]),
     "lt_enstrophy": (ctypes.c_int, [_vp, _vp, _vp, _dbl, _dbl, _vp, _vp]),
     "lt_mass_interior": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "lt_energy_spectrum": (ctypes.c_int, [_vp, _vp, _dbl, _i32, _vp, _vp, _vp]),
     "lt_slab_velocity": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "lt_slab_enstrophy": (ctypes.c_int, [_vp, _vp, _dbl, _dbl, _vp, _vp]),
     "lt_slab_mass_interior": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
@@ -631,6 +634,24 @@ class Plan:
                                           _ptr(out), _stream_handle()))
         scratch.record_stream(torch.cuda.current_stream())
         return out
+
+    @_on_device
+    def energy_spectrum(self, uhat, scale: float, n_bins: int):
+        """float64 device tensor [n_bins]: scale * sum over the Fourier modes of each integer wavenumber bin of
+        sum_a 0.5 |uhat_a|^2 (lt_energy_spectrum: fp64, fixed summation order, no [*res, K] mask).  ``uhat``: the
+        transformed velocity field, complex [d, *res] or its real view [d, *res, 2], in the plan's dtype."""
+        if uhat.is_complex():
+            uhat = torch.view_as_real(uhat)
+        uhat = uhat.contiguous()
+        self._tensor_ok(uhat, [self.d] + self.f_shape[1:] + [2])
+        n_bins = int(n_bins)
+        scratch = torch.empty([SPECTRUM_BLOCKS, max(n_bins, 1)], dtype=torch.float64, device=uhat.device)
+        out = torch.empty([max(n_bins, 1)], dtype=torch.float64, device=uhat.device)
+        self._check(self.lib.lt_energy_spectrum(self._handle, _ptr(uhat), float(scale), n_bins, _ptr(scratch),
+                                                _ptr(out), _stream_handle()))
+        for t in (uhat, scratch):
+            t.record_stream(torch.cuda.current_stream())
+        return out[:n_bins]
 
     @_on_device
     def mass_interior(self, f, no_mass_mask: Optional[torch.Tensor] = None):

@@ -1421,6 +1421,35 @@ int lt_mass_interior(lt_plan *p, const void *f, const uint8_t *mask, double *out
   return aux(p, 6, f, nullptr, nullptr, out, s, 1.0, 1.0, mask);
 }
 
+int lt_energy_spectrum(lt_plan *p, const void *uhat, double scale, int32_t n_bins, double *partial_scratch, double *out,
+                       void *s) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (!uhat || !partial_scratch || !out) return fail(LT_ERR_INVALID, "null transformed field / scratch / output");
+  if (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
+    return fail(LT_ERR_UNSUPPORTED, "energy spectrum: 2-D / 3-D grids in the reference layout without ghost planes");
+  if (n_bins < 1) return fail(LT_ERR_INVALID, "energy spectrum: %d bins", (int)n_bins);
+  if (n_bins > LT_SPECTRUM_MAX_BINS)
+    return fail(LT_ERR_UNSUPPORTED, "energy spectrum: %d bins, the kernel's table of bins per wave holds "
+                                    "LT_SPECTRUM_MAX_BINS = %d", (int)n_bins, LT_SPECTRUM_MAX_BINS);
+  lt::AuxArgs a;
+  memset(&a, 0, sizeof a);
+  a.what = 10; a.layout = p->desc.layout;
+  a.f = uhat; a.partial = partial_scratch; a.out = out;
+  a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2; a.N = p->N;
+  // fixed launch geometry: contiguous ranges of whole workgroup passes (256 modes), four passes or more, in at most
+  // LT_SPECTRUM_BLOCKS workgroups
+  const long long pass = 256;
+  a.count = ((p->N + LT_SPECTRUM_BLOCKS - 1) / LT_SPECTRUM_BLOCKS + pass - 1) / pass * pass;
+  if (a.count < 4 * pass) a.count = 4 * pass;
+  a.reduce_blocks = (int)((p->N + a.count - 1) / a.count);
+  a.scale = scale; a.n_bins = n_bins;
+  a.stream = static_cast<hipStream_t>(s);
+  const int r = p->unit.aux(a);
+  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no energy spectrum kernel");
+  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  return LT_OK;
+}
+
 namespace {
 int slab_plan_ok(lt_plan *p, const char *who) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");

@@ -8,6 +8,7 @@
 #include "kernels.hpp"
 #include "twostep_masked.hpp"
 #include "twostep2d.hpp"
+#include "spectrum.hpp"
 
 #define LT_CAT_(a, b) a##b
 #define LT_CAT(a, b) LT_CAT_(a, b)
@@ -55,6 +56,8 @@
 //                         one-step variants of the reference layout, on parameter
 //                         blocks of their own (KParamsI, KParamsFI), and the equilibrium and f_neq kernels; no launch of
 //                         several steps.  Objects of their own again: every other plan launches what it launched before
+//   spectrum (inst13_)    2-D and 3-D units: the two launches of the energy spectrum (spectrum.hpp), which depend on the
+//                         scalar type and the dimension only -- an object of its own, so that no other object changes
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -68,6 +71,7 @@
 #define LT_PART_mrt 10
 #define LT_PART_mrt_outlets 11
 #define LT_PART_incompressible 12
+#define LT_PART_spectrum 13
 #define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
@@ -91,11 +95,17 @@
 #elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 0
+#elif LT_PART_IS(spectrum)
+#define LT_ONE_STEP 0
+#define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets or incompressible"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible or spectrum"
 #endif
 #if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
 #error "the MRT collision exists on D2Q9 and D3Q27"
+#endif
+#if LT_PART_IS(spectrum) && LT_FIELD(d, LT_UNIT) < 2
+#error "the energy spectrum exists in 2-D and 3-D"
 #endif
 
 namespace lt {
@@ -688,6 +698,11 @@ int aux_impl(const AuxArgs &a) {
       } else {
         return kNoKernel;
       }
+    case 10:    // energy spectrum of d Fourier-transformed fields: part spectrum
+#if LT_FIELD(d, LT_UNIT) >= 2
+      if constexpr (LAYOUT == 0) return LT_CAT(spectrum_, LT_TAG)(a);
+#endif
+      return kNoKernel;
     case 9:
       if constexpr (S::D == 3 && LAYOUT == 1) {
         hipLaunchKernelGGL((interior_mass_slab_kernel<T, S::Q>), dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream,
@@ -817,6 +832,18 @@ int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
     }
   }
   return kNoKernel;
+}
+#elif LT_PART_IS(spectrum)
+// lt_energy_spectrum (what 10): a.f the transformed fields, a.partial the caller's [a.reduce_blocks][a.n_bins] scratch;
+// a.count modes per workgroup
+int LT_CAT(spectrum_, LT_TAG)(const AuxArgs &a) {
+  if (a.what != 10 || a.layout != 0 || a.n_bins < 1 || a.n_bins > kSpectrumMaxBins) return kNoKernel;
+  hipLaunchKernelGGL((energy_spectrum_kernel<T, S::D>), dim3(a.reduce_blocks), dim3(kSpectrumThreads),
+                     kSpectrumWaves * a.n_bins * sizeof(double), a.stream, static_cast<const T *>(a.f), a.n0, a.n1, a.n2,
+                     a.count, a.n_bins, a.partial);
+  hipLaunchKernelGGL(finish_spectrum_kernel<T>, dim3((a.n_bins + kSpectrumThreads - 1) / kSpectrumThreads),
+                     dim3(kSpectrumThreads), 0, a.stream, a.partial, a.reduce_blocks, a.n_bins, a.scale, a.out);
+  return (int)hipGetLastError();
 }
 #elif LT_PART_IS(mrt_outlets)
 int LT_CAT(mrt_outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {

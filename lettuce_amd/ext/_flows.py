@@ -3,8 +3,10 @@ Taylor-Green vortex (2-D/3-D), flow around an obstacle, doubly periodic shear la
 the reference, plus the 3-D variant BASELINE.json's cfg5 asks for).
 
 API of lettuce/ext/_flows/_ext_flow.py:8-42, taylorgreen.py:16-122, obstacle.py:54-151,
-doublyshear.py:19-80, poiseuille.py:19-95 (the channel a body force drives).  The other demo flows (Couette,
-cavity, decaying turbulence) are out of scope.
+doublyshear.py:19-80, poiseuille.py:19-95 (the channel a body force drives), decayingturbulence.py:23-189
+(a random solenoidal velocity field with a prescribed spectrum; its spectrum is binned by index, without the
+reference's [*res, K] mask, so that the flow constructs at 256^3).  The other demo flows (Couette, cavity) are out
+of scope.
 """
 import warnings
 from abc import ABC, abstractmethod
@@ -13,6 +15,7 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
+from .._errors import LettuceException
 from .._flow import Flow
 from .._stencil import D1Q3, D2Q9, D3Q19
 from .._unit import UnitConversion
@@ -21,7 +24,8 @@ from ._boundary import AntiBounceBackOutlet, BounceBackBoundary, EquilibriumBoun
 from ._equilibrium import QuadraticEquilibrium
 
 __all__ = ["ExtFlow", "TaylorGreenVortex", "TaylorGreenVortex2D", "TaylorGreenVortex3D",
-           "Obstacle", "DoublyPeriodicShear2D", "DoublyPeriodicShear3D", "PoiseuilleFlow2D", "flow_by_name"]
+           "Obstacle", "DoublyPeriodicShear2D", "DoublyPeriodicShear3D", "PoiseuilleFlow2D", "DecayingTurbulence",
+           "flow_by_name"]
 
 
 class ExtFlow(Flow, ABC):
@@ -395,6 +399,162 @@ class PoiseuilleFlow2D(ExtFlow):
     @property
     def acceleration(self):
         return self.context.convert_to_tensor([0.001, 0])
+
+
+class DecayingTurbulence(ExtFlow):
+    """Decaying homogeneous isotropic turbulence in 2-D and 3-D (lettuce/ext/_flows/decayingturbulence.py:23-189): a
+    random velocity field with the energy spectrum E(k) ~ k^4 exp(-2 (k / k0)^2), made solenoidal in Fourier space and
+    scaled to ``ic_energy``.  The numpy operations are the reference's, one for one, so that a given ``randseed`` gives
+    the reference's initial velocity.  ``energy_spectrum`` returns the pair (spectrum, wavenumbers).
+
+    Kept from the reference: its ``np.meshgrid(*frequencies)`` has the default 'xy' indexing, so the wavenumber
+    components of the first two axes are swapped and the first two extents must be equal (refused here by name, where
+    numpy would fail to broadcast); ``_compute_initial_pressure`` returns zeros; in 2-D ``initialize_pressure`` defaults
+    to True, which this engine's ``Flow.initialize`` refuses -- pass ``initialize_pressure=False``.
+    Changed: ``self.spectrum`` is summed per bin index (``spectrum_bins`` of ``_reporter.py``, bincount) instead of
+    through a float64 mask [*res, K].  The initial velocity does not depend on it.
+    Not in ``flow_by_name``: the fifth positional argument is ``k0``, not the stencil."""
+
+    def __init__(self, context: "Context", resolution: Union[int, List[int]], reynolds_number, mach_number,
+                 k0=20, ic_energy=0.5, stencil: Optional["Stencil"] = None,
+                 equilibrium: Optional["Equilibrium"] = None, initialize_pressure: bool = True,
+                 initialize_fneq: bool = True, randseed: Optional[int] = None):
+        self.initialize_pressure = initialize_pressure
+        self.initialize_fneq = initialize_fneq
+        self.randseed = randseed
+        self.k0 = k0
+        self.ic_energy = ic_energy
+        self.wavenumbers = []
+        self.spectrum = []
+        default_stencils = [D1Q3(), D2Q9(), D3Q19()]
+        stencil = stencil or default_stencils[len(resolution) - 1]
+        stencil = stencil() if callable(stencil) else stencil
+        if stencil.d != 2:
+            self.initialize_pressure = False
+        self.stencil = stencil
+        ExtFlow.__init__(self, context, resolution, reynolds_number, mach_number, stencil, equilibrium)
+
+    def make_resolution(self, resolution, stencil=None) -> List[int]:
+        if isinstance(resolution, int):
+            return [resolution] * stencil.d
+        return resolution
+
+    def make_units(self, reynolds_number, mach_number, resolution) -> "UnitConversion":
+        return UnitConversion(reynolds_number=reynolds_number, mach_number=mach_number,
+                              characteristic_length_lu=resolution[0], characteristic_length_pu=2 * np.pi,
+                              characteristic_velocity_pu=None)
+
+    def analytic_solution(self, x, t=0):
+        return
+
+    def _generate_wavenumbers(self):
+        """(wavenorms, wavenumber, bins): the reference's first two and, in place of its mask, the bin of every mode
+        (K for the modes of no bin) on the same 'xy' meshgrid"""
+        from ._reporter import spectrum_bins
+        self.dimensions = self.grid[0].shape
+        if len(self.dimensions) < 2 or self.dimensions[0] != self.dimensions[1]:
+            raise LettuceException(f"DecayingTurbulence: the first two extents must be equal, got "
+                                   f"{list(self.dimensions)} (the wavenumber grid is built with numpy's default "
+                                   f"'xy' meshgrid, which swaps the first two axes)")
+        frequencies = [np.fft.fftfreq(dim, d=1 / dim) for dim in self.dimensions]
+        wavenumber = np.meshgrid(*frequencies)
+        wavenorms = np.linalg.norm(wavenumber, axis=0)
+        self.wavenumbers = np.arange(int(np.max(wavenorms)))
+        bins, _ = spectrum_bins(list(self.dimensions))
+        bins = np.minimum(bins.numpy().swapaxes(0, 1), len(self.wavenumbers))
+        return wavenorms, wavenumber, bins
+
+    def _generate_spectrum(self):
+        wavenorms, wavenumber, bins = self._generate_wavenumbers()
+        ek = wavenorms ** 4 * np.exp(-2 * (wavenorms / self.k0) ** 2)
+        ek /= np.sum(ek)
+        ek *= self.ic_energy
+        n_bins = len(self.wavenumbers)
+        self.spectrum = np.bincount(bins.ravel(), weights=ek.ravel(), minlength=n_bins + 1)[:n_bins]
+        return ek, wavenumber
+
+    def _generate_initial_velocity(self, ek, wavenumber):
+        d = self.stencil.d
+        axes = tuple(np.arange(d))
+        dx = self.units.convert_length_to_pu(1.0)
+        np.random.seed(self.randseed)
+        u = np.random.random(np.array(wavenumber).shape) * 2 * np.pi + 0j
+        u = [np.fft.fftn(u[dim], axes=axes) for dim in range(d)]
+
+        u_real = [u[dim].real for dim in range(d)]
+        u_imag = [u[dim].imag for dim in range(d)]
+        for dim in range(d):
+            u_real[dim].ravel()[0] = 0
+            u_imag[dim].ravel()[0] = 0
+
+        u_real_h = [np.sqrt(2 / d * ek / (u_imag[dim] ** 2 + u_real[dim] ** 2 + 1.e-15)) * u_real[dim]
+                    for dim in range(d)]
+        u_imag_h = [np.sqrt(2 / d * ek / (u_imag[dim] ** 2 + u_real[dim] ** 2 + 1.e-15)) * u_imag[dim]
+                    for dim in range(d)]
+        for dim in range(d):
+            u_real_h[dim].ravel()[0] = 0
+            u_imag_h[dim].ravel()[0] = 0
+
+        # remove the divergence, with the modified wavenumber sin(k dx) / dx of second-order central differences
+        wavenumber_modified = [np.sin(wavenumber[dim] * dx) / dx for dim in range(d)]
+        wavenorm_modified = np.linalg.norm(wavenumber_modified, axis=0) + 1e-16
+
+        divergence_real = np.zeros(self.dimensions)
+        divergence_imag = np.zeros(self.dimensions)
+        for dim in range(d):
+            divergence_real += wavenumber_modified[dim] * u_real_h[dim]
+            divergence_imag += wavenumber_modified[dim] * u_imag_h[dim]
+
+        u_real = [u_real_h[dim] - divergence_real * wavenumber_modified[dim] / wavenorm_modified ** 2
+                  for dim in range(d)]
+        u_imag = [u_imag_h[dim] - divergence_imag * wavenumber_modified[dim] / wavenorm_modified ** 2
+                  for dim in range(d)]
+        for dim in range(d):
+            u_real[dim].ravel()[0] = 0
+            u_imag[dim].ravel()[0] = 0
+
+        # scale the velocity field to the initial energy asked for
+        e_kin = [np.sum(u_real[dim] ** 2 + u_imag[dim] ** 2) for dim in range(d)]
+        e_kin = np.sum(e_kin) * .5
+
+        factor = np.sqrt(self.ic_energy / e_kin)
+        u_real = [u_real[dim] * factor for dim in range(d)]
+        u_imag = [u_imag[dim] * factor for dim in range(d)]
+
+        # back to physical space
+        norm = ((self.resolution[0] * dx ** (1 - d) * np.sqrt(self.units.characteristic_length_pu))
+                if d == 3 else (self.resolution[0] / dx))
+
+        u = np.asarray([(np.fft.ifftn(u_real[dim] + u_imag[dim] * 1.0j, axes=axes) * norm).real
+                        for dim in range(d)])
+        return u
+
+    def _compute_initial_pressure(self):
+        return np.zeros(self.dimensions)[None, ...]
+
+    def initial_pu(self):
+        """Initial pressure and velocity; sets the characteristic velocity in physical units, as the reference."""
+        ek, wavenumber = self._generate_spectrum()
+        u = self._generate_initial_velocity(ek, wavenumber)
+        self.units.characteristic_velocity_pu = np.array(u).max()
+        p = self._compute_initial_pressure()
+        self.units.characteristic_velocity_pu = np.linalg.norm(u, axis=0).max()
+        return p, u
+
+    @property
+    def energy_spectrum(self):
+        return self.spectrum, self.wavenumbers
+
+    @property
+    def grid(self):
+        endpoints = [2 * torch.pi * (1 - 1 / n) for n in self.resolution]      # like endpoint=False in np.linspace
+        xyz = tuple(torch.linspace(0, endpoints[n], steps=self.resolution[n], device=self.context.device,
+                                   dtype=self.context.dtype) for n in range(self.stencil.d))
+        return torch.meshgrid(*xyz, indexing="ij")
+
+    @property
+    def boundaries(self) -> List["Boundary"]:
+        return []
 
 
 # name -> flow class, as used by `lettuce benchmark` (lettuce/ext/_flows/_flow_by_name.py:10-16)

@@ -1,23 +1,29 @@
 """Observables read between steps ("next" row F3) and the reporter that logs them.
 
-API of lettuce/ext/_reporter/observable_reporter.py:17-42,140-199.  On a native context the
+API of lettuce/ext/_reporter/observable_reporter.py:17-199.  On a native context the
 kinetic energy, the maximum velocity, the enstrophy and the Mass observable are device-side
 wavefront/LDS reductions in fp64 (``lt_kinetic_energy``, ``lt_max_velocity``, ``lt_enstrophy``,
 ``lt_mass_interior``); the enstrophy uses one [d, *res] scratch field for u, the others none.
-VTK / HDF5 / image writers, the energy spectrum and the error reporter are host-side
-post-processing and out of scope.
+The energy spectrum is one ``torch.fft.fftn`` of the velocity field and one binning reduction on the
+device (``lt_energy_spectrum``: integer bins, fp64, fixed order); neither path builds the
+reference's [*res, K] wave mask, so the observable runs at the engine's grid sizes.
+VTK / HDF5 / image writers are host-side post-processing and out of scope.
 """
+import math
 import sys
 from abc import ABC, abstractmethod
 from typing import Optional
 
+import numpy as np
 import torch
 
+from .._errors import LettuceException
+from .._native import SPECTRUM_MAX_BINS
 from .._simulation import Reporter
 from ..util import torch_gradient
 
 __all__ = ["Observable", "ObservableReporter", "MaximumVelocity", "IncompressibleKineticEnergy",
-           "Enstrophy", "Mass", "ErrorReporter"]
+           "Enstrophy", "EnergySpectrum", "Mass", "ErrorReporter"]
 
 
 class Observable(ABC):
@@ -79,6 +85,84 @@ class Enstrophy(Observable):
             w_y = grad[0][2] - grad[2][0]
             total += torch.sum(w_x * w_x + w_y * w_y)
         return total * dx ** flow.stencil.d
+
+
+def spectrum_bins(resolution, device=None):
+    """``(bins, K)`` of the reference's wave mask (observable_reporter.py:78-97), in integers: ``bins`` [*resolution],
+    int64, holds the bin of every Fourier mode and ``K`` is the number of bins.  Index i on an axis of extent n has the
+    wavenumber k = fftfreq(n, 1 / n)[i]; with m = sum_a k_a^2 the bin is 0 for m = 0 and else the n >= 1 with
+    n^2 - n < m <= n^2 + n, which is the reference's n - 0.5 < |k| <= n + 0.5 squared (an integer m never ties with
+    n^2 + n + 1/4).  K = isqrt(max m), the reference's int(max |k|); modes with a bin >= K belong to no bin."""
+    d = len(resolution)
+    m = torch.zeros([1] * d, dtype=torch.int64, device=device)
+    for a, n in enumerate(resolution):
+        i = torch.arange(n, dtype=torch.int64, device=device)
+        k = torch.where(i < (n + 1) // 2, i, i - n)
+        m = m + (k * k).reshape([-1 if b == a else 1 for b in range(d)])
+    # a first guess from the floating-point root, corrected by the two integer comparisons that decide
+    bins = torch.sqrt(m.to(torch.float64)).to(torch.int64)
+    bins = bins + (bins * bins + bins < m).to(torch.int64)
+    bins = bins - ((bins * bins - bins >= m) & (m > 0)).to(torch.int64)
+    return bins, math.isqrt(int(m.max()))
+
+
+class EnergySpectrum(Observable):
+    """The kinetic energy spectrum (observable_reporter.py:71-137): E(n) = sum over the Fourier modes with
+    n - 0.5 < |k| <= n + 0.5 of 0.5 |u_hat / norm|^2, n < K = int(max |k|).
+
+    The reference sums ``ekin[..., None] * wavemask`` with a boolean mask [*res, K] (3.7 GB at 256^3).  Here every
+    mode is binned by index instead.  On a native context: ``flow.u()``, one ``torch.fft.fftn`` over the [d, *res]
+    field and ``lt_energy_spectrum`` (fp64 squares and sums in a fixed order, cast to the context dtype at the end).
+    Elsewhere the same bin index with ``index_add_`` in the context dtype.  Both differ from the reference's values
+    at rounding level only.  Needs the whole field: not ``slab_aware``, a slab simulation refuses it by name."""
+
+    def __init__(self, flow: "Flow"):
+        super().__init__(flow)
+        self.dx = self.flow.units.convert_length_to_pu(1.0)
+        self.dimensions = self.flow.resolution
+        d = self.flow.stencil.d
+        if d not in (2, 3) or len(self.dimensions) != d:
+            raise LettuceException(f"EnergySpectrum: 2-D and 3-D flows, this one has d = {d} on {list(self.dimensions)}")
+        if d == 3:
+            self.norm = self.dimensions[0] * np.sqrt(2 * np.pi) / self.dx ** 2
+        else:
+            self.norm = self.dimensions[0] / self.dx
+        self._n_bins = math.isqrt(sum((n // 2) ** 2 for n in self.dimensions))
+        self.wavenumbers = torch.arange(self._n_bins)
+        self._bins = None           # torch path: [nodes] int64 on the context's device, K for the modes of no bin
+        self._wavemask = None
+
+    @property
+    def wavemask(self):
+        """the reference's boolean mask [*res, K], kept for compatibility: built on first access, used by nothing"""
+        if self._wavemask is None:
+            bins, _ = spectrum_bins(self.dimensions, self.context.device)
+            self._wavemask = bins[..., None] == self.wavenumbers.to(self.context.device)
+        return self._wavemask
+
+    def __call__(self, f: Optional[torch.Tensor] = None):
+        return self.spectrum_from_u(self.flow.u())
+
+    def spectrum_from_u(self, u):
+        flow = self.flow
+        d = flow.stencil.d
+        u = flow.units.convert_velocity_to_pu(u)
+        axes = tuple(range(1, d + 1))
+        plan = flow._engine_plan(flow.f) if (u.is_cuda and u.dtype == self.context.dtype
+                                             and list(u.shape) == [d, *self.dimensions]) else None
+        if plan is not None and 1 <= self._n_bins <= SPECTRUM_MAX_BINS:
+            uh = torch.fft.fftn(u, dim=axes)
+            ek = plan.energy_spectrum(uh, 1.0 / float(self.norm) ** 2, self._n_bins)
+            return ek.to(self.context.dtype)
+        # above LT_SPECTRUM_MAX_BINS bins (a grid beyond 2000^3) the kernel's table no longer fits: the torch path
+        uh = torch.fft.fftn(u, dim=axes) / self.norm
+        ekin = torch.sum(0.5 * (uh.imag ** 2 + uh.real ** 2), dim=0)
+        if self._bins is None or self._bins.device != ekin.device:
+            bins, _ = spectrum_bins(self.dimensions, ekin.device)
+            self._bins = bins.clamp(max=self._n_bins).reshape(-1)
+        ek = torch.zeros(self._n_bins + 1, dtype=ekin.dtype, device=ekin.device)
+        ek.index_add_(0, self._bins, ekin.reshape(-1))
+        return ek[:self._n_bins]
 
 
 class Mass(Observable):
