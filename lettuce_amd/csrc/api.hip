@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <type_traits>
 
 #include "dispatch.hpp"
 #include "kernels.hpp"
@@ -126,38 +127,45 @@ struct lt_plan {
   int n0, n1, n2;            // memory extents incl. ghost planes
   int interior_begin, interior_end;   // a2 planes that are real nodes
   long long N;               // n0*n1*n2
-  int shift;                 // lt_plan_set_shift_policy: workgroup order of the two-step kernel (A/B)
-  int tune = -1;             // cache policy: -1 = automatic
-  int residency = -1;        // workgroups per CU of the big launches: -1 = automatic, 0 = no cap
   int n_cu = 0;              // compute units of the plan's device
-  double smagorinsky = 0.17; // Smagorinsky constant (lt_plan_set_smagorinsky); the reference's default
-  double tau_minus = 1.0;    // TRT: relaxation time of the antisymmetric part (lt_plan_set_trt); the reference's default
-  // MRT (lt_plan_set_mrt): the transform (lt_mrt_transform; 0 = not set yet) and the relaxation rates of its q moments
-  struct Mrt {
-    int transform = 0;
-    double rates[27] = {};
-    bool operator==(const Mrt &o) const {
-      return transform == o.transform && std::equal(rates, rates + 27, o.rates);
+  // What a setter may change between two launches and every launch reads, like tau.  One record: a captured graph is
+  // replayed only for the Settings it was captured with (run_graph compares the whole of it), and a new setting is
+  // added here -- its field, its term in operator==, and its line in fill() if it is a value the kernels take (the
+  // four at the end choose the kernel and its launch instead: kernel_selector, resolve_tune, resolve_lds)
+  struct Settings {
+    double smagorinsky = 0.17; // Smagorinsky constant (lt_plan_set_smagorinsky); the reference's default
+    double tau_minus = 1.0;    // TRT: relaxation time of the antisymmetric part (lt_plan_set_trt); the reference's default
+    // MRT (lt_plan_set_mrt): the transform (lt_mrt_transform; 0 = not set yet) and the relaxation rates of its q moments
+    struct Mrt { int transform = 0; double rates[27] = {}; } mrt;
+    // uniform body force (lt_plan_set_force).  on: the kernels with COLL = 4 + collision
+    struct Force { bool on = false; double a[3] = {0.0, 0.0, 0.0}, ueq_scale = 0.0, source_scale = 0.0; } force;
+    // the equilibrium (lt_plan_set_equilibrium): lt_equilibrium_kind and, for the incompressible one, its rho0
+    int equilibrium = LT_EQUILIBRIUM_QUADRATIC;
+    double rho0 = 1.0;
+    int masked = 0;            // lt_plan_set_masks
+    int tune = -1;             // cache policy: -1 = automatic
+    int shift = 0;             // lt_plan_set_shift_policy: workgroup order of the two-step kernel (A/B)
+    int residency = -1;        // workgroups per CU of the big launches: -1 = automatic, 0 = no cap
+    bool operator==(const Settings &o) const {
+      return smagorinsky == o.smagorinsky && tau_minus == o.tau_minus && mrt.transform == o.mrt.transform &&
+             std::equal(mrt.rates, mrt.rates + 27, o.mrt.rates) && force.on == o.force.on &&
+             std::equal(force.a, force.a + 3, o.force.a) && force.ueq_scale == o.force.ueq_scale &&
+             force.source_scale == o.force.source_scale && equilibrium == o.equilibrium && rho0 == o.rho0 &&
+             masked == o.masked && tune == o.tune && shift == o.shift && residency == o.residency;
     }
-  } mrt;
-  // uniform body force (lt_plan_set_force): read at every launch like tau.  forced: the kernels with COLL = 4 + collision
-  struct Force {
-    bool on = false;
-    double a[3] = {0.0, 0.0, 0.0}, ueq_scale = 0.0, source_scale = 0.0;
-    bool operator==(const Force &o) const {
-      return on == o.on && a[0] == o.a[0] && a[1] == o.a[1] && a[2] == o.a[2] && ueq_scale == o.ueq_scale &&
-             source_scale == o.source_scale;
+    void fill(lt::StepArgs &a) const {
+      a.smagorinsky = smagorinsky;
+      a.tau_minus = tau_minus;
+      a.mrt_transform = mrt.transform;
+      std::copy(mrt.rates, mrt.rates + 27, a.mrt_rates);
+      std::copy(force.a, force.a + 3, a.accel);
+      a.ueq_scale = force.ueq_scale; a.source_scale = force.source_scale;
+      a.rho0 = rho0;
     }
-  } force;
-  // the equilibrium (lt_plan_set_equilibrium): lt_equilibrium_kind and, for the incompressible one, its rho0; read at
-  // every launch like tau
-  int equilibrium = LT_EQUILIBRIUM_QUADRATIC;
-  double rho0 = 1.0;
+  } set;
   int two_step = -1;         // lt_run: pair the fused steps (lbm2_kernel): -1 = automatic, 0 / 1
   int seg_len = 0;           // planes per workgroup of the two-step kernel, 0 = automatic
   int many = -1;             // lt_run: several steps per launch on small 2-D grids: -1 = automatic, 0 / 1
-  int many_now = 1;          // steps of the kFusedMany launch being issued
-  long long second_begin = 0, second_end = 0;   // second plane range of the kFusedTwice launch being issued
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // lt_plan_set_fused_events
   long long last_single = 0, last_twice = 0, last_many = 0;   // fused launches of the last lt_run
   // engine-owned device scratch
@@ -165,7 +173,6 @@ struct lt_plan {
   unsigned *nsm_bits = nullptr;
   void *bt = nullptr;        // BoundaryTable<T>
   double *partial = nullptr;
-  int masked = 0;
   int n_abb = 0;             // anti-bounce-back outlets of the plan
   int n_pout = 0;            // constant-pressure outlets of the plan (one-step kernels only: multi_step_refusal)
   int abb_depth = 0;         // how deep an outlet's neighbour must be rebuilt (lt_plan_create)
@@ -177,14 +184,10 @@ struct lt_plan {
   unsigned long long *signal = nullptr;
   unsigned long long signal_target = 0;
   unsigned *signal_timed_out = nullptr;
-  unsigned long long *signal_now = nullptr;   // where step() finds the counter for the launch being issued (or null)
-  const void *ghost_lo_now = nullptr, *ghost_hi_now = nullptr;   // received halo messages the edge launch being issued reads
   int defer_stream = 0;      // lt_run / lt_continue stop before their last (streaming) pass (lt_plan_set_deferred_stream)
   // distance between consecutive populations of the caller's buffers, in elements (lt_plan_set_population_stride);
-  // 0 = dense (N).  stride_in_now / stride_out_now: what step() uses for the launch being issued when the two
-  // differ from it (the resident entry points move between the caller's dense buffers and the padded ones)
+  // 0 = dense (N)
   long long pop_stride = 0;
-  long long stride_in_now = -1, stride_out_now = -1;
   // engine-owned padded population buffers (lt_resident_*): res[res_cur] holds the post-collision populations
   int resident = -1;         // -1 = automatic, 0 = off, 1 = on (lt_plan_set_resident)
   long long res_pad = -1;    // elements between the end of one population and the start of the next; -1 = automatic
@@ -195,7 +198,6 @@ struct lt_plan {
   // first-use check of the masked two-step kernel (run_canary; lt_plan_set_canary / lt_plan_canary_status)
   int canary_mode = 1;       // 1 = check on first use, 0 = skip, 2 = test hook: report a mismatch without launching
   int canary = 0;            // 0 = not run for the present masks / settings, 1 = passed, 2 = skipped, -1 = failed
-  int canary_running = 0;
   long long canary_mismatches = 0;
   char canary_msg[320] = "";
   hipStream_t cstream = nullptr;
@@ -206,7 +208,7 @@ struct lt_plan {
   hipStream_t gstream = nullptr;
   hipEvent_t gev_in = nullptr, gev_out = nullptr;
   hipGraphExec_t gexec = nullptr;
-  struct { void *a, *b; double tau, smagorinsky, tau_minus; int masked, tune, shift, residency; Force force; Mrt mrt; int equilibrium; double rho0; } gkey = {};
+  struct { void *a, *b; double tau; Settings set; } gkey = {};
 };
 
 namespace {
@@ -251,7 +253,7 @@ int upload_boundaries(lt_plan *p, hipStream_t stream) {
   return LT_OK;
 }
 
-int check_boundary(const lt_plan *p, const lt_boundary_desc &b, int n_abb_before) {
+int check_boundary(const lt_plan *p, const lt_boundary_desc &b) {
   switch (b.kind) {
     case LT_BOUNDARY_BOUNCE_BACK:
     case LT_BOUNDARY_EQUILIBRIUM:
@@ -272,9 +274,7 @@ int check_boundary(const lt_plan *p, const lt_boundary_desc &b, int n_abb_before
   }
 }
 
-// Nontemporal accesses pay off when the two population buffers cannot stay in the caches
-// (32 MiB L2 + 256 MiB Infinity Cache); small grids keep cached stores.
-// populations whose velocity component along the slowest memory axis equals `dir`
+// populations whose velocity component along logical axis `logical_axis` equals `dir`
 template <class S>
 lt::QList crossing_of(int logical_axis, int dir) {
   lt::QList l;
@@ -282,17 +282,6 @@ lt::QList crossing_of(int logical_axis, int dir) {
   for (int q = 0; q < S::Q; ++q)
     if (S::E[q][logical_axis] == dir && l.n < 9) l.q[l.n++] = q;
   return l;
-}
-
-lt::QList crossing(const lt_plan *p, int dir) {
-  const int axis = p->unit.d == 2 ? 0 : (p->desc.layout == LT_LAYOUT_REFERENCE ? 0 : 2);
-  switch (p->desc.stencil) {
-    case LT_D1Q3: return crossing_of<lt::D1Q3>(0, dir);
-    case LT_D2Q9: return crossing_of<lt::D2Q9>(axis, dir);
-    case LT_D3Q15: return crossing_of<lt::D3Q15>(axis, dir);
-    case LT_D3Q19: return crossing_of<lt::D3Q19>(axis, dir);
-    default: return crossing_of<lt::D3Q27>(axis, dir);
-  }
 }
 
 // populations whose velocity component along MEMORY axis `mem_axis` equals `dir` (the axis maps are
@@ -307,6 +296,19 @@ lt::QList crossing_axis(const lt_plan *p, int mem_axis, int dir) {
     default: return crossing_of<lt::D3Q27>(axis, dir);
   }
 }
+// ... along the slowest memory axis, the one the sweeps run along and the slabs are cut along
+lt::QList crossing(const lt_plan *p, int dir) { return crossing_axis(p, p->unit.d == 2 ? 1 : 2, dir); }
+
+// a pack / unpack kernel of the plan's scalar type: launch(T(), std::bool_constant<PACK>()) for the dtype and the
+// direction of the copy (PACK: field -> buffer)
+template <class F>
+void with_dtype_and_direction(const lt_plan *p, bool do_pack, F launch) {
+  if (p->desc.dtype == LT_F32) {
+    if (do_pack) launch(float(), std::true_type()); else launch(float(), std::false_type());
+  } else {
+    if (do_pack) launch(double(), std::true_type()); else launch(double(), std::false_type());
+  }
+}
 
 int pack(lt_plan *p, bool do_pack, void *f, long long plane, int dir, void *buf, void *stream) {
   if (!p || !f || !buf) return fail(LT_ERR_INVALID, "null argument");
@@ -317,23 +319,19 @@ int pack(lt_plan *p, bool do_pack, void *f, long long plane, int dir, void *buf,
   const long long off = plane * plane_nodes;
   const unsigned grid = (plane_nodes + lt::kThreads - 1) / lt::kThreads;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (p->desc.dtype == LT_F32) {
-    if (do_pack) hipLaunchKernelGGL((lt::plane_pack_kernel<float, true>), dim3(grid), dim3(lt::kThreads), 0, s,
-                                    (float *)f, (float *)buf, pop_stride_of(p), off, plane_nodes, ql);
-    else hipLaunchKernelGGL((lt::plane_pack_kernel<float, false>), dim3(grid), dim3(lt::kThreads), 0, s,
-                            (float *)f, (float *)buf, pop_stride_of(p), off, plane_nodes, ql);
-  } else {
-    if (do_pack) hipLaunchKernelGGL((lt::plane_pack_kernel<double, true>), dim3(grid), dim3(lt::kThreads), 0, s,
-                                    (double *)f, (double *)buf, pop_stride_of(p), off, plane_nodes, ql);
-    else hipLaunchKernelGGL((lt::plane_pack_kernel<double, false>), dim3(grid), dim3(lt::kThreads), 0, s,
-                            (double *)f, (double *)buf, pop_stride_of(p), off, plane_nodes, ql);
-  }
+  with_dtype_and_direction(p, do_pack, [&](auto scalar, auto packs) {
+    using T = decltype(scalar);
+    hipLaunchKernelGGL((lt::plane_pack_kernel<T, decltype(packs)::value>), dim3(grid), dim3(lt::kThreads), 0, s, (T *)f,
+                       (T *)buf, pop_stride_of(p), off, plane_nodes, ql);
+  });
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
 
+// Nontemporal accesses pay off when the two population buffers cannot stay in the caches
+// (32 MiB L2 + 256 MiB Infinity Cache); small grids keep cached stores.
 int resolve_tune(const lt_plan *p) {
-  if (p->tune == 0 || p->tune == 3) return p->tune;
+  if (p->set.tune == 0 || p->set.tune == 3) return p->set.tune;
   const long long bytes = 2ll * p->unit.q * p->N * p->esize;
   return bytes > (128ll << 20) ? 3 : 0;
 }
@@ -345,7 +343,7 @@ int resolve_tune(const lt_plan *p) {
 // allocation (160 KB per CU).  Only for launches that fill the chip several times over and stream
 // from HBM; small launches (boundary planes beside the interior launch, small grids) stay uncapped.
 int resolve_lds(const lt_plan *p, long long workgroups) {
-  int n = p->residency;
+  int n = p->set.residency;
   if (n < 0) {
     const long long bytes = 2ll * p->unit.q * p->N * p->esize;
     const bool kbc32 = p->desc.collision == LT_COLLISION_KBC && p->esize == 4;
@@ -364,9 +362,9 @@ int resolve_lds(const lt_plan *p, long long workgroups) {
 // each) 32768 + 64 elements was the best or within a per cent of the best everywhere: two-step launch -7.0 % at
 // 256^3 fp32 (populations exactly 64 MiB apart when dense), -2.3 % at 512 x 512 x 64, -5.1 % at 256 x 256 x 512,
 // -4.9 % at 384^3, -5.2 % at 256^3 fp64, -3.9 % for D3Q15 (profiles/r03_pad_sweep_robust.jsonl).
-long long default_pad(const lt_plan *) { return 32768 + 64; }
+long long default_pad() { return 32768 + 64; }
 long long resident_stride(const lt_plan *p) {
-  const long long pad = p->res_pad >= 0 ? p->res_pad : default_pad(p);
+  const long long pad = p->res_pad >= 0 ? p->res_pad : default_pad();
   const long long unit = 256 / p->esize;                      // keep every population 256-byte aligned
   return (p->N + pad + unit - 1) / unit * unit;
 }
@@ -417,7 +415,7 @@ TwoStepTile two_step_tile_of(int d, int q, int esize, int n0, bool masked = fals
   return {width, rows};
 }
 TwoStepTile two_step_tile(const lt_plan *p) {
-  return two_step_tile_of(p->unit.d, p->unit.q, p->esize, p->n0, p->masked != 0);
+  return two_step_tile_of(p->unit.d, p->unit.q, p->esize, p->n0, p->set.masked != 0);
 }
 
 // The 3-D two-step kernels address with 32-bit byte offsets: lbm2_kernel within a plane, lbm2m_kernel (buffer
@@ -441,8 +439,10 @@ bool masked_big_exists(int layout, int collision, int q) {
 // planes.  Pick the divisor L of n2 with the best (L / (L + 2)) * (blocks / blocks rounded up to
 // whole rounds): 128 planes = 256 workgroups at 256^3 (measured 0.3345 ms per step against 0.3412
 // with 32 planes and 0.52 with 256, which leaves half the CUs idle).
-int resolve_seg_len(const lt_plan *p, int planes) {
-  if (p->seg_len > (p->masked ? 1 : 0)) return p->seg_len;
+// `override` > 0: the launch's own segment length in place of the plan's (lt_plan_set_two_step).
+int resolve_seg_len(const lt_plan *p, int planes, int override = 0) {
+  const int asked = override > 0 ? override : p->seg_len;
+  if (asked > (p->set.masked ? 1 : 0)) return asked;
   const TwoStepTile tile = two_step_tile(p);
   long long tiles = (long long)(p->n0 / tile.width) * (p->n1 / (tile.rows ? tile.rows : 8));
   long long cus = p->n_cu > 0 ? p->n_cu : 256;
@@ -454,7 +454,7 @@ int resolve_seg_len(const lt_plan *p, int planes) {
   }
   int best = 1;
   double best_score = -1.0;
-  for (int len = p->masked ? 2 : 1; len <= planes; ++len) {   // masked: the outlet's plane never opens a segment
+  for (int len = p->set.masked ? 2 : 1; len <= planes; ++len) {   // masked: the outlet's plane never opens a segment
     const long long segs = (planes + len - 1) / len;
     if (!p->desc.ghost_planes && planes % len) continue;   // keep whole-grid launches evenly cut
     const long long blocks = tiles * segs;
@@ -486,21 +486,15 @@ int halo2(lt_plan *p, bool do_pack, void *f, int side, void *buf, void *stream) 
   }
   const lt::QList in_plane = crossing(p, 0), cross = crossing(p, dir);
   lt::QList away = crossing(p, -dir);
-  if (!p->masked) away.n = 0;                      // only a no-streaming node ever reads them
+  if (!p->set.masked) away.n = 0;                      // only a no-streaming node ever reads them
   const int plane_nodes = p->n0 * p->n1;
   const unsigned grid = (plane_nodes + lt::kThreads - 1) / lt::kThreads;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (p->desc.dtype == LT_F32) {
-    if (do_pack) hipLaunchKernelGGL((lt::halo2_kernel<float, true>), dim3(grid), dim3(lt::kThreads), 0, s, (float *)f,
-                                    (float *)buf, pop_stride_of(p), near * plane_nodes, far * plane_nodes, plane_nodes, in_plane, cross, away);
-    else hipLaunchKernelGGL((lt::halo2_kernel<float, false>), dim3(grid), dim3(lt::kThreads), 0, s, (float *)f,
-                            (float *)buf, pop_stride_of(p), near * plane_nodes, far * plane_nodes, plane_nodes, in_plane, cross, away);
-  } else {
-    if (do_pack) hipLaunchKernelGGL((lt::halo2_kernel<double, true>), dim3(grid), dim3(lt::kThreads), 0, s, (double *)f,
-                                    (double *)buf, pop_stride_of(p), near * plane_nodes, far * plane_nodes, plane_nodes, in_plane, cross, away);
-    else hipLaunchKernelGGL((lt::halo2_kernel<double, false>), dim3(grid), dim3(lt::kThreads), 0, s, (double *)f,
-                            (double *)buf, pop_stride_of(p), near * plane_nodes, far * plane_nodes, plane_nodes, in_plane, cross, away);
-  }
+  with_dtype_and_direction(p, do_pack, [&](auto scalar, auto packs) {
+    using T = decltype(scalar);
+    hipLaunchKernelGGL((lt::halo2_kernel<T, decltype(packs)::value>), dim3(grid), dim3(lt::kThreads), 0, s, (T *)f,
+                       (T *)buf, pop_stride_of(p), near * plane_nodes, far * plane_nodes, plane_nodes, in_plane, cross, away);
+  });
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
@@ -542,15 +536,40 @@ bool canary_ok(lt_plan *p);
 // transform (Dellar and Hermite are told apart by the lattice)
 int kernel_coll(const lt_plan *p) {
   if (p->desc.collision == LT_COLLISION_MRT)
-    return p->mrt.transform == LT_MRT_D2Q9_LALLEMAND ? lt::kCollMrtLallemand : lt::kCollMrt;
+    return p->set.mrt.transform == LT_MRT_D2Q9_LALLEMAND ? lt::kCollMrtLallemand : lt::kCollMrt;
   // the incompressible equilibrium: the collisions that evaluate feq get kernels of their own (no collision does not)
-  const bool incompressible = p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE && p->desc.collision != LT_COLLISION_NONE;
-  return p->desc.collision | (p->force.on ? lt::kCollForce : 0) | (incompressible ? lt::kCollIncompressible : 0);
+  const bool incompressible = p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE && p->desc.collision != LT_COLLISION_NONE;
+  return p->desc.collision | (p->set.force.on ? lt::kCollForce : 0) | (incompressible ? lt::kCollIncompressible : 0);
 }
 static_assert(lt::kCollNone == LT_COLLISION_NONE && lt::kCollBgk == LT_COLLISION_BGK && lt::kCollKbc == LT_COLLISION_KBC &&
               lt::kCollSmagorinsky == LT_COLLISION_SMAGORINSKY && lt::kCollTrt == LT_COLLISION_TRT &&
               lt::kCollRegularized == LT_COLLISION_REGULARIZED && lt::kCollMrt == LT_COLLISION_MRT,
               "the kernels' collision numbers are the ABI's where the ABI has the operator");
+
+// Zeroed kernel arguments with the fields set that choose the kernel of a launch of `mode` on this plan (unit.inc,
+// dispatch): what step() launches with, and what every question "has the unit such a kernel" / "what is its name" is
+// asked with, so that the answer is about the kernel the launch will take
+lt::StepArgs kernel_selector(const lt_plan *p, int mode) {
+  lt::StepArgs a;
+  memset(&a, 0, sizeof a);
+  const bool masked = p->set.masked != 0;
+  a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = mode;
+  a.masked = p->set.masked;
+  a.abb_depth = p->abb_depth;
+  a.abb_axis = masked ? masked_two_step_axis(p) : 2;
+  a.n_abb = masked ? p->n_abb : 0;
+  a.n_pout = masked ? p->n_pout : 0;
+  if (masked && p->n_abb == 1 && p->n_pout == 0)
+    for (int i = 0; i < p->desc.n_boundaries; ++i) {
+      const lt_boundary_desc &b = p->desc.boundaries[i];
+      if (b.kind == LT_BOUNDARY_ABB_OUTLET && !(b.flags & LT_BOUNDARY_ABSENT) && mem_axis_of(p, b.axis) == 0)
+        a.abb0_slot = i + 1;
+    }
+  a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
+  a.shift = p->set.shift;                              // workgroup-order A/B variant of the two-step sweeps
+  a.tune = resolve_tune(p);
+  return a;
+}
 
 // ---- which plans have a launch of several steps ----
 const char *const kForceMultiStep = "a body force (lt_plan_set_force) has the one-step kernels and the plain two-step sweep "
@@ -589,15 +608,12 @@ const char *multi_step_refusal(const lt_plan *p, int mode) {
   const bool twice = mode == lt::kFusedTwice;
   // what a body force, TRT and the regularised collision have beside the one-step kernels (unit.inc, parts forced and
   // relaxations): the plain two-step sweep of periodic D3Q19 fp32 plans without masks
-  const bool plain_sweep = twice && p->unit.d == 3 && !p->masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
+  const bool plain_sweep = twice && p->unit.d == 3 && !p->set.masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
                            p->desc.dtype == LT_F32;
-  if (p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE) return kIncompressibleMultiStep;   // (unit.inc, part incompressible)
-  if (p->force.on) {
+  if (p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE) return kIncompressibleMultiStep;   // (unit.inc, part incompressible)
+  if (p->set.force.on) {
     if (!plain_sweep) return kForceMultiStep;
-    lt::StepArgs a;
-    memset(&a, 0, sizeof a);
-    a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = lt::kFusedTwice;
-    if (!has_kernel(p->unit, a)) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
+    if (!has_kernel(p->unit, kernel_selector(p, lt::kFusedTwice))) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
   }
   if (p->desc.collision == LT_COLLISION_TRT && !plain_sweep) return kTrtMultiStep;
   if (p->desc.collision == LT_COLLISION_REGULARIZED && !plain_sweep) return kRegularizedMultiStep;
@@ -605,16 +621,40 @@ const char *multi_step_refusal(const lt_plan *p, int mode) {
   if (p->desc.collision == LT_COLLISION_MRT) return kMrtMultiStep;     // the one-step kernels only (unit.inc, part mrt)
   if (twice && p->desc.ghost_planes && p->desc.collision == LT_COLLISION_SMAGORINSKY) return kSmagorinskySlabs;
   // masks: their admission, and on a slab an outlet only along the rows
-  if (twice && p->masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0)))
+  if (twice && p->set.masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0)))
     return kMaskedTwoStep;
   return nullptr;
 }
 
-int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long pb, long long pe,
-         void *stream, long long stride = 1, void *pack_lo = nullptr, void *pack_hi = nullptr) {
+// One call of step(): what belongs to the launch and not to the plan.  Every entry point builds its own and hands it
+// over; step() keeps nothing of it in the plan.
+struct Launch {
+  int mode;
+  const void *in;
+  void *out;
+  double tau;
+  long long begin, end;                          // a2 planes [begin, end) ...
+  void *stream;
+  long long stride = 1;                          // ... every stride-th of them
+  void *pack_lo = nullptr, *pack_hi = nullptr;   // halo messages the launch writes (or null)
+  long long begin2 = 0, end2 = 0;                // kFusedTwice: second plane range (a slab's other edge)
+  int many = 1;                                  // kFusedMany: steps of the launch
+  int seg_len = 0;                               // kFusedTwice: planes per workgroup; 0 = the plan's (resolve_seg_len)
+  unsigned long long *signal = nullptr;          // counter the edge workgroups of the signalling slab launch add to
+  const void *ghost_lo = nullptr, *ghost_hi = nullptr;   // received halo messages the direct edge launch reads
+  long long stride_in = -1, stride_out = -1;     // elements between the populations of in / out; < 0: the plan's pop_stride
+  bool canary = false;                           // a launch of the first-use check itself (run_canary): no check of its own
+  Launch(int mode_, const void *in_, void *out_, double tau_, long long begin_, long long end_, void *stream_)
+      : mode(mode_), in(in_), out(out_), tau(tau_), begin(begin_), end(end_), stream(stream_) {}
+};
+
+int step(lt_plan *p, const Launch &l) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
-  if (!in || !out) return fail(LT_ERR_INVALID, "null population buffer");
-  if (in == out) return fail(LT_ERR_INVALID, "in-place operation is not supported (in == out)");
+  const int mode = l.mode;
+  const long long pb = l.begin, pe = l.end, stride = l.stride;
+  const double tau = l.tau;
+  if (!l.in || !l.out) return fail(LT_ERR_INVALID, "null population buffer");
+  if (l.in == l.out) return fail(LT_ERR_INVALID, "in-place operation is not supported (in == out)");
   if (pb < 0 || pe > p->n2 || pb > pe)
     return fail(LT_ERR_INVALID, "plane range [%lld, %lld) outside [0, %d)", pb, pe, p->n2);
   if (p->desc.ghost_planes && (pb < 1 || pe > p->n2 - 1) && mode != lt::kCollideOnly && pe > pb)
@@ -629,9 +669,9 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
   };
   if (why && !after_range) return refuse();
   const bool mrt = p->desc.collision == LT_COLLISION_MRT;
-  if (mrt && mode != lt::kStreamOnly && p->mrt.transform == 0)
+  if (mrt && mode != lt::kStreamOnly && p->set.mrt.transform == 0)
     return fail(LT_ERR_INVALID, "the plan's collision is MRT: lt_plan_set_mrt must give the transform and the rates first");
-  if (mode == lt::kFusedMany && (p->desc.ghost_planes || (p->masked && p->n_abb > 1)))
+  if (mode == lt::kFusedMany && (p->desc.ghost_planes || (p->set.masked && p->n_abb > 1)))
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: no slabs, at most one anti-bounce-back outlet");
   if (mode == lt::kFusedTwice) {
     if (p->desc.ghost_planes == 1)
@@ -642,58 +682,35 @@ int step(lt_plan *p, int mode, const void *in, void *out, double tau, long long 
     if (!p->desc.ghost_planes && (pb != 0 || pe != p->n2))
       return fail(LT_ERR_INVALID, "periodic plan: the two-step launch covers all planes");
     if (why) return refuse();
-    if (p->masked && !p->canary_running && !canary_ok(p)) return fail(LT_ERR_UNSUPPORTED, "%s", p->canary_msg);
+    if (p->set.masked && !l.canary && !canary_ok(p)) return fail(LT_ERR_UNSUPPORTED, "%s", p->canary_msg);
   }
-  if (p->desc.n_boundaries > 0 && !p->masked)
+  if (p->desc.n_boundaries > 0 && !p->set.masked)
     return fail(LT_ERR_INVALID, "plan has boundaries but lt_plan_set_masks was not called");
   if (mode != lt::kStreamOnly && p->desc.collision != LT_COLLISION_NONE && !mrt && !(tau > 0.0))
     return fail(LT_ERR_INVALID, "relaxation time tau = %g", tau);
-  lt::StepArgs a;
-  memset(&a, 0, sizeof a);
-  a.in = in; a.out = out;
+  lt::StepArgs a = kernel_selector(p, mode);
+  a.in = l.in; a.out = l.out;
   a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2;
   a.p_begin = (int)pb; a.planes = (int)((pe - pb + stride - 1) / stride); a.p_stride = (int)stride;
   a.wrap2 = p->desc.ghost_planes ? 0 : 1;
   a.tau = tau > 0.0 ? tau : 1.0;
-  a.smagorinsky = p->smagorinsky;
-  a.tau_minus = p->tau_minus;
-  a.mrt_transform = p->mrt.transform;
-  std::copy(p->mrt.rates, p->mrt.rates + 27, a.mrt_rates);
-  a.accel[0] = p->force.a[0]; a.accel[1] = p->force.a[1]; a.accel[2] = p->force.a[2];
-  a.ueq_scale = p->force.ueq_scale; a.source_scale = p->force.source_scale;
-  a.rho0 = p->rho0;
+  p->set.fill(a);
   a.node = p->node; a.nsm_bits = p->nsm_bits; a.bt = p->bt; a.nb = p->desc.n_boundaries;
-  a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = mode;
-  a.masked = p->masked;
-  a.abb_depth = p->abb_depth;
-  a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
-  a.n_abb = p->masked ? p->n_abb : 0;
-  a.n_pout = p->masked ? p->n_pout : 0;
-  a.abb0_slot = 0;
-  if (p->masked && p->n_abb == 1 && p->n_pout == 0)
-    for (int i = 0; i < p->desc.n_boundaries; ++i) {
-      const lt_boundary_desc &b = p->desc.boundaries[i];
-      if (b.kind == LT_BOUNDARY_ABB_OUTLET && !(b.flags & LT_BOUNDARY_ABSENT) && mem_axis_of(p, b.axis) == 0)
-        a.abb0_slot = i + 1;
-    }
-  a.tune = resolve_tune(p);
   a.lds_bytes = resolve_lds(p, ((long long)a.planes * a.n1 * a.n0 + 255) / 256);
-  a.seg_len = mode == lt::kFusedTwice ? resolve_seg_len(p, p->unit.d == 2 ? p->n1 : a.planes) : 0;
-  a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
-  if (mode == lt::kFusedTwice) a.shift = p->shift;      // workgroup-order A/B variant
-  if (mode == lt::kFusedMany) a.seg_len = p->many_now;
-  a.stream = static_cast<hipStream_t>(stream);
-  a.stride_in = p->stride_in_now >= 0 ? p->stride_in_now : p->pop_stride;
-  a.stride_out = p->stride_out_now >= 0 ? p->stride_out_now : p->pop_stride;
-  a.pack_lo = pack_lo; a.pack_hi = pack_hi;
-  a.signal = p->signal_now;
-  a.ghost_lo = p->ghost_lo_now; a.ghost_hi = p->ghost_hi_now;
+  if (mode == lt::kFusedTwice) a.seg_len = resolve_seg_len(p, p->unit.d == 2 ? p->n1 : a.planes, l.seg_len);
+  if (mode == lt::kFusedMany) a.seg_len = l.many;
+  a.stream = static_cast<hipStream_t>(l.stream);
+  a.stride_in = l.stride_in >= 0 ? l.stride_in : p->pop_stride;
+  a.stride_out = l.stride_out >= 0 ? l.stride_out : p->pop_stride;
+  a.pack_lo = l.pack_lo; a.pack_hi = l.pack_hi;
+  a.signal = l.signal;
+  a.ghost_lo = l.ghost_lo; a.ghost_hi = l.ghost_hi;
   a.interior_begin = p->interior_begin; a.interior_end = p->interior_end;
   a.pack_lo_plane = (int)pb; a.pack_hi_plane = (int)(pb + stride * (a.planes - 1));
   if (mode == lt::kFusedTwice) {
-    a.p_begin2 = (int)p->second_begin;
-    a.planes2 = (int)(p->second_end - p->second_begin);
-    if (a.planes2 > 0) a.pack_hi_plane = (int)p->second_end - 1;   // upper message: last plane of the second range
+    a.p_begin2 = (int)l.begin2;
+    a.planes2 = (int)(l.end2 - l.begin2);
+    if (a.planes2 > 0) a.pack_hi_plane = (int)l.end2 - 1;   // upper message: last plane of the second range
   }
   const int r = p->unit.step(a);
   if (r == lt::kNoKernel)
@@ -724,12 +741,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
         hipEventCreateWithFlags(&p->gev_out, hipEventDisableTiming) != hipSuccess)
       return -fail(LT_ERR_HIP, "cannot create the graph stream/events");
   }
-  const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.smagorinsky == p->smagorinsky &&
-                    p->gkey.tau_minus == p->tau_minus &&
-                    p->gkey.force == p->force && p->gkey.mrt == p->mrt && p->gkey.equilibrium == p->equilibrium &&
-                    p->gkey.rho0 == p->rho0 &&
-                    p->gkey.masked == p->masked && p->gkey.tune == p->tune && p->gkey.residency == p->residency &&
-                    p->gkey.shift == p->shift;
+  const bool same = p->gexec && p->gkey.a == cur && p->gkey.b == other && p->gkey.tau == tau && p->gkey.set == p->set;
   if (!same) {
     if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
     hipGraph_t graph = nullptr;
@@ -738,7 +750,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     void *c = cur, *o = other;
     int rc = LT_OK;
     for (int i = 0; i < kGraphChunk && rc == LT_OK; ++i) {
-      rc = step(p, lt::kFused, c, o, tau, 0, p->n2, p->gstream);
+      rc = step(p, Launch(lt::kFused, c, o, tau, 0, p->n2, p->gstream));
       void *t = c; c = o; o = t;
     }
     const hipError_t e = hipStreamEndCapture(p->gstream, &graph);
@@ -747,8 +759,7 @@ long long run_graph(lt_plan *p, void *cur, void *other, double tau, long long fu
     const hipError_t ei = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) { p->gexec = nullptr; return -fail(LT_ERR_HIP, "hipGraphInstantiate failed"); }
-    p->gkey = {cur, other, tau, p->smagorinsky, p->tau_minus, p->masked, p->tune, p->shift, p->residency, p->force, p->mrt,
-               p->equilibrium, p->rho0};
+    p->gkey = {cur, other, tau, p->set};
   }
   const long long reps = fused / kGraphChunk;
   if (hipEventRecord(p->gev_in, user) != hipSuccess ||
@@ -781,25 +792,19 @@ bool two_step_possible(lt_plan *p, const char **why) {
   // with masks the whole (padded) field is addressed with 32-bit offsets
   const long long widest = std::max(pop_stride_of(p), p->resident != 0 ? resident_stride(p) : 0ll);
   const bool big = masked_big_exists(p->desc.layout, p->desc.collision, p->unit.q);
-  if (!two_step_addressable(p->unit.d, p->unit.q, p->esize, p->n0, p->n1, p->n2, p->masked != 0, big) ||
-      (p->masked && p->unit.d == 3 && (big ? 1ll : (long long)p->unit.q) * widest * p->esize >= (1ll << 32))) {
-    *why = p->masked ? "with boundaries the two-step kernel addresses with 32-bit offsets: q * nodes * sizeof(scalar) (BGK, "
+  if (!two_step_addressable(p->unit.d, p->unit.q, p->esize, p->n0, p->n1, p->n2, p->set.masked != 0, big) ||
+      (p->set.masked && p->unit.d == 3 && (big ? 1ll : (long long)p->unit.q) * widest * p->esize >= (1ll << 32))) {
+    *why = p->set.masked ? "with boundaries the two-step kernel addresses with 32-bit offsets: q * nodes * sizeof(scalar) (BGK, "
                        "reference layout: nodes * sizeof(scalar)) must stay below 4 GiB"
                      : "a plane of the grid exceeds the two-step kernel's 32-bit in-plane offsets";
     return false;
   }
-  lt::StepArgs a;
-  memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = kernel_coll(p); a.mode = lt::kFusedTwice;
-  a.masked = p->masked;
-  a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
-  a.strip = p->unit.d == 2 ? tile.width : 0;
-  if (!has_kernel(p->unit, a)) {
+  if (!has_kernel(p->unit, kernel_selector(p, lt::kFusedTwice))) {
     *why = "no two-step kernel for this lattice / dtype / collision";
     return false;
   }
   // with boundaries: the kernel is held against two one-step launches once per plan and set of masks (run_canary)
-  if (p->masked && !p->canary_running && !canary_ok(p)) {
+  if (p->set.masked && !canary_ok(p)) {
     *why = p->canary_msg;
     return false;
   }
@@ -814,7 +819,7 @@ bool two_step_never_automatic(const lt_plan *p) {
   if (p->desc.collision == LT_COLLISION_KBC) return true;
   // a body force: never automatic (the forced two-step sweep has not been measured against two one-step launches,
   // DESIGN.md section 7)
-  if (p->force.on) return true;
+  if (p->set.force.on) return true;
   // TRT, regularised: never automatic either, for the same reason
   if (p->desc.collision == LT_COLLISION_TRT || p->desc.collision == LT_COLLISION_REGULARIZED) return true;
   // MRT has no two-step kernel
@@ -877,15 +882,6 @@ void run_canary(lt_plan *p) {
                              "bytes); the plan keeps the one-step kernel", bytes);
     return;
   }
-  // the plan as the caller set it up, but on dense scratch buffers and without the slab drivers' per-launch state
-  const long long s_in = p->stride_in_now, s_out = p->stride_out_now, sb = p->second_begin, se = p->second_end;
-  unsigned long long *const sig = p->signal_now;
-  const void *const glo = p->ghost_lo_now, *const ghi = p->ghost_hi_now;
-  p->stride_in_now = p->stride_out_now = p->N;
-  p->second_begin = p->second_end = 0;
-  p->signal_now = nullptr;
-  p->ghost_lo_now = p->ghost_hi_now = nullptr;
-  p->canary_running = 1;
   char saved_error[sizeof g_error];
   memcpy(saved_error, g_error, sizeof g_error);
   const double tau = 0.8;
@@ -893,9 +889,17 @@ void run_canary(lt_plan *p) {
   hipLaunchKernelGGL((canary_fill_kernel<T>), dim3(1024), dim3(256), 0, p->cstream, (T *)buf[0], p->N, p->N, p->unit.q);
   if (g) for (int i = 1; i < 4; ++i) (void)hipMemsetAsync(buf[i], 0, bytes, p->cstream);   // planes a slab launch never writes
   (void)hipMemsetAsync(count, 0, sizeof *count, p->cstream);
-  int rc = step(p, lt::kFused, buf[0], buf[1], tau, b1, e1, p->cstream);
-  if (rc == LT_OK) rc = step(p, lt::kFused, buf[1], buf[2], tau, b2, e2, p->cstream);
-  if (rc == LT_OK) rc = step(p, lt::kFusedTwice, buf[0], buf[3], tau, b2, e2, p->cstream);
+  // the plan as the caller set it up -- masks, boundary table, tile, its own segment length -- on dense scratch buffers;
+  // whichever entry point came first, these are the three launches
+  const auto check_launch = [&](int mode, int from, int to, long long begin, long long end) {
+    Launch l(mode, buf[from], buf[to], tau, begin, end, p->cstream);
+    l.stride_in = l.stride_out = p->N;
+    l.canary = true;
+    return step(p, l);
+  };
+  int rc = check_launch(lt::kFused, 0, 1, b1, e1);
+  if (rc == LT_OK) rc = check_launch(lt::kFused, 1, 2, b2, e2);
+  if (rc == LT_OK) rc = check_launch(lt::kFusedTwice, 0, 3, b2, e2);
   unsigned long long bad = 0;
   hipError_t e = hipSuccess;
   if (rc == LT_OK) {
@@ -907,11 +911,6 @@ void run_canary(lt_plan *p) {
   }
   const hipError_t es = hipStreamSynchronize(p->cstream);
   if (e == hipSuccess) e = es;
-  p->canary_running = 0;
-  p->stride_in_now = s_in; p->stride_out_now = s_out;
-  p->second_begin = sb; p->second_end = se;
-  p->signal_now = sig;
-  p->ghost_lo_now = glo; p->ghost_hi_now = ghi;
   release();
   if (rc != LT_OK) {
     char why[sizeof g_error];
@@ -933,7 +932,7 @@ void run_canary(lt_plan *p) {
 
 // may this plan's masked two-step kernel be used?  Runs the check if it has not been run for the present masks
 bool canary_ok(lt_plan *p) {
-  if (!p->masked) return true;
+  if (!p->set.masked) return true;
   if (p->canary == 0) {
     if (p->canary_mode == 0) canary_verdict(p, 2, 0, "");
     else if (p->canary_mode == 2)
@@ -948,7 +947,7 @@ bool canary_ok(lt_plan *p) {
 constexpr int kManyMax = 8;        // == kManyMax of unit.inc
 // steps per many-step launch: a plan with an outlet recomputes one more ring of nodes around each tile.  3-D plans
 // have no many-step kernel (lt_stream_collide_many: LT_ERR_UNSUPPORTED); their range stays the removed kernel's two
-int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->masked && p->n_abb > 0) ? 1 : 0); }
+int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->set.masked && p->n_abb > 0) ? 1 : 0); }
 
 // Several steps per launch (lbm_many_kernel): 2-D, tiles of 8 x 8, with masks at most one outlet.  Every
 // workgroup recomputes a halo of K - 1 nodes around its tile (K with an outlet), so this only pays while the
@@ -962,13 +961,9 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->mas
 // 12^3 neighbourhood: 131 KB for D3Q19 fp32 and 3.4 x the arithmetic).
 bool many_step_wanted(lt_plan *p) {
   if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || multi_step_refusal(p, lt::kFusedMany) != nullptr) return false;
-  if (p->masked && p->n_abb > 1) return false;
+  if (p->set.masked && p->n_abb > 1) return false;
   if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
-  lt::StepArgs a;
-  memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = p->desc.collision; a.mode = lt::kFusedMany;
-  a.masked = p->masked;
-  if (!has_kernel(p->unit, a)) return false;
+  if (!has_kernel(p->unit, kernel_selector(p, lt::kFusedMany))) return false;
   if (p->many == 1) return true;
   // automatic only where the many-step kernel is bit-identical to the one-step kernel, so that the
   // result of n steps does not depend on how the caller splits them into batches (KBC agrees at
@@ -977,17 +972,26 @@ bool many_step_wanted(lt_plan *p) {
   // with masks the launch is bound by its own latency chain (node byte, boundary values, a barrier per step) and
   // recomputes a wider ring: 128 x 64 nodes 4.2 -> 2.4 us per step, 128 x 128 4.3 -> 2.5, 256 x 128 4.5 -> 3.3,
   // 256 x 256 5.6 -> 5.7 (tools/small_masked_bench.py, fp64)
-  if (p->masked) return p->N <= 256ll * 128ll;
+  if (p->set.masked) return p->N <= 256ll * 128ll;
   return p->N <= 256ll * 256ll;
 }
 
 // `fused` stream-collide steps starting from the post-collision populations in *cur, ping-ponging with *other (both
 // pointers are updated: on return *cur holds the result): pairs of steps through the two-step kernel where it
 // applies, the rest one by one; several steps per launch on small 2-D grids.  The optional events bracket the
-// dominant kind of launch only.
-int fused_section(lt_plan *p, void *&cur, void *&other, double tau, long long fused, void *stream) {
+// dominant kind of launch only.  `stride`: elements between consecutive populations of the two buffers, negative for the
+// caller's own (the plan's pop_stride), which alone may go through a captured graph.
+int fused_section(lt_plan *p, void *&cur, void *&other, double tau, long long fused, void *stream, long long stride = -1) {
   int rc;
-  if (graph_wanted(p, fused) && p->stride_in_now < 0) {
+  const auto advance = [&](int mode, int many = 1) {
+    Launch l(mode, cur, other, tau, 0, p->n2, stream);
+    l.many = many;
+    l.stride_in = l.stride_out = stride;
+    const int status = step(p, l);
+    if (status == LT_OK) std::swap(cur, other);
+    return status;
+  };
+  if (graph_wanted(p, fused) && stride < 0) {
     const long long done = run_graph(p, cur, other, tau, fused, stream);
     if (done < 0) return (int)-done;
     fused -= done;                       // an even number of steps: still in `cur`
@@ -998,11 +1002,10 @@ int fused_section(lt_plan *p, void *&cur, void *&other, double tau, long long fu
     // launches of up to kManyMax steps each; the events bracket them
     if (p->ev_start) (void)hipEventRecord(p->ev_start, hs);
     while (fused > 0) {
-      p->many_now = fused < many_max(p) ? (int)fused : many_max(p);
-      rc = step(p, lt::kFusedMany, cur, other, tau, 0, p->n2, stream);
+      const int steps = fused < many_max(p) ? (int)fused : many_max(p);
+      rc = advance(lt::kFusedMany, steps);
       if (rc) return rc;
-      void *t = cur; cur = other; other = t;
-      fused -= p->many_now;
+      fused -= steps;
       ++p->last_many;
     }
     if (p->ev_stop) (void)hipEventRecord(p->ev_stop, hs);
@@ -1015,16 +1018,14 @@ int fused_section(lt_plan *p, void *&cur, void *&other, double tau, long long fu
   p->last_twice = twice; p->last_single = single;
   if (p->ev_start && twice > 0) (void)hipEventRecord(p->ev_start, hs);
   for (long long i = 0; i < twice; ++i) {
-    rc = step(p, lt::kFusedTwice, cur, other, tau, 0, p->n2, stream);
+    rc = advance(lt::kFusedTwice);
     if (rc) return rc;
-    void *t = cur; cur = other; other = t;
   }
   if (p->ev_stop && twice > 0) (void)hipEventRecord(p->ev_stop, hs);
   if (p->ev_start && twice == 0) (void)hipEventRecord(p->ev_start, hs);
   for (long long i = 0; i < single; ++i) {
-    rc = step(p, lt::kFused, cur, other, tau, 0, p->n2, stream);
+    rc = advance(lt::kFused);
     if (rc) return rc;
-    void *t = cur; cur = other; other = t;
   }
   if (p->ev_stop && twice == 0) (void)hipEventRecord(p->ev_stop, hs);
   return LT_OK;
@@ -1042,7 +1043,7 @@ int run(lt_plan *p, bool from_fstar, void *a, void *b, double tau, long long n, 
   int rc;
   long long fused = n;
   if (!from_fstar) {
-    rc = step(p, lt::kCollideOnly, cur, other, tau, 0, p->n2, stream);
+    rc = step(p, Launch(lt::kCollideOnly, cur, other, tau, 0, p->n2, stream));
     if (rc) return rc;
     void *t = cur; cur = other; other = t;
     fused = n - 1;
@@ -1053,7 +1054,7 @@ int run(lt_plan *p, bool from_fstar, void *a, void *b, double tau, long long n, 
     *result_in_b = (cur == b) ? 1 : 0;
     return LT_OK;
   }
-  rc = step(p, lt::kStreamOnly, cur, other, tau, 0, p->n2, stream);
+  rc = step(p, Launch(lt::kStreamOnly, cur, other, tau, 0, p->n2, stream));
   if (rc) return rc;
   *result_in_b = (other == b) ? 1 : 0;
   return LT_OK;
@@ -1080,7 +1081,7 @@ int aux(lt_plan *p, int what, const void *f, void *rho, void *u, double *out, vo
   a.partial = p->partial; a.reduce_blocks = kReduceBlocks; a.out = out;
   a.n0 = p->n0; a.n1 = p->n1; a.n2 = what == 8 ? (p->interior_end - p->interior_begin) + 6 : p->n2;
   a.scale = scale; a.inv_dx = inv_dx; a.mask = mask;
-  a.equilibrium = p->equilibrium; a.rho0 = p->rho0;
+  a.equilibrium = p->set.equilibrium; a.rho0 = p->set.rho0;
   a.stream = static_cast<hipStream_t>(stream);
   const int r = p->unit.aux(a);
   if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no auxiliary kernel %d", what);
@@ -1119,14 +1120,32 @@ MaskCheck mask_check_of(const lt_plan *p) {
   return c;
 }
 
-// reads the mismatch bits of a compile / recheck launch on `hs` into the plan's admission flags
-int store_admission(lt_plan *p, hipStream_t hs) {
+// Decides the admission of the masked two-step kernels: one launch of a mask kernel over all nodes on `hs`
+// (compile_masks_kernel or recheck_masks_kernel; `lead`: its arguments in front of the MaskCheck's), whose mismatch
+// bits become the plan's admission flags
+template <class Kernel, class... Lead>
+int decide_admission(lt_plan *p, hipStream_t hs, Kernel kernel, Lead... lead) {
+  LT_HIP(hipMemsetAsync(p->mask_flag, 0, sizeof(unsigned), hs));
+  const MaskCheck c = mask_check_of(p);
+  const unsigned grid = (unsigned)((p->N + lt::kThreads - 1) / lt::kThreads);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(lt::kThreads), 0, hs, lead..., c.plane_nodes, p->n0, c.axis, c.plane,
+                     c.expected, c.face, c.eq_slots, p->mask_flag);
+  LT_HIP(hipGetLastError());
   unsigned flags = 0;
   LT_HIP(hipMemcpyAsync(&flags, p->mask_flag, sizeof flags, hipMemcpyDeviceToHost, hs));
   LT_HIP(hipStreamSynchronize(hs));
   p->nsm_confined = (flags & 1u) == 0;
   p->inlet_faces_outlet = (flags & 2u) == 0;
   return LT_OK;
+}
+
+// memory extents of a descriptor's grid, a0 the contiguous one, a slab's ghost planes included (of a `dims`-dimensional unit)
+struct Extents { long long e0, e1, e2; };
+Extents extents_of(const lt_plan_desc &d, int dims) {
+  if (dims == 1) return {d.shape[0], 1, 1};
+  if (dims == 2) return {d.shape[1], d.shape[0], 1};
+  if (d.layout == LT_LAYOUT_REFERENCE) return {d.shape[2], d.shape[1], d.shape[0]};
+  return {d.shape[0], d.shape[1], d.shape[2] + 2 * d.ghost_planes};
 }
 
 // the outlets' axes decide how deep an outlet's neighbour must be rebuilt (see lt_plan_create); -1: unsupported
@@ -1184,11 +1203,7 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   p->desc = *d;
   p->unit = unit;
   p->esize = d->dtype == LT_F32 ? 4 : 8;
-  long long e0, e1, e2;
-  if (unit.d == 1) { e0 = d->shape[0]; e1 = 1; e2 = 1; }
-  else if (unit.d == 2) { e0 = d->shape[1]; e1 = d->shape[0]; e2 = 1; }
-  else if (d->layout == LT_LAYOUT_REFERENCE) { e0 = d->shape[2]; e1 = d->shape[1]; e2 = d->shape[0]; }
-  else { e0 = d->shape[0]; e1 = d->shape[1]; e2 = d->shape[2] + 2 * d->ghost_planes; }
+  const auto [e0, e1, e2] = extents_of(*d, unit.d);
   if (e0 * e1 * e2 >= (1ll << 31)) {
     delete p;
     return fail(LT_ERR_UNSUPPORTED, "%lld nodes per rank exceed the 2^31 index range", e0 * e1 * e2);
@@ -1197,7 +1212,6 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   p->N = e0 * e1 * e2;
   p->interior_begin = d->ghost_planes;
   p->interior_end = p->n2 - d->ghost_planes;
-  p->shift = 0;
   {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -1206,7 +1220,7 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
   }
   int n_abb = 0;
   for (int i = 0; i < d->n_boundaries; ++i) {
-    const int rc = check_boundary(p, d->boundaries[i], n_abb);
+    const int rc = check_boundary(p, d->boundaries[i]);
     if (rc) { delete p; return rc; }
     if (d->boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET) ++n_abb;
     if (d->boundaries[i].kind == LT_BOUNDARY_PRESSURE_OUTLET) ++p->n_pout;
@@ -1263,27 +1277,21 @@ int lt_plan_set_masks(lt_plan *p, const uint8_t *ncm, const uint8_t *nsm, void *
   if (!ncm && !nsm) {
     if (p->desc.n_boundaries > 0)
       return fail(LT_ERR_INVALID, "a plan with boundaries needs a no_collision_mask");
-    p->masked = 0;
+    p->set.masked = 0;
     return LT_OK;
   }
   if (!p->node) LT_HIP(hipMalloc((void **)&p->node, (size_t)p->N));
   if (nsm && !p->nsm_bits) LT_HIP(hipMalloc((void **)&p->nsm_bits, (size_t)p->N * sizeof(unsigned)));
   if (!p->mask_flag) LT_HIP(hipMalloc((void **)&p->mask_flag, sizeof(unsigned)));
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  LT_HIP(hipMemsetAsync(p->mask_flag, 0, sizeof(unsigned), hs));
-  const MaskCheck c = mask_check_of(p);
-  const unsigned grid = (unsigned)((p->N + lt::kThreads - 1) / lt::kThreads);
-  hipLaunchKernelGGL(lt::compile_masks_kernel, dim3(grid), dim3(lt::kThreads), 0, hs, ncm, nsm, p->unit.q, p->N,
-                     p->node, nsm ? p->nsm_bits : nullptr, c.plane_nodes, p->n0, c.axis, c.plane, c.expected,
-                     c.face, c.eq_slots, p->mask_flag);
-  LT_HIP(hipGetLastError());
-  const int rc = store_admission(p, hs);
+  const int rc = decide_admission(p, hs, lt::compile_masks_kernel, ncm, nsm, p->unit.q, p->N, p->node,
+                                  nsm ? p->nsm_bits : nullptr);
   if (rc) return rc;
   if (p->gexec) {                                    // captured with the mask pointers of its time (nsm_bits may be new)
     (void)hipGraphExecDestroy(p->gexec);
     p->gexec = nullptr;
   }
-  p->masked = 1;
+  p->set.masked = 1;
   p->canary = 0;                                     // new masks: the first-use check runs again
   return LT_OK;
 }
@@ -1295,7 +1303,7 @@ int lt_plan_update_boundary(lt_plan *p, int32_t index, const lt_boundary_desc *b
   if (b->kind != old.kind)
     return fail(LT_ERR_INVALID, "boundary %d: kind cannot change (%d -> %d)", index, old.kind, b->kind);
   // what lt_plan_create would refuse is refused here too, and leaves the plan as it was
-  int rc = check_boundary(p, *b, 0);
+  int rc = check_boundary(p, *b);
   if (rc) return rc;
   p->desc.boundaries[index] = *b;
   const int depth = abb_depth_of(p->desc);
@@ -1322,44 +1330,40 @@ int lt_plan_update_boundary(lt_plan *p, int32_t index, const lt_boundary_desc *b
     (void)hipGraphExecDestroy(p->gexec);
     p->gexec = nullptr;
   }
-  if (moved && p->masked) {
+  if (moved && p->set.masked) {
     // the admission of the masked two-step kernels was decided for the old outlet: decide it again on the compiled
     // masks (node bytes and no-streaming bits as lt_plan_set_masks left them) for the new one
-    LT_HIP(hipMemsetAsync(p->mask_flag, 0, sizeof(unsigned), hs));
-    const MaskCheck c = mask_check_of(p);
-    const unsigned grid = (unsigned)((p->N + lt::kThreads - 1) / lt::kThreads);
-    hipLaunchKernelGGL(lt::recheck_masks_kernel, dim3(grid), dim3(lt::kThreads), 0, hs, p->node, p->nsm_bits, p->N,
-                       c.plane_nodes, p->n0, c.axis, c.plane, c.expected, c.face, c.eq_slots, p->mask_flag);
-    LT_HIP(hipGetLastError());
-    return store_admission(p, hs);
+    return decide_admission(p, hs, lt::recheck_masks_kernel, p->node, p->nsm_bits, p->N);
   }
   return LT_OK;
 }
 
 int lt_collide(lt_plan *p, const void *f, void *o, double tau, void *s) {
-  return step(p, lt::kCollideOnly, f, o, tau, p ? p->interior_begin : 0, p ? p->interior_end : 0, s);
+  return step(p, Launch(lt::kCollideOnly, f, o, tau, p ? p->interior_begin : 0, p ? p->interior_end : 0, s));
 }
 int lt_stream(lt_plan *p, const void *f, void *o, void *s) {
-  return step(p, lt::kStreamOnly, f, o, 1.0, p ? p->interior_begin : 0, p ? p->interior_end : 0, s);
+  return step(p, Launch(lt::kStreamOnly, f, o, 1.0, p ? p->interior_begin : 0, p ? p->interior_end : 0, s));
 }
 int lt_stream_collide(lt_plan *p, const void *f, void *o, double tau, void *s) {
-  return step(p, lt::kFused, f, o, tau, p ? p->interior_begin : 0, p ? p->interior_end : 0, s);
+  return step(p, Launch(lt::kFused, f, o, tau, p ? p->interior_begin : 0, p ? p->interior_end : 0, s));
 }
 int lt_collide_planes(lt_plan *p, const void *f, void *o, double tau, int64_t b, int64_t e, void *s) {
-  return step(p, lt::kCollideOnly, f, o, tau, b, e, s);
+  return step(p, Launch(lt::kCollideOnly, f, o, tau, b, e, s));
 }
 int lt_stream_planes(lt_plan *p, const void *f, void *o, int64_t b, int64_t e, void *s) {
-  return step(p, lt::kStreamOnly, f, o, 1.0, b, e, s);
+  return step(p, Launch(lt::kStreamOnly, f, o, 1.0, b, e, s));
 }
 int lt_stream_collide_planes(lt_plan *p, const void *f, void *o, double tau, int64_t b, int64_t e,
                              void *s) {
-  return step(p, lt::kFused, f, o, tau, b, e, s);
+  return step(p, Launch(lt::kFused, f, o, tau, b, e, s));
 }
 
 int lt_stream_collide_plane_pair(lt_plan *p, const void *f, void *o, double tau, int64_t first,
                                  int64_t second, void *s) {
   if (second <= first) return fail(LT_ERR_INVALID, "plane pair (%lld, %lld)", (long long)first, (long long)second);
-  return step(p, lt::kFused, f, o, tau, first, second + 1, s, second - first);
+  Launch l(lt::kFused, f, o, tau, first, second + 1, s);
+  l.stride = second - first;
+  return step(p, l);
 }
 
 int lt_stream_collide_plane_pair_packed(lt_plan *p, const void *f, void *o, double tau,
@@ -1369,8 +1373,10 @@ int lt_stream_collide_plane_pair_packed(lt_plan *p, const void *f, void *o, doub
   if (second < first) return fail(LT_ERR_INVALID, "plane pair (%lld, %lld)", (long long)first, (long long)second);
   if (!pack_first || !pack_second) return fail(LT_ERR_INVALID, "null pack buffer");
   if (p->desc.layout != LT_LAYOUT_SLAB) return fail(LT_ERR_UNSUPPORTED, "fused packing needs the slab layout");
-  const long long stride = second > first ? second - first : 1;
-  return step(p, lt::kFused, f, o, tau, first, second + 1, s, stride, pack_first, pack_second);
+  Launch l(lt::kFused, f, o, tau, first, second + 1, s);
+  l.stride = second > first ? second - first : 1;
+  l.pack_lo = pack_first; l.pack_hi = pack_second;
+  return step(p, l);
 }
 
 int lt_run(lt_plan *p, void *a, void *b, double tau, int64_t n, void *s, int32_t *r) {
@@ -1497,21 +1503,12 @@ int lt_plan_kernel_info(lt_plan *p, int32_t *vec, int32_t *tpb, int64_t *blocks)
 
 const char *lt_plan_kernel_name(lt_plan *p) {
   if (!p) return "";
-  lt::StepArgs a;
-  memset(&a, 0, sizeof a);
-  a.layout = p->desc.layout; a.coll = kernel_coll(p);
   // what the fused section launches: lt_run's pairs, or a two-step slab driver on a plan with two
   // ghost planes
-  a.mode = (two_step_wanted(p) || p->desc.ghost_planes == 2) ? lt::kFusedTwice : lt::kFused;
-  if (many_step_wanted(p)) a.mode = lt::kFusedMany;
-  a.masked = p->masked;
-  a.abb_depth = p->abb_depth;
-  a.n_pout = p->masked ? p->n_pout : 0;
-  a.abb_axis = p->masked ? masked_two_step_axis(p) : 2;
-  a.strip = p->unit.d == 2 ? two_step_tile(p).width : 0;
-  a.shift = p->shift;
-  if (a.mode == lt::kFusedTwice && !has_kernel(p->unit, a)) a.mode = lt::kFused;
-  a.tune = resolve_tune(p);
+  int mode = (two_step_wanted(p) || p->desc.ghost_planes == 2) ? lt::kFusedTwice : lt::kFused;
+  if (many_step_wanted(p)) mode = lt::kFusedMany;
+  if (mode == lt::kFusedTwice && !has_kernel(p->unit, kernel_selector(p, mode))) mode = lt::kFused;
+  const lt::StepArgs a = kernel_selector(p, mode);
   if (!p->unit.name(a, lt::NameBuf{p->kernel_name, sizeof p->kernel_name})) p->kernel_name[0] = 0;
   return p->kernel_name;
 }
@@ -1569,8 +1566,8 @@ int lt_plan_set_shift_policy(lt_plan *p, int32_t policy) {
   if (policy < 0 || policy > 6) return fail(LT_ERR_INVALID, "shift policy %d", policy);
   if (policy == 1 || policy == 2 || policy == 5)
     return fail(LT_ERR_UNSUPPORTED, "shift policy %d: its tile variant lost its A/B and was removed", policy);
-  if (p->shift != policy) p->canary = 0;
-  p->shift = policy;
+  if (p->set.shift != policy) p->canary = 0;
+  p->set.shift = policy;
   return LT_OK;
 }
 
@@ -1619,9 +1616,9 @@ int lt_resident_load(lt_plan *p, const void *f, double tau, void *stream) {
   int rc = resident_alloc(p);
   if (rc) return rc;
   p->res_valid = 0;
-  p->stride_in_now = pop_stride_of(p); p->stride_out_now = p->res_stride;
-  rc = step(p, lt::kCollideOnly, f, p->res[0], tau, 0, p->n2, stream);
-  p->stride_in_now = p->stride_out_now = -1;
+  Launch l(lt::kCollideOnly, f, p->res[0], tau, 0, p->n2, stream);
+  l.stride_out = p->res_stride;
+  rc = step(p, l);
   if (rc) return rc;
   p->res_cur = 0;
   p->res_valid = 1;
@@ -1634,9 +1631,7 @@ int lt_resident_advance(lt_plan *p, double tau, int64_t n, void *stream) {
   p->last_single = p->last_twice = p->last_many = 0;
   if (n == 0) return LT_OK;
   void *cur = p->res[p->res_cur], *other = p->res[1 - p->res_cur];
-  p->stride_in_now = p->stride_out_now = p->res_stride;
-  const int rc = fused_section(p, cur, other, tau, n, stream);
-  p->stride_in_now = p->stride_out_now = -1;
+  const int rc = fused_section(p, cur, other, tau, n, stream, p->res_stride);
   if (rc) { p->res_valid = 0; return rc; }
   p->res_cur = cur == p->res[0] ? 0 : 1;
   return LT_OK;
@@ -1644,10 +1639,9 @@ int lt_resident_advance(lt_plan *p, double tau, int64_t n, void *stream) {
 int lt_resident_store(lt_plan *p, void *out, void *stream) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (!p->res_valid) return fail(LT_ERR_INVALID, "no resident populations: call lt_resident_load first");
-  p->stride_in_now = p->res_stride; p->stride_out_now = pop_stride_of(p);
-  const int rc = step(p, lt::kStreamOnly, p->res[p->res_cur], out, 1.0, 0, p->n2, stream);
-  p->stride_in_now = p->stride_out_now = -1;
-  return rc;
+  Launch l(lt::kStreamOnly, p->res[p->res_cur], out, 1.0, 0, p->n2, stream);
+  l.stride_in = p->res_stride;
+  return step(p, l);
 }
 int lt_resident_free(lt_plan *p) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
@@ -1667,12 +1661,12 @@ int lt_plan_set_graph_mode(lt_plan *p, int32_t mode) {
 int lt_stream_collide_twice(lt_plan *p, const void *f, void *out, double tau, void *stream) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   const int g = p->desc.ghost_planes;
-  return step(p, lt::kFusedTwice, f, out, tau, g, p->n2 - g, stream);
+  return step(p, Launch(lt::kFusedTwice, f, out, tau, g, p->n2 - g, stream));
 }
 int lt_stream_collide_twice_planes(lt_plan *p, const void *f, void *out, double tau, int64_t begin,
                                    int64_t end, void *stream) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
-  return step(p, lt::kFusedTwice, f, out, tau, begin, end, stream);
+  return step(p, Launch(lt::kFusedTwice, f, out, tau, begin, end, stream));
 }
 int lt_stream_collide_twice_planes_packed(lt_plan *p, const void *f, void *out, double tau, int64_t begin,
                                           int64_t end, void *pack_lower, void *pack_upper, void *stream) {
@@ -1685,24 +1679,34 @@ int lt_stream_collide_twice_planes_packed(lt_plan *p, const void *f, void *out, 
     return fail(LT_ERR_INVALID, "lower message: the range must start at the first interior plane");
   if (pack_upper && end != p->n2 - 2)
     return fail(LT_ERR_INVALID, "upper message: the range must end at the last interior plane");
-  return step(p, lt::kFusedTwice, f, out, tau, begin, end, stream, 1, pack_lower, pack_upper);
+  Launch l(lt::kFusedTwice, f, out, tau, begin, end, stream);
+  l.pack_lo = pack_lower; l.pack_hi = pack_upper;
+  return step(p, l);
 }
-int lt_stream_collide_twice_edges(lt_plan *p, const void *f, void *out, double tau, int32_t edge_planes,
-                                  void *pack_lower, void *pack_upper, void *stream) {
-  if (!p) return fail(LT_ERR_INVALID, "null plan");
+namespace {
+// both edges of a slab in one launch, edge_planes each (one segment per range and tile); recv_*: the received halo
+// messages to read the planes beyond the cuts from, or null: the ghost planes of f
+int twice_edges(lt_plan *p, const void *f, void *out, double tau, int32_t edge_planes, const void *recv_lower,
+                const void *recv_upper, void *pack_lower, void *pack_upper, void *stream) {
   if (p->desc.ghost_planes != 2) return fail(LT_ERR_INVALID, "edge launch needs ghost_planes = 2");
   const long long lo = 2, hi = p->n2 - 2;
   if (edge_planes < 2 || 2ll * edge_planes > hi - lo)
     return fail(LT_ERR_INVALID, "edge_planes = %d (2 .. %lld)", edge_planes, (hi - lo) / 2);
   if ((pack_lower == nullptr) != (pack_upper == nullptr))
     return fail(LT_ERR_INVALID, "give both message buffers or neither");
-  p->second_begin = hi - edge_planes; p->second_end = hi;
-  const int saved = p->seg_len;
-  p->seg_len = edge_planes;                       // one segment per range and tile
-  const int rc = step(p, lt::kFusedTwice, f, out, tau, lo, lo + edge_planes, stream, 1, pack_lower, pack_upper);
-  p->seg_len = saved;
-  p->second_begin = p->second_end = 0;
-  return rc;
+  Launch l(lt::kFusedTwice, f, out, tau, lo, lo + edge_planes, stream);
+  l.begin2 = hi - edge_planes; l.end2 = hi;
+  l.seg_len = edge_planes;
+  l.pack_lo = pack_lower; l.pack_hi = pack_upper;
+  l.ghost_lo = recv_lower; l.ghost_hi = recv_upper;
+  return step(p, l);
+}
+}  // namespace
+
+int lt_stream_collide_twice_edges(lt_plan *p, const void *f, void *out, double tau, int32_t edge_planes,
+                                  void *pack_lower, void *pack_upper, void *stream) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  return twice_edges(p, f, out, tau, edge_planes, nullptr, nullptr, pack_lower, pack_upper, stream);
 }
 int lt_stream_collide_twice_edges_direct(lt_plan *p, const void *f, void *out, double tau, int32_t edge_planes,
                                          const void *recv_lower, const void *recv_upper, void *pack_lower,
@@ -1711,17 +1715,14 @@ int lt_stream_collide_twice_edges_direct(lt_plan *p, const void *f, void *out, d
   if (!pack_lower || !pack_upper || (recv_lower == nullptr) != (recv_upper == nullptr))
     return fail(LT_ERR_INVALID, "the direct edge launch needs both send buffers, and both received messages or "
                                 "neither (then the ghost planes of f_dev are read)");
-  if (p->masked) return fail(LT_ERR_UNSUPPORTED, "the direct edge launch exists for plans without masks");
-  p->ghost_lo_now = recv_lower; p->ghost_hi_now = recv_upper;
-  const int rc = lt_stream_collide_twice_edges(p, f, out, tau, edge_planes, pack_lower, pack_upper, stream);
-  p->ghost_lo_now = p->ghost_hi_now = nullptr;
-  return rc;
+  if (p->set.masked) return fail(LT_ERR_UNSUPPORTED, "the direct edge launch exists for plans without masks");
+  return twice_edges(p, f, out, tau, edge_planes, recv_lower, recv_upper, pack_lower, pack_upper, stream);
 }
 // The whole slab in one launch that feeds the exchange while it runs: see include/lettuce_hip.h
 int lt_stream_collide_twice_slab(lt_plan *p, const void *f, void *out, double tau, void *stream) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (p->desc.ghost_planes != 2) return fail(LT_ERR_INVALID, "the two-step slab launch needs ghost_planes = 2");
-  if (p->masked) return fail(LT_ERR_UNSUPPORTED, "the signalling slab launch exists for plans without masks");
+  if (p->set.masked) return fail(LT_ERR_UNSUPPORTED, "the signalling slab launch exists for plans without masks");
   const long long lo = 2, hi = p->n2 - 2;
   if (hi - lo < 4) return fail(LT_ERR_INVALID, "the slab needs at least 4 interior planes");
   hipStream_t hs = static_cast<hipStream_t>(stream);
@@ -1739,18 +1740,11 @@ int lt_stream_collide_twice_slab(lt_plan *p, const void *f, void *out, double ta
     return fail(LT_ERR_UNSUPPORTED, "two steps per launch: the grid does not tile");
   // upper edge = second range [hi - 2, hi): one short segment; first range [lo, hi - 2) in segments of at least
   // two planes
-  p->second_begin = hi - 2; p->second_end = hi;
-  const int saved = p->seg_len;
-  if (p->seg_len == 1) p->seg_len = 2;
-  if (p->seg_len == 0) {
-    const int len = resolve_seg_len(p, (int)(hi - 2 - lo));
-    p->seg_len = len < 2 ? 2 : len;
-  }
-  p->signal_now = p->signal;
-  const int rc = step(p, lt::kFusedTwice, f, out, tau, lo, hi - 2, stream);
-  p->signal_now = nullptr;
-  p->seg_len = saved;
-  p->second_begin = p->second_end = 0;
+  Launch l(lt::kFusedTwice, f, out, tau, lo, hi - 2, stream);
+  l.begin2 = hi - 2; l.end2 = hi;
+  l.seg_len = std::max(2, resolve_seg_len(p, (int)(hi - 2 - lo)));
+  l.signal = p->signal;
+  const int rc = step(p, l);
   if (rc == LT_OK) p->signal_target += 2ull * (unsigned long long)((p->n0 / tile.width) * (p->n1 / tile.rows));
   return rc;
 }
@@ -1790,11 +1784,7 @@ int lt_two_step_limits(const lt_plan_desc *d, int32_t masked, int32_t *tile_widt
   const Unit &unit = kUnits[2 * d->stencil + d->dtype];
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   const int esize = d->dtype == LT_F32 ? 4 : 8;
-  long long e0, e1, e2;
-  if (unit.d == 1) { e0 = d->shape[0]; e1 = 1; e2 = 1; }
-  else if (unit.d == 2) { e0 = d->shape[1]; e1 = d->shape[0]; e2 = 1; }
-  else if (d->layout == LT_LAYOUT_REFERENCE) { e0 = d->shape[2]; e1 = d->shape[1]; e2 = d->shape[0]; }
-  else { e0 = d->shape[0]; e1 = d->shape[1]; e2 = d->shape[2] + 2 * d->ghost_planes; }
+  const auto [e0, e1, e2] = extents_of(*d, unit.d);
   const TwoStepTile tile = unit.d >= 2 ? two_step_tile_of(unit.d, unit.q, esize, (int)e0, masked != 0) : TwoStepTile{0, 0};
   if (tile_width) *tile_width = tile.width;
   if (tile_rows) *tile_rows = tile.rows;
@@ -1805,7 +1795,7 @@ int lt_two_step_limits(const lt_plan_desc *d, int32_t masked, int32_t *tile_widt
 }
 int lt_slab_two_step_message_blocks(lt_plan *p, int32_t *blocks) {
   if (!p || !blocks) return fail(LT_ERR_INVALID, "null argument");
-  *blocks = crossing(p, 0).n + (p->masked ? 3 : 2) * crossing(p, 1).n;
+  *blocks = crossing(p, 0).n + (p->set.masked ? 3 : 2) * crossing(p, 1).n;
   return LT_OK;
 }
 int lt_slab_pack_two_step(lt_plan *p, const void *f, int32_t side, void *buf, void *s) {
@@ -1837,14 +1827,15 @@ int lt_stream_collide_many(lt_plan *p, const void *f, void *out, double tau, int
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (n_steps < 1 || n_steps > many_max(p))
     return fail(LT_ERR_INVALID, "n_steps = %d (1..%d per launch for this plan)", n_steps, many_max(p));
-  p->many_now = n_steps;
-  return step(p, lt::kFusedMany, f, out, tau, 0, p->n2, stream);
+  Launch l(lt::kFusedMany, f, out, tau, 0, p->n2, stream);
+  l.many = n_steps;
+  return step(p, l);
 }
 
 int lt_plan_set_many_step(lt_plan *p, int32_t mode) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "many-step mode %d", mode);
-  if (mode == 1 && p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
+  if (mode == 1 && p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: %s", kIncompressibleMultiStep);
   p->many = mode;
   return LT_OK;
@@ -1856,7 +1847,7 @@ int lt_plan_set_smagorinsky(lt_plan *p, double constant) {
     return fail(LT_ERR_INVALID, "the plan's collision is %d, not Smagorinsky", p->desc.collision);
   if (!(constant >= 0.0) || !std::isfinite(constant))
     return fail(LT_ERR_INVALID, "Smagorinsky constant %g (finite and >= 0)", constant);
-  p->smagorinsky = constant;
+  p->set.smagorinsky = constant;
   return LT_OK;
 }
 
@@ -1866,7 +1857,7 @@ int lt_plan_set_trt(lt_plan *p, double tau_minus) {
     return fail(LT_ERR_INVALID, "the plan's collision is %d, not TRT", p->desc.collision);
   if (!(tau_minus > 0.0) || !std::isfinite(tau_minus))
     return fail(LT_ERR_INVALID, "TRT relaxation time tau_minus = %g (finite and > 0)", tau_minus);
-  p->tau_minus = tau_minus;
+  p->set.tau_minus = tau_minus;
   return LT_OK;
 }
 
@@ -1885,9 +1876,9 @@ int lt_plan_set_mrt(lt_plan *p, int transform, const double *relaxation, int cou
   for (int i = 0; i < count; ++i)
     if (!(relaxation[i] > 0.0) || !std::isfinite(relaxation[i]))
       return fail(LT_ERR_INVALID, "MRT relaxation rate %d = %g (finite and > 0)", i, relaxation[i]);
-  p->mrt.transform = transform;
-  std::fill(p->mrt.rates, p->mrt.rates + 27, 0.0);
-  std::copy(relaxation, relaxation + count, p->mrt.rates);
+  p->set.mrt.transform = transform;
+  std::fill(p->set.mrt.rates, p->set.mrt.rates + 27, 0.0);
+  std::copy(relaxation, relaxation + count, p->set.mrt.rates);
   return LT_OK;
 }
 
@@ -1896,7 +1887,7 @@ int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, 
   if (p->desc.collision != LT_COLLISION_BGK && p->desc.collision != LT_COLLISION_SMAGORINSKY)
     return fail(LT_ERR_UNSUPPORTED, "a body force exists for the BGK and Smagorinsky collisions; the plan's collision "
                                     "is %d", p->desc.collision);
-  lt_plan::Force f;
+  lt_plan::Settings::Force f;
   if (acceleration) {
     f.on = true;
     for (int c = 0; c < p->unit.d; ++c) f.a[c] = acceleration[c];
@@ -1906,7 +1897,7 @@ int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, 
       return fail(LT_ERR_INVALID, "body force: acceleration (%g, %g, %g), scales %g and %g must be finite", f.a[0],
                   f.a[1], f.a[2], ueq_scale, source_scale);
   }
-  p->force = f;
+  p->set.force = f;
   return LT_OK;
 }
 
@@ -1932,8 +1923,8 @@ int lt_plan_set_equilibrium(lt_plan *p, int kind, double rho0) {
         return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium on a plan with a constant-pressure outlet "
                                         "(EquilibriumOutletP): that boundary evaluates the quadratic equilibrium in the kernel");
   }
-  p->equilibrium = kind;
-  p->rho0 = rho0;
+  p->set.equilibrium = kind;
+  p->set.rho0 = rho0;
   return LT_OK;
 }
 
@@ -1941,7 +1932,7 @@ int lt_plan_set_two_step(lt_plan *p, int32_t mode, int32_t planes_per_workgroup)
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "two-step mode %d", mode);
   if (mode == 1 && p->desc.collision == LT_COLLISION_MRT) return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kMrtMultiStep);
-  if (mode == 1 && p->equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
+  if (mode == 1 && p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
     return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kIncompressibleMultiStep);
   const int sweep = p->unit.d == 2 ? p->n1 : p->n2;          // extent of the sweep axis
   if (planes_per_workgroup < 0 ||
@@ -2046,7 +2037,7 @@ int lt_plan_set_residency(lt_plan *p, int32_t workgroups_per_cu) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (workgroups_per_cu < -1 || workgroups_per_cu == 1 || workgroups_per_cu > 8)
     return fail(LT_ERR_INVALID, "workgroups per CU %d (use -1, 0 or 2..8)", workgroups_per_cu);
-  p->residency = workgroups_per_cu;
+  p->set.residency = workgroups_per_cu;
   return LT_OK;
 }
 
@@ -2056,7 +2047,7 @@ int lt_plan_set_tuning(lt_plan *p, int32_t cache_policy, int32_t wide) {
   if (wide)
     return fail(LT_ERR_UNSUPPORTED, "the 16-byte variants of the one-step kernel lost their A/B (8-13 %% slower) and "
                                     "were removed");
-  p->tune = cache_policy;
+  p->set.tune = cache_policy;
   return LT_OK;
 }
 
