@@ -56,7 +56,9 @@ def main():
         args.first_candidate_budget = 2.0
     bench.MIN_BATCH_S = 0.0
     ctx = lt.Context("cpu", torch.float64, use_native=False)
-    res = [8, 4, 8 * world]
+    # 16^3 nodes per rank: the line's value is MLUPS rounded to one decimal, and a two-step batch of a smaller slab on a
+    # busy host (tens of ms) rounds to 0.0, which a held line must not carry
+    res = [16, 16, 16 * world]
     slab = lt.ZSlab(res)
 
     def real(driver):

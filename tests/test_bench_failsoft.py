@@ -45,7 +45,7 @@ def test_a_good_second_candidate_may_replace_the_held_line():
     assert "bit-identical" in t["checks"]["two-step/rccl"] and "after the timed batches too" in t["checks"]["two-step/rccl"]
     assert t["failures"] == {}
     assert t["chosen"] in ("single-step/rccl", "two-step/rccl")
-    assert len(t["rank_checksums"]) == 2 and all(abs(c - 8 * 4 * 8) < 1e-6 for c in t["rank_checksums"])   # mass of a rank's slab
+    assert len(t["rank_checksums"]) == 2 and all(abs(c - 16 * 16 * 16) < 1e-6 for c in t["rank_checksums"])   # mass of a rank's slab
 
 
 @pytest.mark.parametrize("stub,expect", [("raises-in-build", "unavailable"), ("raises-in-batch", "failed in the timed batches"),
@@ -105,6 +105,6 @@ def test_a_plain_run_times_one_batch_of_k_steps_and_dumps_what_every_rank_comput
         dumps.append([np.load(tmp_path / f"run{run}" / f"f_rank{rank}.npy") for rank in range(2)])
     for rank in range(2):
         a, b = dumps[0][rank], dumps[1][rank]
-        assert a.dtype == np.float64 and a.size == 19 * 8 * 4 * 8 and np.isfinite(a).all()
+        assert a.dtype == np.float64 and a.size == 19 * 16 * 16 * 16 and np.isfinite(a).all()
         assert np.array_equal(a, b)
-    assert abs(float(dumps[0][0].sum()) - 8 * 4 * 8) < 1e-9          # mass of a rank's slab (rho = 1 on average)
+    assert abs(float(dumps[0][0].sum()) - 16 * 16 * 16) < 1e-9          # mass of a rank's slab (rho = 1 on average)
