@@ -384,6 +384,31 @@ int lt_slab_mass_interior(lt_plan *plan, const void *f_dev, const uint8_t *no_ma
 int lt_energy_spectrum(lt_plan *plan, const void *uhat_dev, double scale, int32_t n_bins, double *partial_scratch_dev,
                        double *out_dev, void *stream);
 
+/* Jacobi solver of the periodic pressure-Poisson equation lap(p) = rhs (lettuce/util/utility.py:119-156, torch_jacobi),
+ * without a plan: the fields are dense [shape[0]][shape[1]]([shape[2]]) arrays of `dtype` in C order (the last axis
+ * fastest), dims = 2 or 3, every extent >= 1 (extent 1: a node is its own neighbour, extent 2: both neighbours are the
+ * same node, as torch.roll has it).  One sweep, with S the sum of the 2 dims neighbours of p in the reference's order
+ * (axis 0 -, axis 1 -, [axis 2 -,] axis 0 +, axis 1 +, [axis 2 +]) and dx2 = (dtype)(dx * dx):
+ *   p_next = (rhs * dx2 - S) * (-1) / (2 dims)          r = rhs - (S - (2 dims) * p) / dx2
+ * operation for operation in dtype, no contraction, true divisions; the error of an iterate is mean(r^2), r widened to
+ * fp64, summed in a fixed order (at most LT_JACOBI_BLOCKS workgroup partials, then one workgroup) without atomics: two
+ * calls on the same input give the same bits.  Sweep s + 1 is the one that forms the error of iterate s; a one-workgroup
+ * launch after it holds the error against tol_abs ON THE DEVICE and raises a done flag in work_dev, which every later
+ * sweep reads first and then returns without writing.  The host enqueues `batch` sweeps at a time (0: LT_JACOBI_BATCH)
+ * and reads the flag once per batch: no synchronisation per sweep.  Stopping rule, the reference's: after iteration `it`
+ * when !(error_it > tol_abs) (a NaN error stops) or it == max_num_steps; max_num_steps = 0 returns p unchanged (error
+ * 1, the reference's starting value).  p_dev holds the iterate `it` on return (p is ping-ponged with p_scratch_dev, a
+ * buffer of p's size; rhs_dev is only read), *iterations_out = it and *error_out = error_it (either may be null).  The
+ * call returns after the stream has drained.  work_dev: LT_JACOBI_WORK_BYTES caller-owned bytes, 8-byte aligned.
+ * LT_ERR_INVALID, before any HIP call: a null pointer, dims outside 2-3, an extent < 1 (or more than 2^40 nodes), an
+ * unknown dtype, max_num_steps < 0, batch < 0. */
+#define LT_JACOBI_BLOCKS 1024
+#define LT_JACOBI_BATCH 64
+#define LT_JACOBI_WORK_BYTES ((LT_JACOBI_BLOCKS + 4) * 8)
+int lt_jacobi(void *p_dev, void *p_scratch_dev, const void *rhs_dev, int32_t dtype, int32_t dims, const int64_t *shape,
+              double dx, double tol_abs, int64_t max_num_steps, int32_t batch, void *work_dev, int64_t *iterations_out,
+              double *error_out, void *stream);
+
 /* Introspection for tests and benchmarks. */
 int lt_plan_kernel_info(lt_plan *plan, int32_t *vec_width, int32_t *threads_per_block,
                         int64_t *blocks_per_launch);

@@ -1,7 +1,7 @@
 """State of a simulation and its macroscopic moments; the operator ABCs.
 
-Drop-in for lettuce/_flow.py:16-236,309-336 (``Equilibrium``, ``Boundary``, ``Flow``,
-``initialize_f_neq``).  ``flow.f`` is a plain ``[q, *resolution]`` tensor attribute in the
+Drop-in for lettuce/_flow.py:16-336 (``Equilibrium``, ``Boundary``, ``Flow``, ``pressure_poisson``,
+``initialize_pressure_poisson``, ``initialize_f_neq``).  ``flow.f`` is a plain ``[q, *resolution]`` tensor attribute in the
 reference's C-contiguous layout; the HIP engine works on that memory directly.
 
 On a native context (``Context.use_native``) the moments of the grid-shaped state
@@ -17,9 +17,9 @@ import numpy as np
 import torch
 
 from ._stencil import TorchStencil
-from .util import torch_gradient, LettuceException
+from .util import torch_gradient, torch_jacobi, LettuceException
 
-__all__ = ["Equilibrium", "Flow", "Boundary", "initialize_f_neq"]
+__all__ = ["Equilibrium", "Flow", "Boundary", "pressure_poisson", "initialize_pressure_poisson", "initialize_f_neq"]
 
 
 class Equilibrium(ABC):
@@ -95,8 +95,7 @@ class Flow(ABC):
         rho0 = self.context.convert_to_tensor(self.units.convert_pressure_pu_to_density_lu(p0))
         u0 = self.context.convert_to_tensor(self.units.convert_velocity_to_lu(u0))
         if self.initialize_pressure:
-            raise LettuceException("pressure-Poisson initialisation is outside this engine's "
-                                   "scope (SURVEY.md section 2); set initialize_pressure=False")
+            rho0 = pressure_poisson(self.units, u0, rho0)
         self.f = self.equilibrium(self, rho=rho0, u=u0)
         if self.initialize_fneq:
             self.f = initialize_f_neq(self)
@@ -287,6 +286,65 @@ def local_contract(matrix: torch.Tensor, field: torch.Tensor) -> torch.Tensor:
         term = col * field[k][None, ...]
         out = term if out is None else out.add_(term)
     return out
+
+
+class _TrueQuotients:
+    """A tensor whose ``/ scalar`` is a division on every device: torch's device kernels turn the division by a host
+    scalar into a multiplication by its reciprocal (one bit may differ), the CPU kernels divide.  Dividing by a 0-dim
+    tensor of the field's dtype on the field's device divides everywhere, so that the unit conversions of
+    ``pressure_poisson`` -- ``UnitConversion``'s own formulas, applied to this wrapper -- give the CPU's bits."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+    def __truediv__(self, scalar):
+        divisor = torch.as_tensor(scalar, dtype=self.tensor.dtype, device=self.tensor.device)
+        return _TrueQuotients(self.tensor / divisor)
+
+    def __mul__(self, scalar):
+        return _TrueQuotients(self.tensor * scalar)
+
+    def __add__(self, scalar):
+        return _TrueQuotients(self.tensor + scalar)
+
+    def __sub__(self, scalar):
+        return _TrueQuotients(self.tensor - scalar)
+
+
+def pressure_poisson(units: "UnitConversion", u, rho0, tol_abs=1e-10, max_num_steps=100000):
+    """The density whose pressure solves lap(p) = -sum_ij d_j d_i (u_i u_j) for the velocity ``u`` (lattice units),
+    from the first guess ``rho0``, by Jacobi iteration in physical units (lettuce/_flow.py:239-288).
+
+    The right-hand side is the reference's: second-order ``torch_gradient`` twice per pair (i, j), subtracted in its
+    loop order, on torch, evaluated once.  The iteration is ``util.torch_jacobi``: on a device the engine's solver,
+    which stops by the reference's rule without a host synchronisation per sweep.
+    Changed: the solver gets ``dim = u.shape[0]``, where the reference passes 2 whatever the field (its own comment:
+    "still not working in 3D") -- in 2-D the same call; in 3-D the Laplacian of all three axes."""
+    rhs, p, dx = _poisson_problem(units, u, rho0)
+    p = torch_jacobi(rhs, p, dx, dim=u.shape[0], tol_abs=tol_abs, max_num_steps=max_num_steps)[None, ...]
+    return units.convert_pressure_pu_to_density_lu(_TrueQuotients(p)).tensor
+
+
+def _poisson_problem(units, u, rho0):
+    """(right-hand side, first guess of the pressure, dx) of ``pressure_poisson``, in physical units"""
+    dx = units.convert_length_to_pu(1.0)
+    u = units.convert_velocity_to_pu(_TrueQuotients(u)).tensor
+    p = units.convert_density_lu_to_pressure_pu(_TrueQuotients(rho0)).tensor
+    dim = u.shape[0]
+    with torch.no_grad():
+        rhs = torch.zeros_like(u[0])
+        for i in range(dim):
+            for j in range(dim):
+                rhs -= torch_gradient(torch_gradient(u[i] * u[j], dx)[i], dx)[j]
+    return rhs, p[0], dx
+
+
+def initialize_pressure_poisson(flow: "Flow", max_num_steps=100000, tol_pressure=1e-6):
+    """The equilibrium populations of the flow's velocity with the density of ``pressure_poisson`` -- to be assigned to
+    ``flow.f`` before ``initialize_f_neq`` (lettuce/_flow.py:291-306)."""
+    u = flow.u()
+    rho = pressure_poisson(flow.units, u, flow.rho(), tol_abs=tol_pressure, max_num_steps=max_num_steps)
+    return flow.equilibrium(flow=flow, rho=rho, u=u)
 
 
 def initialize_f_neq(flow: "Flow"):

@@ -27,6 +27,8 @@ LT_ABI_VERSION = 2
 LT_MAX_BOUNDARIES = 127
 SPECTRUM_BLOCKS = 1024          # LT_SPECTRUM_BLOCKS: rows of lt_energy_spectrum's scratch
 SPECTRUM_MAX_BINS = 2048        # LT_SPECTRUM_MAX_BINS: the most bins its kernel takes
+JACOBI_BATCH = 64                         # LT_JACOBI_BATCH: sweeps of lt_jacobi between two looks at its stop flag
+JACOBI_WORK_BYTES = (1024 + 4) * 8        # LT_JACOBI_WORK_BYTES: its partials and state record
 LT_MAX_Q = 27
 
 STENCIL_IDS = {"D2Q9": 0, "D3Q19": 1, "D3Q27": 2, "D1Q3": 3, "D3Q15": 4}
@@ -142,6 +144,8 @@ SYMBOLS = {
                                              ctypes.POINTER(ctypes.c_int64)]),
     "lt_stream_collide_many": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i32, _vp]),
     "lt_plan_set_many_step": (ctypes.c_int, [_vp, _i32]),
+    "lt_jacobi": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(_i64), _dbl, _dbl, _i64, _i32, _vp,
+                                 ctypes.POINTER(_i64), ctypes.POINTER(_dbl), _vp]),
     "lt_probe_copy": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "lt_probe_div_cs": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "lt_ipc_alloc": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(_vp), ctypes.c_char_p]),
@@ -240,6 +244,30 @@ def probe_div_cs(x: torch.Tensor, which: int) -> torch.Tensor:
     if code != 0:
         raise NativeEngineError(lib.lt_last_error().decode())
     return out
+
+
+def jacobi(rhs: torch.Tensor, p: torch.Tensor, dx: float, tol_abs: float, max_num_steps: int, batch: int = 0):
+    """The engine's Jacobi solver of the periodic Poisson equation (lt_jacobi; the reference's ``torch_jacobi`` with its
+    stopping rule held on the device): ``(p, iterations, error)`` -- a new tensor with the iterate after ``iterations``
+    sweeps (``p`` itself is not written) and the mean squared residuum of that iterate.  ``rhs`` and ``p``: contiguous
+    fp32 / fp64 device tensors of one 2-D or 3-D shape.  ``batch``: sweeps enqueued between two looks at the device's
+    stop flag (0: the library's JACOBI_BATCH)."""
+    lib = load_library()
+    if (rhs.device.type != "cuda" or p.device != rhs.device or p.dtype != rhs.dtype or p.dtype not in DTYPE_IDS
+            or p.shape != rhs.shape or not p.is_contiguous() or not rhs.is_contiguous()):
+        raise NativeEngineError(f"jacobi: contiguous fp32 / fp64 device tensors of one shape, got {tuple(rhs.shape)} "
+                                f"{rhs.dtype} on {rhs.device} and {tuple(p.shape)} {p.dtype} on {p.device}")
+    with torch.cuda.device(p.device):
+        out, scratch = p.clone(), torch.empty_like(p)
+        work = torch.empty(JACOBI_WORK_BYTES // 8, dtype=torch.float64, device=p.device)
+        shape = (_i64 * max(3, p.ndim))(*p.shape)
+        iterations, error = _i64(0), _dbl(0.0)
+        code = lib.lt_jacobi(_ptr(out), _ptr(scratch), _ptr(rhs), DTYPE_IDS[p.dtype], p.ndim, shape, float(dx),
+                             float(tol_abs), int(max_num_steps), int(batch), _ptr(work), ctypes.byref(iterations),
+                             ctypes.byref(error), _stream_handle())
+    if code != 0:
+        raise NativeEngineError(lib.lt_last_error().decode())
+    return out, int(iterations.value), float(error.value)
 
 
 class Plan:

@@ -1527,6 +1527,59 @@ int lt_slab_unpack(lt_plan *p, void *f, int64_t plane, int32_t direction, const 
   return pack(p, false, f, plane, direction, const_cast<void *>(buf), s);
 }
 
+int lt_jacobi(void *p, void *p_scratch, const void *rhs, int32_t dtype, int32_t dims, const int64_t *shape, double dx,
+              double tol_abs, int64_t max_num_steps, int32_t batch, void *work, int64_t *iterations_out, double *error_out,
+              void *stream) {
+  if (!p || !p_scratch || !rhs || !shape || !work) return fail(LT_ERR_INVALID, "jacobi: null field / scratch / shape / work buffer");
+  if (dims != 2 && dims != 3) return fail(LT_ERR_INVALID, "jacobi: %d dimensions (2 or 3)", (int)dims);
+  if (dtype != LT_F32 && dtype != LT_F64) return fail(LT_ERR_INVALID, "jacobi: unknown dtype %d", (int)dtype);
+  long long N = 1;
+  for (int a = 0; a < dims; ++a) {
+    if (shape[a] < 1 || shape[a] > 0x7fffffffLL)
+      return fail(LT_ERR_INVALID, "jacobi: shape[%d] = %lld (an extent is >= 1 and < 2^31)", a, (long long)shape[a]);
+    N *= shape[a];
+    if (N > (1LL << 40)) return fail(LT_ERR_INVALID, "jacobi: more than 2^40 nodes");
+  }
+  if (max_num_steps < 0) return fail(LT_ERR_INVALID, "jacobi: max_num_steps = %lld", (long long)max_num_steps);
+  if (batch < 0) return fail(LT_ERR_INVALID, "jacobi: batch = %d", (int)batch);
+  if (p == p_scratch || (uintptr_t)work % 8) return fail(LT_ERR_INVALID, "jacobi: scratch is the field itself, or the work buffer is not 8-byte aligned");
+  if (iterations_out) *iterations_out = 0;
+  if (error_out) *error_out = 1.0;                  // the reference's starting value: what max_num_steps = 0 leaves
+  if (max_num_steps == 0) return LT_OK;
+  const long long K = batch ? batch : LT_JACOBI_BATCH;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  struct Record { int32_t done, pad; int64_t iterations; double error; } record = {0, 0, 0, 1.0};
+  void *state = lt::jacobi_state(work);
+  LT_HIP(hipMemsetAsync(state, 0, sizeof record, s));
+  lt::JacobiArgs a;
+  memset(&a, 0, sizeof a);
+  a.rhs = rhs; a.work = work; a.dtype = dtype; a.d = dims;
+  a.n0 = (int)shape[0]; a.n1 = (int)shape[1]; a.n2 = dims == 3 ? (int)shape[2] : 1;
+  a.dx2 = dx * dx; a.tol = tol_abs; a.stream = s;
+  void *buf[2] = {p, p_scratch};                    // iterate k lies in buf[k % 2]
+  // Sweep k reads iterate k - 1 and writes iterate k; the launch behind it forms the error of iterate k - 1 (none behind
+  // sweep 1: the reference never looks at the starting field's).  Sweep max + 1 is there for the last error alone.
+  const long long last = (long long)max_num_steps + 1;
+  for (long long k = 1; k <= last && !record.done;) {
+    for (long long end = std::min(last, k + K - 1); k <= end; ++k) {
+      a.p_in = buf[(k - 1) % 2];
+      a.p_out = k == last ? nullptr : buf[k % 2];
+      a.sweep = k; a.finish = k >= 2;
+      const int r = lt::jacobi_sweep(a);
+      if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+    }
+    LT_HIP(hipMemcpyAsync(&record, state, sizeof record, hipMemcpyDeviceToHost, s));
+    LT_HIP(hipStreamSynchronize(s));
+  }
+  if (record.iterations % 2) {
+    LT_HIP(hipMemcpyAsync(p, p_scratch, (size_t)N * (dtype == LT_F32 ? 4 : 8), hipMemcpyDeviceToDevice, s));
+    LT_HIP(hipStreamSynchronize(s));
+  }
+  if (iterations_out) *iterations_out = record.iterations;
+  if (error_out) *error_out = record.error;
+  return LT_OK;
+}
+
 int lt_probe_copy(void *dst, const void *src, int64_t n_bytes, int32_t cache_policy,
                   int32_t max_blocks, void *stream) {
   if (!dst || !src || n_bytes < 16 || n_bytes % 16 != 0 || (uintptr_t)dst % 16 || (uintptr_t)src % 16)

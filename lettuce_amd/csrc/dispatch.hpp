@@ -160,4 +160,21 @@ LT_UNITS(LT_DECLARE_UNIT)
 // returns -1 when the combination has no instantiated kernel, else the hipError_t of the launch
 constexpr int kNoKernel = -1;
 
+// The Jacobi solver's two launches (jacobi.hpp), in an object of their own (jacobi.hip) that holds no unit: one sweep from
+// p_in into p_out (nullptr: the iterate is not kept) with the workgroup partials of the input iterate's squared residuum,
+// and -- when finish is set -- the one-workgroup launch behind it that forms the error of iterate sweep - 1, holds it
+// against tol and writes the state record.  work: the caller's kJacobiBlocks partials with the record behind them.
+struct JacobiArgs {
+  const void *p_in, *rhs;
+  void *p_out, *work;
+  int dtype, d;                // 0 float, 1 double; 2 or 3
+  int n0, n1, n2;              // n2 = 1 in 2-D
+  double dx2, tol;             // dx2 formed in double, cast to the dtype at the launch
+  long long sweep;
+  bool finish;
+  hipStream_t stream;
+};
+int jacobi_sweep(const JacobiArgs &);          // the hipError_t of the launches
+void *jacobi_state(void *work);                // where the record lies in the work buffer
+
 }  // namespace lt

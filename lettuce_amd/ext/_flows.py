@@ -410,7 +410,9 @@ class DecayingTurbulence(ExtFlow):
     Kept from the reference: its ``np.meshgrid(*frequencies)`` has the default 'xy' indexing, so the wavenumber
     components of the first two axes are swapped and the first two extents must be equal (refused here by name, where
     numpy would fail to broadcast); ``_compute_initial_pressure`` returns zeros; in 2-D ``initialize_pressure`` defaults
-    to True, which this engine's ``Flow.initialize`` refuses -- pass ``initialize_pressure=False``.
+    to True: ``Flow.initialize`` then takes the density from ``pressure_poisson`` (a Jacobi iteration to 1e-10, on a
+    device the engine's ``lt_jacobi``), so that the run starts without the acoustic transient of rho = 1; in 3-D the
+    option is switched off, as in the reference.
     Changed: ``self.spectrum`` is summed per bin index (``spectrum_bins`` of ``_reporter.py``, bincount) instead of
     through a float64 mask [*res, K].  The initial velocity does not depend on it.
     Not in ``flow_by_name``: the fifth positional argument is ``k0``, not the stencil."""

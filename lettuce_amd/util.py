@@ -1,9 +1,9 @@
 """Exceptions, warnings and the small numerical helpers the hot path's callers need.
 
 Mirrors the public names of lettuce/util/utility.py:21-34 (exception/warning classes),
-:37-99 (``torch_gradient``) and :158-161 (``append_axes``) of the reference.  IO helpers
-(HDF5, datasets), the Jacobi pressure solver and moment transforms are out of scope
-(SURVEY.md section 2).
+:37-99 (``torch_gradient``), :119-156 (``torch_jacobi``, on the engine's ``lt_jacobi`` for device
+tensors) and :158-161 (``append_axes``) of the reference.  IO helpers (HDF5, datasets),
+``grid_fine_to_coarse`` and moment transforms are out of scope.
 """
 import inspect
 
@@ -13,7 +13,7 @@ from ._errors import LettuceException, LettuceWarning, InefficientCodeWarning, E
 from ._native import NativeEngineError
 
 __all__ = ["LettuceException", "LettuceWarning", "InefficientCodeWarning", "ExperimentalWarning",
-           "NativeEngineError", "torch_gradient", "append_axes", "get_subclasses"]
+           "NativeEngineError", "torch_gradient", "torch_jacobi", "append_axes", "get_subclasses"]
 
 
 def get_subclasses(cls, module):
@@ -50,6 +50,61 @@ def torch_gradient(f, dx=1, order=2):
                 acc = term if acc is None else acc + term
             out[axis] = acc * scale
     return out
+
+
+def _jacobi_engine(f, p, dim):
+    """the engine's library when lt_jacobi takes these arguments, else None: contiguous fp32 / fp64 device tensors of
+    one shape whose number of axes is ``dim`` (2 or 3), and a library that loads"""
+    from . import _native
+    if not (isinstance(f, torch.Tensor) and isinstance(p, torch.Tensor)):
+        return None
+    if (p.device.type != "cuda" or f.device != p.device or p.dtype not in _native.DTYPE_IDS or f.dtype != p.dtype
+            or dim not in (2, 3) or p.ndim != dim or f.shape != p.shape or p.numel() == 0
+            or not p.is_contiguous() or not f.is_contiguous()):
+        return None
+    try:
+        return _native.load_library()
+    except NativeEngineError:
+        return None
+
+
+def torch_jacobi(f, p, dx, dim, tol_abs=1e-10, max_num_steps=100000):
+    """Jacobi solver for the periodic pressure-Poisson equation lap(p) = f (lettuce/util/utility.py:119-156): the
+    reference's signature, stopping rule and result.
+
+    Contiguous fp32 / fp64 device tensors with ``dim == p.ndim`` go to the engine (``lt_jacobi``: one fused sweep per
+    iteration with the reference's arithmetic operation for operation, the mean squared residuum in fp64 in a fixed
+    order, the stopping rule held on the device and read by the host once per batch of sweeps); everything else --
+    CPU tensors, other dtypes, views, a ``dim`` that is not the field's, no library -- runs the reference's torch
+    expression below, which synchronises with the device on every sweep (``error > tol_abs``)."""
+    if _jacobi_engine(f, p, dim) is not None:
+        from . import _native
+        return _native.jacobi(f, p, dx, tol_abs, max_num_steps)[0]
+    return _jacobi_expression(f, p, dx, dim, tol_abs, max_num_steps)
+
+
+def _jacobi_expression(f, p, dx, dim, tol_abs, max_num_steps):
+    """torch_jacobi as whole-field torch expressions, on any device"""
+    if dim not in (2, 3):
+        raise LettuceException("Invalid dimension!")
+    taps = 2 * dim
+    dx2 = dx ** 2
+
+    def neighbours(q):
+        # the reference's order: the lower neighbour along every axis, then the upper ones, added from the left
+        shifted = [q.roll(shifts=shift, dims=axis) for shift in (1, -1) for axis in range(dim)]
+        total = shifted[0]
+        for term in shifted[1:]:
+            total = total + term
+        return total
+
+    error, it = 1, 0
+    while error > tol_abs and it < max_num_steps:
+        it += 1
+        p = (f * dx2 - neighbours(p)) * -1 / taps
+        residuum = f - (neighbours(p) - taps * p) / dx2
+        error = torch.mean(residuum ** 2)
+    return p
 
 
 def append_axes(array, n):
