@@ -384,6 +384,28 @@ int lt_slab_mass_interior(lt_plan *plan, const void *f_dev, const uint8_t *no_ma
 int lt_energy_spectrum(lt_plan *plan, const void *uhat_dev, double scale, int32_t n_bins, double *partial_scratch_dev,
                        double *out_dev, void *stream);
 
+/* Momentum-exchange force of the fluid on a body of full-way bounce-back nodes (no counterpart in the reference
+ * snapshot), per time step, in lattice units:
+ *   out_dev[c] = sum over x_s with solid[x_s] of sum over q >= 1 with not solid[x_s - e_q] of 2 e_{q,c} f_q(x_s),
+ * c = 0 .. d - 1 in logical axis order; out_dev[c] = 0 for d <= c < 3.  f_dev: the populations after streaming, dense
+ * [q][N] in the plan's dtype (the caller's own buffer: resident populations are stored into it first).  solid_dev: one
+ * byte per node [N], nonzero = solid.  f_q(x_s) arrived from x_s - e_q and, swapped at collision time, leaves again
+ * along -e_q in the same step; x_s - e_q wraps periodically on every axis, as streaming wraps it (extents 1 and 2
+ * included), nodes of other boundaries count as not solid, links between two solid nodes carry nothing.  A sphere in
+ * a +x stream has out_dev[0] > 0.
+ * A fluid node costs its one byte; a solid node the bytes of its q - 1 neighbours and, unless all of them are solid,
+ * f_q of its fluid links and its own f_0 (read in place of the others and dropped).
+ * fp64 from the first operation (2 f_q and the sign are exact).  Fixed summation order, no floating-point atomics: the
+ * first launch has min(ceil(N / 256), LT_BOUNDARY_FORCE_BLOCKS) workgroups striding the nodes and writes
+ * partial_scratch_dev [3][workgroups]; the second, one workgroup, adds them in index order and writes all three
+ * outputs, exact 0.0 where nothing is solid.  Two calls on the same input give the same bits.  partial_scratch_dev is
+ * caller-owned: 3 * LT_BOUNDARY_FORCE_BLOCKS doubles always suffice.  out_dev: 3 doubles.
+ * LT_ERR_UNSUPPORTED: 1-D plans, the slab layout or ghost planes, a plan with a population stride (f_dev is dense).
+ * LT_ERR_INVALID: a null pointer, before any HIP call. */
+#define LT_BOUNDARY_FORCE_BLOCKS 1024
+int lt_boundary_force(lt_plan *plan, const void *f_dev, const uint8_t *solid_dev, double *partial_scratch_dev,
+                      double *out_dev, void *stream);
+
 /* Jacobi solver of the periodic pressure-Poisson equation lap(p) = rhs (lettuce/util/utility.py:119-156, torch_jacobi),
  * without a plan: the fields are dense [shape[0]][shape[1]]([shape[2]]) arrays of `dtype` in C order (the last axis
  * fastest), dims = 2 or 3, every extent >= 1 (extent 1: a node is its own neighbour, extent 2: both neighbours are the

@@ -27,6 +27,7 @@ LT_ABI_VERSION = 2
 LT_MAX_BOUNDARIES = 127
 SPECTRUM_BLOCKS = 1024          # LT_SPECTRUM_BLOCKS: rows of lt_energy_spectrum's scratch
 SPECTRUM_MAX_BINS = 2048        # LT_SPECTRUM_MAX_BINS: the most bins its kernel takes
+BOUNDARY_FORCE_BLOCKS = 1024    # LT_BOUNDARY_FORCE_BLOCKS: columns of lt_boundary_force's scratch
 JACOBI_BATCH = 64                         # LT_JACOBI_BATCH: sweeps of lt_jacobi between two looks at its stop flag
 JACOBI_WORK_BYTES = (1024 + 4) * 8        # LT_JACOBI_WORK_BYTES: its partials and state record
 LT_MAX_Q = 27
@@ -100,6 +101,7 @@ SYMBOLS = {
     "lt_enstrophy": (ctypes.c_int, [_vp, _vp, _vp, _dbl, _dbl, _vp, _vp]),
     "lt_mass_interior": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "lt_energy_spectrum": (ctypes.c_int, [_vp, _vp, _dbl, _i32, _vp, _vp, _vp]),
+    "lt_boundary_force": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "lt_slab_velocity": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "lt_slab_enstrophy": (ctypes.c_int, [_vp, _vp, _dbl, _dbl, _vp, _vp]),
     "lt_slab_mass_interior": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
@@ -307,6 +309,7 @@ class Plan:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._keepalive = {}            # boundary index -> field tensor the engine holds a pointer to
         self._const = {}                # answers of the engine that do not change while the masks stay
+        self._force_scratch = None      # lt_boundary_force's partial sums, allocated on first use
         self.resident_mode = -1         # lt_plan_set_resident: -1 automatic, 0 off, 1 requested
         self.pop_stride = 0             # elements between populations of the caller's buffers (0 = dense)
         desc = _PlanDesc()
@@ -680,6 +683,28 @@ class Plan:
         for t in (uhat, scratch):
             t.record_stream(torch.cuda.current_stream())
         return out[:n_bins]
+
+    @_on_device
+    def boundary_force(self, f, solid_u8):
+        """float64 device tensor [d], logical axis order: the momentum-exchange force of the fluid on the nodes of
+        ``solid_u8`` (uint8 [*res], nonzero = solid), sum of 2 e_q f_q(x_s) over the links from a solid node x_s to a
+        fluid node x_s - e_q, per step in lattice units (lt_boundary_force: fp64, fixed summation order).  ``f``: the
+        populations after streaming.  The scratch of the partial sums is kept on the plan."""
+        self._tensor_ok(f, self.f_shape)
+        grid = self.f_shape[1:]
+        if (solid_u8.device != f.device or solid_u8.dtype != torch.uint8 or not solid_u8.is_contiguous()
+                or list(solid_u8.shape) != list(grid)):
+            raise NativeEngineError(f"solid mask: need a contiguous uint8 tensor {list(grid)} on {f.device}, got "
+                                    f"{list(solid_u8.shape)} {solid_u8.dtype} on {solid_u8.device}")
+        scratch = self._force_scratch
+        if scratch is None or scratch.device != f.device:
+            scratch = self._force_scratch = torch.empty([3, BOUNDARY_FORCE_BLOCKS], dtype=torch.float64, device=f.device)
+        out = torch.empty([3], dtype=torch.float64, device=f.device)
+        self._check(self.lib.lt_boundary_force(self._handle, _ptr(f), _ptr(solid_u8), _ptr(scratch), _ptr(out),
+                                               _stream_handle()))
+        for t in (solid_u8, scratch):
+            t.record_stream(torch.cuda.current_stream())
+        return out[:self.d]
 
     @_on_device
     def mass_interior(self, f, no_mass_mask: Optional[torch.Tensor] = None):

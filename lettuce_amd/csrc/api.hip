@@ -1456,6 +1456,30 @@ int lt_energy_spectrum(lt_plan *p, const void *uhat, double scale, int32_t n_bin
   return LT_OK;
 }
 
+int lt_boundary_force(lt_plan *p, const void *f, const uint8_t *solid, double *partial_scratch, double *out, void *s) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (!f || !solid || !partial_scratch || !out)
+    return fail(LT_ERR_INVALID, "null populations / solid mask / scratch / output");
+  if (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
+    return fail(LT_ERR_UNSUPPORTED, "boundary force: 2-D / 3-D grids in the reference layout without ghost planes");
+  if (pop_stride_of(p) != p->N)
+    return fail(LT_ERR_UNSUPPORTED, "boundary force: reads dense population buffers only (the plan has a population "
+                                    "stride of %lld)", pop_stride_of(p));
+  lt::AuxArgs a;
+  memset(&a, 0, sizeof a);
+  a.what = 11; a.layout = p->desc.layout;
+  a.f = f; a.mask = solid; a.partial = partial_scratch; a.out = out;
+  a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2; a.N = p->N; a.stride = p->N;
+  // fixed launch geometry: a node per thread and pass, at most LT_BOUNDARY_FORCE_BLOCKS workgroups of 256
+  const long long blocks = (p->N + 255) / 256;
+  a.reduce_blocks = (int)(blocks < LT_BOUNDARY_FORCE_BLOCKS ? blocks : LT_BOUNDARY_FORCE_BLOCKS);
+  a.stream = static_cast<hipStream_t>(s);
+  const int r = p->unit.aux(a);
+  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no boundary force kernel");
+  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  return LT_OK;
+}
+
 namespace {
 int slab_plan_ok(lt_plan *p, const char *who) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");

@@ -74,7 +74,9 @@ struct AuxArgs {
                          // 7 f_neq initialisation (scale = tau, inv_dx = the identity's cs^2), 8 enstrophy of a slab's
                          // velocity field u [3][n2][n1][n0] (three neighbour planes per side), 9 interior mass of a slab,
                          // 10 energy spectrum (f = d Fourier-transformed fields, partial = the caller's scratch of
-                         // reduce_blocks x n_bins doubles, count = modes per workgroup, out = n_bins doubles)
+                         // reduce_blocks x n_bins doubles, count = modes per workgroup, out = n_bins doubles),
+                         // 11 momentum-exchange force on the nodes of mask (f = dense populations, partial = the caller's
+                         // scratch of 3 x reduce_blocks doubles, out = 3 doubles)
   int layout;
   const void *f;         // populations (what 0, 2, 3) / feq output (what 1; cast away const)
   void *rho;             // what 0: out, what 1: in
@@ -89,7 +91,7 @@ struct AuxArgs {
   double scale, inv_dx;  // what 5: u_pu = scale * u_lu, 1 / dx_pu
   int equilibrium;       // what 1, 7: lt_equilibrium_kind of the plan (0: quadratic) and, for kind 1, its rho0
   double rho0;
-  const unsigned char *mask;   // what 6, 9: no-mass mask or null
+  const unsigned char *mask;   // what 6, 9: no-mass mask or null; what 11: the solid nodes
   int z_begin, nz_global;      // what 9: global index of the rank's first plane, planes of the whole grid
   long long u_stride;          // what 0: elements between the components of u (0 = N)
   int n_bins;                  // what 10: bins of the spectrum
@@ -137,7 +139,7 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 // on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
 // collision) and outlets (plans with a constant-pressure outlet) and incompressible (the kernels of the incompressible
 // equilibrium), every unit, sweeps and smagorinsky (3-D
-// units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27), spectrum (2-D and 3-D units).  Declared for every unit, defined where the Makefile builds the part.
+// units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27), spectrum and boundary_force (2-D and 3-D units).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
   int aux_##tag(const AuxArgs &);                              \
@@ -154,7 +156,8 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
   int mrt_outlets_##tag(const StepArgs &, const NameBuf *);    \
   int incompressible_##tag(const StepArgs &, const NameBuf *); \
   int incompressible_aux_##tag(const AuxArgs &);               \
-  int spectrum_##tag(const AuxArgs &);
+  int spectrum_##tag(const AuxArgs &);                         \
+  int boundary_force_##tag(const AuxArgs &);
 LT_UNITS(LT_DECLARE_UNIT)
 
 // returns -1 when the combination has no instantiated kernel, else the hipError_t of the launch

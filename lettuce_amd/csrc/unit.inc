@@ -9,6 +9,7 @@
 #include "twostep_masked.hpp"
 #include "twostep2d.hpp"
 #include "spectrum.hpp"
+#include "boundary_force.hpp"
 
 #define LT_CAT_(a, b) a##b
 #define LT_CAT(a, b) LT_CAT_(a, b)
@@ -58,6 +59,8 @@
 //                         several steps.  Objects of their own again: every other plan launches what it launched before
 //   spectrum (inst13_)    2-D and 3-D units: the two launches of the energy spectrum (spectrum.hpp), which depend on the
 //                         scalar type and the dimension only -- an object of its own, so that no other object changes
+//   boundary_force (inst14_)  2-D and 3-D units: the two launches of the momentum-exchange force on a bounce-back body
+//                         (boundary_force.hpp) -- an object of its own again
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -72,6 +75,7 @@
 #define LT_PART_mrt_outlets 11
 #define LT_PART_incompressible 12
 #define LT_PART_spectrum 13
+#define LT_PART_boundary_force 14
 #define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
@@ -95,17 +99,20 @@
 #elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 0
-#elif LT_PART_IS(spectrum)
+#elif LT_PART_IS(spectrum) || LT_PART_IS(boundary_force)
 #define LT_ONE_STEP 0
 #define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible or spectrum"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible, spectrum or boundary_force"
 #endif
 #if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
 #error "the MRT collision exists on D2Q9 and D3Q27"
 #endif
 #if LT_PART_IS(spectrum) && LT_FIELD(d, LT_UNIT) < 2
 #error "the energy spectrum exists in 2-D and 3-D"
+#endif
+#if LT_PART_IS(boundary_force) && LT_FIELD(d, LT_UNIT) < 2
+#error "the boundary force kernel exists in 2-D and 3-D"
 #endif
 
 namespace lt {
@@ -703,6 +710,11 @@ int aux_impl(const AuxArgs &a) {
       if constexpr (LAYOUT == 0) return LT_CAT(spectrum_, LT_TAG)(a);
 #endif
       return kNoKernel;
+    case 11:    // momentum-exchange force on the nodes of a.mask: part boundary_force
+#if LT_FIELD(d, LT_UNIT) >= 2
+      if constexpr (LAYOUT == 0) return LT_CAT(boundary_force_, LT_TAG)(a);
+#endif
+      return kNoKernel;
     case 9:
       if constexpr (S::D == 3 && LAYOUT == 1) {
         hipLaunchKernelGGL((interior_mass_slab_kernel<T, S::Q>), dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream,
@@ -843,6 +855,17 @@ int LT_CAT(spectrum_, LT_TAG)(const AuxArgs &a) {
                      a.count, a.n_bins, a.partial);
   hipLaunchKernelGGL(finish_spectrum_kernel<T>, dim3((a.n_bins + kSpectrumThreads - 1) / kSpectrumThreads),
                      dim3(kSpectrumThreads), 0, a.stream, a.partial, a.reduce_blocks, a.n_bins, a.scale, a.out);
+  return (int)hipGetLastError();
+}
+#elif LT_PART_IS(boundary_force)
+// lt_boundary_force (what 11): a.f the dense populations, a.mask the solid bytes, a.partial the caller's
+// [3][a.reduce_blocks] scratch, a.out three doubles
+int LT_CAT(boundary_force_, LT_TAG)(const AuxArgs &a) {
+  if (a.what != 11 || a.layout != 0 || a.reduce_blocks < 1 || a.reduce_blocks > kForceMaxBlocks) return kNoKernel;
+  hipLaunchKernelGGL((boundary_force_kernel<T, S>), dim3(a.reduce_blocks), dim3(kForceThreads), 0, a.stream,
+                     static_cast<const T *>(a.f), a.mask, a.N, a.n0, a.n1, a.n2, a.partial);
+  hipLaunchKernelGGL((finish_force_kernel<T, S::D>), dim3(1), dim3(kForceThreads), 0, a.stream, a.partial,
+                     a.reduce_blocks, a.out);
   return (int)hipGetLastError();
 }
 #elif LT_PART_IS(mrt_outlets)

@@ -7,6 +7,9 @@ wavefront/LDS reductions in fp64 (``lt_kinetic_energy``, ``lt_max_velocity``, ``
 The energy spectrum is one ``torch.fft.fftn`` of the velocity field and one binning reduction on the
 device (``lt_energy_spectrum``: integer bins, fp64, fixed order); neither path builds the
 reference's [*res, K] wave mask, so the observable runs at the engine's grid sizes.
+The force on a bounce-back body (``BoundaryForce`` and the drag and lift coefficients, which the reference snapshot
+does not have) is a momentum-exchange sum over the body's surface links: ``lt_boundary_force`` reads one byte per
+node and the populations of surface nodes only, in fp64 with a fixed order.
 VTK / HDF5 / image writers are host-side post-processing and out of scope.
 """
 import math
@@ -23,7 +26,8 @@ from .._simulation import Reporter
 from ..util import torch_gradient
 
 __all__ = ["Observable", "ObservableReporter", "MaximumVelocity", "IncompressibleKineticEnergy",
-           "Enstrophy", "EnergySpectrum", "Mass", "ErrorReporter"]
+           "Enstrophy", "EnergySpectrum", "Mass", "BoundaryForce", "DragCoefficient", "LiftCoefficient",
+           "ErrorReporter"]
 
 
 class Observable(ABC):
@@ -180,6 +184,104 @@ class Mass(Observable):
         if self.mask is not None:
             mass -= (f * self.mask.to(dtype=torch.float)).sum()
         return mass
+
+
+def momentum_exchange(stencil, f, solid):
+    """The torch expression of ``BoundaryForce``: fp64 ``[d]``.  ``f`` [q, *res]; ``solid`` bool [*res] on the same
+    device.  Per q one ``torch.roll`` of the mask (``roll(solid, e_q)[x] = solid[x - e_q]``), the populations on the
+    links from a solid to a fluid node, summed in fp64."""
+    d = stencil.d
+    axes = tuple(range(d))
+    total = torch.zeros(d, dtype=torch.float64, device=f.device)
+    for q in range(1, stencil.q):
+        e = [int(x) for x in stencil.e[q]]
+        link = solid & ~torch.roll(solid, shifts=tuple(e), dims=axes)
+        s = 2.0 * f[q][link].to(torch.float64).sum()
+        for c in range(d):
+            if e[c]:
+                total[c] += e[c] * s
+    return total
+
+
+class BoundaryForce(Observable):
+    """The force the fluid exerts on a body of full-way bounce-back nodes, per time step, in lattice units, by momentum
+    exchange: ``[d]`` values in the context dtype,
+
+        F_c = sum over solid x_s, over q >= 1 with x_s - e_q not solid, of 2 e_{q,c} f_q(x_s).
+
+    ``flow.f`` is post-streaming: f_q(x_s) arrived from x_s - e_q and, swapped by the bounce-back rule at collision
+    time, leaves again along -e_q within the same step.  Neighbours wrap periodically as streaming does, nodes of other
+    boundaries count as not solid, links between two solid nodes carry nothing.  A body in a +x stream has F_0 > 0.
+
+    ``boundary``: a ``BounceBackBoundary`` (its mask) or a bool tensor / array ``[*res]``.  Where ``Simulation`` lets a
+    boundary of a higher index win on some of the body's nodes, those nodes do not bounce back: pass
+    ``simulation.no_collision_mask == index`` instead.  On a native context one masked reduction on the device
+    (``lt_boundary_force``: fp64, fixed order); elsewhere, and for D1Q3, one ``torch.roll`` of the mask per q and
+    sums in fp64.  Needs the whole field: not ``slab_aware``, a slab simulation refuses it by name."""
+
+    def __init__(self, flow: "Flow", boundary):
+        super().__init__(flow)
+        self._solid = None
+        self.mask = boundary if isinstance(boundary, (torch.Tensor, np.ndarray)) else getattr(boundary, "_mask", boundary)
+
+    @property
+    def mask(self) -> torch.Tensor:
+        """the solid nodes: contiguous uint8 ``[*res]`` on the context's device (assign a bool tensor / array)"""
+        return self._solid
+
+    @mask.setter
+    def mask(self, value):
+        if not isinstance(value, (torch.Tensor, np.ndarray)):
+            raise LettuceException(f"{type(self).__name__}: a BounceBackBoundary or a bool tensor / array "
+                                   f"{list(self.flow.resolution)}, got {type(value).__name__}")
+        if list(value.shape) != list(self.flow.resolution):
+            raise LettuceException(f"{type(self).__name__}: mask of shape {list(value.shape)} on a grid "
+                                   f"{list(self.flow.resolution)}")
+        solid = torch.as_tensor(value).to(self.context.device) != 0
+        self._solid = solid.to(torch.uint8).contiguous()
+
+    def force(self, f: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the force in fp64, ``[d]``, on the device of ``f``"""
+        flow = self.flow
+        f = flow.f if f is None else f
+        d = flow.stencil.d
+        plan = flow._engine_plan(f) if (d >= 2 and self._solid.device == f.device) else None
+        if plan is not None:
+            return plan.boundary_force(f, self._solid)
+        return momentum_exchange(flow.stencil, f, self._solid.to(f.device) != 0)
+
+    def __call__(self, f: Optional[torch.Tensor] = None):
+        return self.force(f).to(self.context.dtype)
+
+
+class DragCoefficient(BoundaryForce):
+    """C = F[direction] / (0.5 rho_char_lu u_char_lu^2 A_lu) of the force on ``boundary`` (``BoundaryForce``).
+    ``area`` in physical units -- the frontal area in 3-D, the diameter in 2-D -- becomes
+    A_lu = area * convert_length_to_lu(1)^(d - 1); the ratio is dimensionless."""
+
+    def __init__(self, flow: "Flow", boundary, area, direction: int = 0):
+        super().__init__(flow, boundary)
+        self.direction = int(direction)
+        if not 0 <= self.direction < flow.stencil.d:
+            raise LettuceException(f"{type(self).__name__}: direction {self.direction} on a {flow.stencil.d}-D flow")
+        self.area = area
+
+    @property
+    def area_lu(self) -> float:
+        units = self.flow.units
+        return float(self.area) * float(units.convert_length_to_lu(1.0)) ** (self.flow.stencil.d - 1)
+
+    def __call__(self, f: Optional[torch.Tensor] = None):
+        units = self.flow.units
+        scale = 0.5 * float(units.characteristic_density_lu) * float(units.characteristic_velocity_lu) ** 2 * self.area_lu
+        return (self.force(f)[self.direction] / scale).to(self.context.dtype)
+
+
+class LiftCoefficient(DragCoefficient):
+    """The same across the stream: ``direction`` defaults to 1."""
+
+    def __init__(self, flow: "Flow", boundary, area, direction: int = 1):
+        super().__init__(flow, boundary, area, direction)
 
 
 class ObservableReporter(Reporter):
