@@ -79,7 +79,13 @@ enum lt_boundary_kind {
   /* EquilibriumOutletP (equilibrium_outlet_p.py:12-91): every node of the outlet plane gets feq(rho_outlet, u of the
    * node next to it).  axis, side and flags as for the ABB outlet; one-step kernels only (lt_run keeps them; the
    * entry points with several steps per launch answer LT_ERR_UNSUPPORTED and name the boundary). */
-  LT_BOUNDARY_PRESSURE_OUTLET = 4
+  LT_BOUNDARY_PRESSURE_OUTLET = 4,
+  /* Interpolated / half-way bounce-back on a list of links (no counterpart in the reference snapshot; lt_plan_set_links
+   * below).  The stepping kernels leave such a node alone -- not collided, streamed -- and a sparse pass over the list
+   * follows every collide-only and fused one-step launch.  2-D / 3-D plans in the reference layout without ghost planes;
+   * one-step launches over the whole field only.  (6: lt_plan_create keeps answering "unknown boundary kind 5", which
+   * callers have been promised.) */
+  LT_BOUNDARY_LINK_BOUNCE_BACK = 6
 };
 enum lt_layout { LT_LAYOUT_REFERENCE = 0, LT_LAYOUT_SLAB = 1 };
 /* lettuce/ext/_equilibrium/quadratic_equilibrium.py:11-25 (and quadratic_equilibrium_less_memory.py:14-30, the same
@@ -405,6 +411,44 @@ int lt_energy_spectrum(lt_plan *plan, const void *uhat_dev, double scale, int32_
 #define LT_BOUNDARY_FORCE_BLOCKS 1024
 int lt_boundary_force(lt_plan *plan, const void *f_dev, const uint8_t *solid_dev, double *partial_scratch_dev,
                       double *out_dev, void *stream);
+
+/* Link bounce-back (LT_BOUNDARY_LINK_BOUNCE_BACK): linear interpolated bounce-back after Bouzidi, Firdaouss and
+ * Lallemand (2001), half-way bounce-back being its case d = 1/2.  A link is (r, x_s): x_s a node of the boundary, r >= 1
+ * a direction whose neighbour x_f = x_s + e_r is a fluid node; q = opposite(r), x_ff = x_f + e_r; neighbours wrap
+ * periodically on every axis, as streaming wraps them.  On the post-collision populations the pass writes
+ *   f_r(x_s) = c1 * A + c2 * B,   A = f_q(x_f),   B = second_source ? f_r(x_f) : f_q(x_ff)
+ * -- two products and one sum in the plan's dtype, each rounded on its own -- and streaming then carries the slot to
+ * (r, x_f).  Only fluid nodes are read, only slots of the boundary's nodes written, every slot by one link.
+ *
+ * lt_plan_set_links gives boundary `boundary_index` (0-based, as for lt_plan_update_boundary) its list: n_links entries
+ * in HOST memory, sorted by node, then by direction, no entry twice; nodes[i] the index of x_s within a population
+ * (C order of the grid), directions[i] = r in 1 .. q - 1, c1 / c2 in the plan's dtype, second_source[i] 0 or 1.  The
+ * list is copied into plan-owned device memory (the call returns when the copy is done; lt_plan_destroy frees it),
+ * n_links = 0 is legal and launches nothing, a second call replaces the list.  LT_ERR_INVALID: a boundary of another
+ * kind, a null array, a node or direction out of range, a list out of order.
+ *
+ * After lt_plan_set_links every collide-only and fused one-step launch of the plan (lt_collide, lt_stream_collide,
+ * lt_run, lt_continue, the resident buffers, a captured graph) is followed, on the same stream, by the pass over each
+ * list on the launch's output with its population stride; lt_stream alone gets nothing.  LT_ERR_UNSUPPORTED, each by
+ * name ("... per launch with link bounce-back"): two-step and many-step launches (lt_run keeps one update per
+ * launch, lt_plan_set_two_step / lt_plan_set_many_step(plan, 1) are refused), launches over a range of planes; at
+ * lt_plan_create: 1-D plans, the slab layout, ghost planes.  LT_ERR_INVALID: a launch before every such boundary has
+ * its list.
+ *
+ * lt_apply_links: the pass alone, in place on f_dev (the plan's population stride).
+ * lt_link_force: the momentum-exchange force over the list of one boundary, on POST-STREAMING populations,
+ *   out_dev[c] = sum over the links of e_{q,c} * (f_q(x_s) + f_r(x_f)),   c in logical axis order, 0 beyond d
+ * -- f_q(x_s) left the fluid along the link, f_r(x_f) came back; for d = 1/2 both are equal and this is
+ * lt_boundary_force.  fp64, fixed summation order, no atomics: min(ceil(n_links / 256), LT_LINK_FORCE_BLOCKS) workgroups
+ * write partial_scratch_dev [3][workgroups] (3 * LT_LINK_FORCE_BLOCKS doubles always suffice), one workgroup adds them in
+ * index order.  Two calls on the same input give the same bits; an empty list gives exact zeros. */
+#define LT_LINK_FORCE_BLOCKS 1024
+int lt_plan_set_links(lt_plan *plan, int32_t boundary_index, int64_t n_links, const int32_t *nodes,
+                      const uint8_t *directions, const void *c1, const void *c2, const uint8_t *second_source,
+                      void *stream);
+int lt_apply_links(lt_plan *plan, void *f_dev, void *stream);
+int lt_link_force(lt_plan *plan, int32_t boundary_index, const void *f_dev, double *partial_scratch_dev, double *out_dev,
+                  void *stream);
 
 /* Jacobi solver of the periodic pressure-Poisson equation lap(p) = rhs (lettuce/util/utility.py:119-156, torch_jacobi),
  * without a plan: the fields are dense [shape[0]][shape[1]]([shape[2]]) arrays of `dtype` in C order (the last axis

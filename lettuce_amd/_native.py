@@ -45,6 +45,9 @@ MRT_TRANSFORM_IDS = {"D2Q9Dellar": 1, "D2Q9Lallemand": 2, "D3Q27Hermite": 3}
 # lt_equilibrium_kind, by the kind of a NativeEquilibrium
 EQUILIBRIUM_IDS = {"quadratic": 0, "incompressible": 1}
 BOUNDARY_KINDS = {"bounce_back": 1, "equilibrium": 2, "abb_outlet": 3, "pressure_outlet": 4}
+# ... and the interpolated bounce-back on a link list behind them, a mapping of its own again
+LINK_BOUNDARY_KINDS = {"link_bounce_back": 6}
+LINK_FORCE_BLOCKS = 1024        # LT_LINK_FORCE_BLOCKS: columns of lt_link_force's scratch
 LAYOUT_REFERENCE, LAYOUT_SLAB = 0, 1
 
 
@@ -102,6 +105,9 @@ SYMBOLS = {
     "lt_mass_interior": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "lt_energy_spectrum": (ctypes.c_int, [_vp, _vp, _dbl, _i32, _vp, _vp, _vp]),
     "lt_boundary_force": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lt_plan_set_links": (ctypes.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lt_apply_links": (ctypes.c_int, [_vp, _vp, _vp]),
+    "lt_link_force": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "lt_slab_velocity": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "lt_slab_enstrophy": (ctypes.c_int, [_vp, _vp, _dbl, _dbl, _vp, _vp]),
     "lt_slab_mass_interior": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
@@ -279,7 +285,8 @@ class Plan:
     ``no_collision_mask``): ``{"kind": "bounce_back"}``,
     ``{"kind": "equilibrium", "feq": [q floats] | "field": tensor[q,*res]}``,
     ``{"kind": "abb_outlet", "axis": a, "side": +-1}``,
-    ``{"kind": "pressure_outlet", "axis": a, "side": +-1, "rho_outlet": rho}`` (one-step kernels only).
+    ``{"kind": "pressure_outlet", "axis": a, "side": +-1, "rho_outlet": rho}`` (one-step kernels only),
+    ``{"kind": "link_bounce_back"}`` (interpolated bounce-back; its links: ``set_links``; one-step kernels only).
     """
 
     def __init__(self, stencil: str, dtype: torch.dtype, collision: str,
@@ -334,7 +341,7 @@ class Plan:
     # ------------------------------------------------------------------ helpers
     @_on_device
     def _fill_boundary(self, out: _BoundaryDesc, b: dict, index: int):
-        out.kind = BOUNDARY_KINDS[b["kind"]]
+        out.kind = {**BOUNDARY_KINDS, **LINK_BOUNDARY_KINDS}[b["kind"]]
         out.axis = int(b.get("axis", 0))
         out.side = int(b.get("side", 0))
         out.flags = 0 if b.get("present", True) else 1      # LT_BOUNDARY_ABSENT: another rank holds the outlet plane
@@ -704,6 +711,50 @@ class Plan:
                                                _stream_handle()))
         for t in (solid_u8, scratch):
             t.record_stream(torch.cuda.current_stream())
+        return out[:self.d]
+
+    # ------------------------------------------------------------------ link bounce-back
+    @_on_device
+    def set_links(self, index: int, nodes, directions, c1, c2, second):
+        """The link list of boundary ``index`` (0-based, kind ``link_bounce_back``; lt_plan_set_links): host tensors over
+        the links, sorted by node, then by direction -- ``nodes`` (index of the solid node in C order of the grid),
+        ``directions`` (r in 1 .. q - 1), ``c1`` / ``c2`` in the plan's dtype, ``second`` (0: B = f_q(x_ff), 1: B =
+        f_r(x_f)).  Copied into the plan's device memory before the call returns; an empty list is legal; a second call
+        replaces the list.  Every collide and fused one-step launch is then followed by the pass over the links."""
+        nodes = torch.as_tensor(nodes).detach().cpu().to(torch.int32).contiguous()
+        directions = torch.as_tensor(directions).detach().cpu().to(torch.uint8).contiguous()
+        second = torch.as_tensor(second).detach().cpu().to(torch.uint8).contiguous()
+        c1 = torch.as_tensor(c1).detach().cpu().contiguous()
+        c2 = torch.as_tensor(c2).detach().cpu().contiguous()
+        n = int(nodes.numel())
+        for name, t in (("directions", directions), ("c1", c1), ("c2", c2), ("second", second)):
+            if t.dim() != 1 or int(t.numel()) != n:
+                raise NativeEngineError(f"set_links: {name} has shape {list(t.shape)}, nodes {list(nodes.shape)}")
+        if c1.dtype != self.dtype or c2.dtype != self.dtype:
+            raise NativeEngineError(f"set_links: c1 / c2 of dtype {c1.dtype} / {c2.dtype}, plan dtype {self.dtype}")
+        self._check(self.lib.lt_plan_set_links(self._handle, int(index), n, _ptr(nodes), _ptr(directions), _ptr(c1),
+                                               _ptr(c2), _ptr(second), _stream_handle()))
+        return n
+
+    @_on_device
+    def apply_links(self, f):
+        """the pass over the plan's links alone, in place on the post-collision populations ``f`` (lt_apply_links)"""
+        self._tensor_ok(f, self.f_shape)
+        self._check(self.lib.lt_apply_links(self._handle, _ptr(f), _stream_handle()))
+        return f
+
+    @_on_device
+    def link_force(self, index: int, f):
+        """float64 device tensor [d], logical axis order: the momentum-exchange force on the body of boundary ``index``
+        (0-based) over its link list, sum of e_q (f_q(x_s) + f_r(x_f)) on the populations after streaming
+        (lt_link_force: fp64, fixed summation order)."""
+        self._tensor_ok(f, self.f_shape)
+        scratch = getattr(self, "_link_force_scratch", None)
+        if scratch is None or scratch.device != f.device:
+            scratch = self._link_force_scratch = torch.empty([3, LINK_FORCE_BLOCKS], dtype=torch.float64, device=f.device)
+        out = torch.empty([3], dtype=torch.float64, device=f.device)
+        self._check(self.lib.lt_link_force(self._handle, int(index), _ptr(f), _ptr(scratch), _ptr(out), _stream_handle()))
+        scratch.record_stream(torch.cuda.current_stream())
         return out[:self.d]
 
     @_on_device

@@ -127,6 +127,10 @@ class _NativeStepper:
         if getattr(self.collision, "arithmetic", "exact") != "exact":
             raise NativeEngineError(f"{self.collision.arithmetic!r} arithmetic: the engine has only the reference's "
                                     f"(\"exact\"); fast arithmetic missed its bar (DESIGN.md section 4)")
+        # bodies with link bounce-back: (0-based boundary index, the Boundary); their link lists go to the plan with the
+        # masks (_sync_masks)
+        self._link_bodies = [(i, sim.boundaries[i + 1]) for i, b in enumerate(self.boundaries)
+                             if b.kind == "link_bounce_back"]
         self._mask_state = None
         self._carry = None      # state that allows lt_continue
         self._lazy = None       # (f*, scratch, versions) while flow.f is one streaming pass short
@@ -154,7 +158,8 @@ class _NativeStepper:
 
     def _sync_masks(self):
         sim = self.sim
-        state = (_version(sim.no_collision_mask), _version(sim.no_streaming_mask))
+        state = (_version(sim.no_collision_mask), _version(sim.no_streaming_mask),
+                 tuple((id(body), body._version) for _, body in self._link_bodies))
         if state == self._mask_state:
             return
         if sim.no_collision_mask is None and sim.no_streaming_mask is None:
@@ -162,7 +167,13 @@ class _NativeStepper:
                 raise NativeEngineError("boundaries are present but no_collision_mask is None")
             self.plan.set_masks(None, None)
         else:
+            # the link lists first: what they refuse (a body that touches another boundary) leaves the plan as it was
+            from .ext._boundary import native_link_list
+            lists = [(i, native_link_list(body, i + 1, sim.no_collision_mask, sim.flow.stencil, sim.context.dtype))
+                     for i, body in self._link_bodies]
             self.plan.set_masks(sim.no_collision_mask, self._streaming_mask_full())
+            for i, links in lists:
+                self.plan.set_links(i, *links)
         self._mask_state = state
         self._carry = None
 

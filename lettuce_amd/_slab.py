@@ -456,6 +456,10 @@ class SlabSimulation:
             if not b.native_available():
                 raise LettuceException(f"boundary '{type(b).__name__}' has no engine kernel")
             entry = b.native_generator(i).plan_entry(flow)
+            if entry["kind"] == "link_bounce_back":
+                # its links cross the cuts between the ranks (x_f and x_ff may lie on the neighbour's planes)
+                raise LettuceException(f"boundary '{type(b).__name__}' (link bounce-back) has no slab kernel: the slab "
+                                       f"drivers take the full-way BounceBackBoundary")
             if "field" in entry:
                 # per-node boundary arguments (equilibrium_boundary_pu.py:21-40) were given on the extended
                 # slab like everything else of the flow: cut this rank's planes + ghost planes, z slowest

@@ -54,6 +54,13 @@ bool has_kernel(const Unit &unit, const lt::StepArgs &a) {
   return unit.name(a, lt::NameBuf{name, sizeof name}) != nullptr;
 }
 
+// the units' part links, in the order of kUnits; the 1-D units have none
+typedef int (*LinkFn)(const lt::LinkArgs &);
+const LinkFn kLinkUnits[] = {lt::links_d2q9_f32,  lt::links_d2q9_f64,  lt::links_d3q19_f32, lt::links_d3q19_f64,
+                             lt::links_d3q27_f32, lt::links_d3q27_f64, nullptr,             nullptr,
+                             lt::links_d3q15_f32, lt::links_d3q15_f64};
+static_assert(sizeof kLinkUnits / sizeof kLinkUnits[0] == sizeof kUnits / sizeof kUnits[0], "a row per unit");
+
 constexpr int kReduceBlocks = 1024;
 
 // plain streaming copy, 16 B per lane: the device-copy ceiling the roofline fraction is quoted
@@ -175,6 +182,16 @@ struct lt_plan {
   double *partial = nullptr;
   int n_abb = 0;             // anti-bounce-back outlets of the plan
   int n_pout = 0;            // constant-pressure outlets of the plan (one-step kernels only: multi_step_refusal)
+  // link bounce-back (LT_BOUNDARY_LINK_BOUNCE_BACK): the boundaries of that kind and, per boundary of the plan, its list
+  // in device memory (lt_plan_set_links; `set` also for an empty one)
+  int n_link_kind = 0;
+  struct Links {
+    bool set = false;
+    int n = 0;
+    int *node = nullptr;
+    unsigned char *dir = nullptr, *second = nullptr;
+    void *c1 = nullptr, *c2 = nullptr;
+  } links[LT_MAX_BOUNDARIES];
   int abb_depth = 0;         // how deep an outlet's neighbour must be rebuilt (lt_plan_create)
   int nsm_confined = 1;      // the no-streaming bits are exactly those of the plan's outlet (lt_plan_set_masks)
   int inlet_faces_outlet = 1;  // outlet along a0: every node of the opposite face is an equilibrium node
@@ -269,6 +286,11 @@ int check_boundary(const lt_plan *p, const lt_boundary_desc &b) {
         return fail(LT_ERR_INVALID, "an outlet along the decomposed (z) axis needs >= 2 planes on its rank");
       return LT_OK;
     }
+    case LT_BOUNDARY_LINK_BOUNCE_BACK:
+      if (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
+        return fail(LT_ERR_UNSUPPORTED, "link bounce-back: 2-D / 3-D plans in the reference layout without ghost planes "
+                                        "(no 1-D plan, no slab)");
+      return LT_OK;
     default:
       return fail(LT_ERR_INVALID, "unknown boundary kind %d", b.kind);
   }
@@ -594,6 +616,9 @@ const char *const kIncompressibleMultiStep = "the incompressible equilibrium (lt
                                              "only: no two-step or many-step kernel takes it";
 const char *const kSmagorinskySlabs = "the Smagorinsky collision has the plain two-step sweep of periodic plans only (no "
                                       "edge, packed or signalling launches): slabs keep the one-step kernels";
+// (said with "with" in front of it, like the next one: "two steps per launch with link bounce-back ...")
+const char *const kLinkMultiStep = "link bounce-back (lt_plan_set_links): the pass over the links follows every one-step "
+                                   "launch over the whole field; no two-step, many-step or plane-range launch takes it";
 // (step() says "two steps per launch with" in front of it, the admission "two steps per launch: ")
 const char *const kMaskedTwoStep = "boundaries: at most one anti-bounce-back outlet, at the last plane of the slowest memory "
                                    "axis (periodic plans only) or at an end of the contiguous axis opposite a face of "
@@ -606,6 +631,7 @@ const char *const kMaskedTwoStep = "boundaries: at most one anti-bounce-back out
 const char *multi_step_refusal(const lt_plan *p, int mode) {
   if (mode != lt::kFusedTwice && mode != lt::kFusedMany) return nullptr;
   const bool twice = mode == lt::kFusedTwice;
+  if (p->n_link_kind > 0) return kLinkMultiStep;                       // the one-step kernels and the pass behind them
   // what a body force, TRT and the regularised collision have beside the one-step kernels (unit.inc, parts forced and
   // relaxations): the plain two-step sweep of periodic D3Q19 fp32 plans without masks
   const bool plain_sweep = twice && p->unit.d == 3 && !p->set.masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
@@ -624,6 +650,48 @@ const char *multi_step_refusal(const lt_plan *p, int mode) {
   if (twice && p->set.masked && (!masked_two_step_ok(p) || (p->desc.ghost_planes && p->n_abb > 0 && masked_two_step_axis(p) != 0)))
     return kMaskedTwoStep;
   return nullptr;
+}
+
+// ---- link bounce-back ----
+// has every boundary of that kind its list?  (LT_OK, or the error that names the first without)
+int links_ready(const lt_plan *p) {
+  for (int i = 0; i < p->desc.n_boundaries; ++i)
+    if (p->desc.boundaries[i].kind == LT_BOUNDARY_LINK_BOUNCE_BACK && !p->links[i].set)
+      return fail(LT_ERR_INVALID, "boundary %d is link bounce-back: lt_plan_set_links must give its links first", i);
+  return LT_OK;
+}
+
+lt::LinkArgs link_args(const lt_plan *p, const lt_plan::Links &l, int what, void *f, long long stride, void *stream) {
+  lt::LinkArgs a;
+  memset(&a, 0, sizeof a);
+  a.what = what; a.f = f; a.stride = stride;
+  a.node = l.node; a.dir = l.dir; a.c1 = l.c1; a.c2 = l.c2; a.second = l.second; a.n_links = l.n;
+  a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2;
+  a.stream = static_cast<hipStream_t>(stream);
+  return a;
+}
+
+// The pass over every list of the plan, in place on the post-collision populations f (`stride` elements between its
+// populations), in index order of the boundaries; an empty list launches nothing
+int apply_links(const lt_plan *p, void *f, long long stride, void *stream) {
+  const LinkFn fn = kLinkUnits[2 * p->desc.stencil + p->desc.dtype];
+  for (int i = 0; i < p->desc.n_boundaries; ++i) {
+    const lt_plan::Links &l = p->links[i];
+    if (p->desc.boundaries[i].kind != LT_BOUNDARY_LINK_BOUNCE_BACK || l.n < 1) continue;
+    const int r = fn ? fn(link_args(p, l, 0, f, stride, stream)) : lt::kNoKernel;
+    if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no link kernel for this lattice");
+    if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  }
+  return LT_OK;
+}
+
+void free_links(lt_plan::Links &l) {
+  if (l.node) (void)hipFree(l.node);
+  if (l.dir) (void)hipFree(l.dir);
+  if (l.second) (void)hipFree(l.second);
+  if (l.c1) (void)hipFree(l.c1);
+  if (l.c2) (void)hipFree(l.c2);
+  l = lt_plan::Links();
 }
 
 // One call of step(): what belongs to the launch and not to the plan.  Every entry point builds its own and hands it
@@ -664,7 +732,7 @@ int step(lt_plan *p, const Launch &l) {
   const char *const why = multi_step_refusal(p, mode);
   const bool after_range = why == kSmagorinskySlabs || why == kMaskedTwoStep;
   const auto refuse = [&] {
-    return fail(LT_ERR_UNSUPPORTED, why == kMaskedTwoStep ? "%s per launch with %s" : "%s per launch: %s",
+    return fail(LT_ERR_UNSUPPORTED, why == kMaskedTwoStep || why == kLinkMultiStep ? "%s per launch with %s" : "%s per launch: %s",
                 mode == lt::kFusedMany ? "several steps" : "two steps", why);
   };
   if (why && !after_range) return refuse();
@@ -686,6 +754,13 @@ int step(lt_plan *p, const Launch &l) {
   }
   if (p->desc.n_boundaries > 0 && !p->set.masked)
     return fail(LT_ERR_INVALID, "plan has boundaries but lt_plan_set_masks was not called");
+  // link bounce-back: the pass follows a launch that leaves post-collision populations, over the whole field
+  const bool links = p->n_link_kind > 0 && (mode == lt::kCollideOnly || mode == lt::kFused);
+  if (links) {
+    if (pb != 0 || pe != p->n2 || stride != 1)
+      return fail(LT_ERR_UNSUPPORTED, "a range of planes per launch with %s", kLinkMultiStep);
+    if (const int rc = links_ready(p)) return rc;
+  }
   if (mode != lt::kStreamOnly && p->desc.collision != LT_COLLISION_NONE && !mrt && !(tau > 0.0))
     return fail(LT_ERR_INVALID, "relaxation time tau = %g", tau);
   lt::StepArgs a = kernel_selector(p, mode);
@@ -717,6 +792,7 @@ int step(lt_plan *p, const Launch &l) {
     return fail(LT_ERR_UNSUPPORTED, "no kernel for layout %d collision %d mode %d masked %d",
                 a.layout, a.coll, a.mode, a.masked);
   if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  if (links) return apply_links(p, l.out, a.stride_out > 0 ? a.stride_out : p->N, l.stream);
   return LT_OK;
 }
 
@@ -1224,6 +1300,7 @@ int lt_plan_create(const lt_plan_desc *d, lt_plan **out) {
     if (rc) { delete p; return rc; }
     if (d->boundaries[i].kind == LT_BOUNDARY_ABB_OUTLET) ++n_abb;
     if (d->boundaries[i].kind == LT_BOUNDARY_PRESSURE_OUTLET) ++p->n_pout;
+    if (d->boundaries[i].kind == LT_BOUNDARY_LINK_BOUNCE_BACK) ++p->n_link_kind;
   }
   p->n_abb = n_abb;
   // How deep the kernels must rebuild an outlet's neighbour (neighbour_moments, DEPTH): where the planes of outlets
@@ -1263,6 +1340,7 @@ int lt_plan_destroy(lt_plan *p) {
   if (p->signal_timed_out) (void)hipFree(p->signal_timed_out);
   if (p->partial) (void)hipFree(p->partial);
   for (void *r : p->res) if (r) (void)hipFree(r);
+  for (lt_plan::Links &l : p->links) free_links(l);
   if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
   if (p->gev_in) (void)hipEventDestroy(p->gev_in);
   if (p->gev_out) (void)hipEventDestroy(p->gev_out);
@@ -1476,6 +1554,86 @@ int lt_boundary_force(lt_plan *p, const void *f, const uint8_t *solid, double *p
   a.stream = static_cast<hipStream_t>(s);
   const int r = p->unit.aux(a);
   if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no boundary force kernel");
+  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  return LT_OK;
+}
+
+int lt_plan_set_links(lt_plan *p, int32_t index, int64_t n, const int32_t *nodes, const uint8_t *directions,
+                      const void *c1, const void *c2, const uint8_t *second_source, void *stream) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (index < 0 || index >= p->desc.n_boundaries) return fail(LT_ERR_INVALID, "boundary index %d", index);
+  if (p->desc.boundaries[index].kind != LT_BOUNDARY_LINK_BOUNCE_BACK)
+    return fail(LT_ERR_INVALID, "boundary %d is of kind %d, not link bounce-back", index, p->desc.boundaries[index].kind);
+  if (n < 0 || n >= (1ll << 31)) return fail(LT_ERR_INVALID, "n_links = %lld", (long long)n);
+  if (n > 0 && (!nodes || !directions || !c1 || !c2 || !second_source))
+    return fail(LT_ERR_INVALID, "null nodes / directions / c1 / c2 / second_source");
+  // what the kernels index with: checked here, once, so that they need no bounds of their own
+  for (int64_t i = 0; i < n; ++i) {
+    if (nodes[i] < 0 || nodes[i] >= p->N || directions[i] < 1 || directions[i] >= p->unit.q)
+      return fail(LT_ERR_INVALID, "link %lld: node %d direction %d outside [0, %lld) x [1, %d)", (long long)i, nodes[i],
+                  (int)directions[i], p->N, p->unit.q);
+    if (i > 0 && (nodes[i] < nodes[i - 1] || (nodes[i] == nodes[i - 1] && directions[i] <= directions[i - 1])))
+      return fail(LT_ERR_INVALID, "link %lld: the list must be sorted by node, then by direction, no link twice",
+                  (long long)i);
+  }
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  lt_plan::Links fresh;
+  fresh.set = true;
+  fresh.n = (int)n;
+  if (n > 0) {
+    const size_t count = (size_t)n, esize = (size_t)p->esize;
+    if (hipMalloc((void **)&fresh.node, count * sizeof(int)) != hipSuccess ||
+        hipMalloc((void **)&fresh.dir, count) != hipSuccess || hipMalloc((void **)&fresh.second, count) != hipSuccess ||
+        hipMalloc(&fresh.c1, count * esize) != hipSuccess || hipMalloc(&fresh.c2, count * esize) != hipSuccess) {
+      free_links(fresh);
+      return fail(LT_ERR_ALLOC, "hipMalloc of %lld links failed", (long long)n);
+    }
+    hipError_t e = hipMemcpyAsync(fresh.node, nodes, count * sizeof(int), hipMemcpyHostToDevice, hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.dir, directions, count, hipMemcpyHostToDevice, hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.second, second_source, count, hipMemcpyHostToDevice, hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.c1, c1, count * esize, hipMemcpyHostToDevice, hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.c2, c2, count * esize, hipMemcpyHostToDevice, hs);
+    const hipError_t es = hipStreamSynchronize(hs);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+      free_links(fresh);
+      return fail(LT_ERR_HIP, "copying the links failed: %s", hipGetErrorString(e));
+    }
+  }
+  free_links(p->links[index]);                       // (hipFree waits for the launches that still read the old list)
+  p->links[index] = fresh;
+  if (p->gexec) {                                    // captured with the old list's pointers and length
+    (void)hipGraphExecDestroy(p->gexec);
+    p->gexec = nullptr;
+  }
+  return LT_OK;
+}
+
+int lt_apply_links(lt_plan *p, void *f, void *stream) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (!f) return fail(LT_ERR_INVALID, "null population buffer");
+  if (p->n_link_kind < 1) return fail(LT_ERR_INVALID, "the plan has no link bounce-back boundary");
+  if (const int rc = links_ready(p)) return rc;
+  return apply_links(p, f, pop_stride_of(p), stream);
+}
+
+int lt_link_force(lt_plan *p, int32_t index, const void *f, double *partial_scratch, double *out, void *stream) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (!f || !partial_scratch || !out) return fail(LT_ERR_INVALID, "null populations / scratch / output");
+  if (index < 0 || index >= p->desc.n_boundaries) return fail(LT_ERR_INVALID, "boundary index %d", index);
+  if (p->desc.boundaries[index].kind != LT_BOUNDARY_LINK_BOUNCE_BACK)
+    return fail(LT_ERR_INVALID, "boundary %d is of kind %d, not link bounce-back", index, p->desc.boundaries[index].kind);
+  const lt_plan::Links &l = p->links[index];
+  if (!l.set) return fail(LT_ERR_INVALID, "boundary %d is link bounce-back: lt_plan_set_links must give its links first", index);
+  const LinkFn fn = kLinkUnits[2 * p->desc.stencil + p->desc.dtype];
+  if (!fn) return fail(LT_ERR_UNSUPPORTED, "no link kernel for this lattice");
+  lt::LinkArgs a = link_args(p, l, 1, const_cast<void *>(f), pop_stride_of(p), stream);
+  // fixed launch geometry: a link per thread and pass, at most LT_LINK_FORCE_BLOCKS workgroups of 256
+  const long long blocks = ((long long)l.n + 255) / 256;
+  a.blocks = (int)(blocks < LT_LINK_FORCE_BLOCKS ? blocks : LT_LINK_FORCE_BLOCKS);
+  a.partial = partial_scratch; a.out = out;
+  const int r = fn(a);
+  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no link force kernel");
   if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
   return LT_OK;
 }
@@ -1914,6 +2072,7 @@ int lt_plan_set_many_step(lt_plan *p, int32_t mode) {
   if (mode < -1 || mode > 1) return fail(LT_ERR_INVALID, "many-step mode %d", mode);
   if (mode == 1 && p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: %s", kIncompressibleMultiStep);
+  if (mode == 1 && p->n_link_kind > 0) return fail(LT_ERR_UNSUPPORTED, "several steps per launch with %s", kLinkMultiStep);
   p->many = mode;
   return LT_OK;
 }
@@ -2011,6 +2170,7 @@ int lt_plan_set_two_step(lt_plan *p, int32_t mode, int32_t planes_per_workgroup)
   if (mode == 1 && p->desc.collision == LT_COLLISION_MRT) return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kMrtMultiStep);
   if (mode == 1 && p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
     return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kIncompressibleMultiStep);
+  if (mode == 1 && p->n_link_kind > 0) return fail(LT_ERR_UNSUPPORTED, "two steps per launch with %s", kLinkMultiStep);
   const int sweep = p->unit.d == 2 ? p->n1 : p->n2;          // extent of the sweep axis
   if (planes_per_workgroup < 0 ||
       (planes_per_workgroup > 0 && !p->desc.ghost_planes && sweep % planes_per_workgroup != 0))

@@ -98,6 +98,25 @@ struct AuxArgs {
   hipStream_t stream;
 };
 
+// The link kernels of a plan with link bounce-back (link_bounce.hpp; the units' part links): one compact list of links
+// in plan-owned device memory, c1 / c2 in the plan's scalar type
+struct LinkArgs {
+  int what;              // 0: the bounce-back pass on f, in place; 1: the momentum-exchange force over the list (partial =
+                         // the caller's scratch of 3 x blocks doubles, out = 3 doubles)
+  void *f;               // populations [q][stride]
+  long long stride;      // elements between consecutive populations of f
+  const int *node;
+  const unsigned char *dir;
+  const void *c1, *c2;
+  const unsigned char *second;
+  int n_links;
+  int n0, n1, n2;        // memory extents
+  double *partial;
+  int blocks;            // what 1: workgroups of the first launch (0 for an empty list)
+  double *out;
+  hipStream_t stream;
+};
+
 // Kernel names are written into a buffer of the caller's (lt_plan_kernel_name: the plan's; a probe: a local one).
 // The units' functions take a pointer to one: null launches, non-null only names the kernel the arguments select.
 struct NameBuf {
@@ -139,7 +158,7 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 // on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
 // collision) and outlets (plans with a constant-pressure outlet) and incompressible (the kernels of the incompressible
 // equilibrium), every unit, sweeps and smagorinsky (3-D
-// units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27), spectrum and boundary_force (2-D and 3-D units).  Declared for every unit, defined where the Makefile builds the part.
+// units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27), spectrum, boundary_force and links (2-D and 3-D units).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
   int aux_##tag(const AuxArgs &);                              \
@@ -157,7 +176,8 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
   int incompressible_##tag(const StepArgs &, const NameBuf *); \
   int incompressible_aux_##tag(const AuxArgs &);               \
   int spectrum_##tag(const AuxArgs &);                         \
-  int boundary_force_##tag(const AuxArgs &);
+  int boundary_force_##tag(const AuxArgs &);                   \
+  int links_##tag(const LinkArgs &);
 LT_UNITS(LT_DECLARE_UNIT)
 
 // returns -1 when the combination has no instantiated kernel, else the hipError_t of the launch

@@ -10,6 +10,7 @@
 #include "twostep2d.hpp"
 #include "spectrum.hpp"
 #include "boundary_force.hpp"
+#include "link_bounce.hpp"
 
 #define LT_CAT_(a, b) a##b
 #define LT_CAT(a, b) LT_CAT_(a, b)
@@ -61,6 +62,8 @@
 //                         scalar type and the dimension only -- an object of its own, so that no other object changes
 //   boundary_force (inst14_)  2-D and 3-D units: the two launches of the momentum-exchange force on a bounce-back body
 //                         (boundary_force.hpp) -- an object of its own again
+//   links (inst15_)       2-D and 3-D units: the pass of the interpolated bounce-back over a plan's link list and the two
+//                         launches of the momentum-exchange force over it (link_bounce.hpp) -- an object of its own again
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -76,6 +79,7 @@
 #define LT_PART_incompressible 12
 #define LT_PART_spectrum 13
 #define LT_PART_boundary_force 14
+#define LT_PART_links 15
 #define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
@@ -99,11 +103,11 @@
 #elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 0
-#elif LT_PART_IS(spectrum) || LT_PART_IS(boundary_force)
+#elif LT_PART_IS(spectrum) || LT_PART_IS(boundary_force) || LT_PART_IS(links)
 #define LT_ONE_STEP 0
 #define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible, spectrum or boundary_force"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible, spectrum, boundary_force or links"
 #endif
 #if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
 #error "the MRT collision exists on D2Q9 and D3Q27"
@@ -113,6 +117,9 @@
 #endif
 #if LT_PART_IS(boundary_force) && LT_FIELD(d, LT_UNIT) < 2
 #error "the boundary force kernel exists in 2-D and 3-D"
+#endif
+#if LT_PART_IS(links) && LT_FIELD(d, LT_UNIT) < 2
+#error "the link kernels exist in 2-D and 3-D"
 #endif
 
 namespace lt {
@@ -866,6 +873,26 @@ int LT_CAT(boundary_force_, LT_TAG)(const AuxArgs &a) {
                      static_cast<const T *>(a.f), a.mask, a.N, a.n0, a.n1, a.n2, a.partial);
   hipLaunchKernelGGL((finish_force_kernel<T, S::D>), dim3(1), dim3(kForceThreads), 0, a.stream, a.partial,
                      a.reduce_blocks, a.out);
+  return (int)hipGetLastError();
+}
+#elif LT_PART_IS(links)
+// lt_apply_links and step() (what 0), lt_link_force (what 1): a.f the populations, the list in plan-owned memory
+int LT_CAT(links_, LT_TAG)(const LinkArgs &a) {
+  const LinkList<T> l = {a.node, a.dir, static_cast<const T *>(a.c1), static_cast<const T *>(a.c2), a.second, a.n_links};
+  const LinkTable t = link_table<S>();
+  if (a.what == 0) {
+    if (a.n_links < 1) return 0;
+    const unsigned grid = ((unsigned)a.n_links + kLinkThreads - 1) / kLinkThreads;
+    hipLaunchKernelGGL((link_bounce_kernel<T, S>), dim3(grid), dim3(kLinkThreads), 0, a.stream, static_cast<T *>(a.f),
+                       a.stride, l, a.n0, a.n1, a.n2, t);
+    return (int)hipGetLastError();
+  }
+  if (a.what != 1 || a.blocks < 0 || a.blocks > kLinkMaxBlocks) return kNoKernel;
+  if (a.blocks > 0)
+    hipLaunchKernelGGL((link_force_kernel<T, S>), dim3(a.blocks), dim3(kLinkThreads), 0, a.stream,
+                       static_cast<const T *>(a.f), a.stride, l, a.n0, a.n1, a.n2, t, a.partial);
+  hipLaunchKernelGGL((finish_link_force_kernel<T, S::D>), dim3(1), dim3(kLinkThreads), 0, a.stream, a.partial, a.blocks,
+                     a.out);
   return (int)hipGetLastError();
 }
 #elif LT_PART_IS(mrt_outlets)

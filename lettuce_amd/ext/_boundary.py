@@ -5,19 +5,24 @@ constant-pressure equilibrium outlet that the Obstacle names as the alternative 
 All four live in this one module; ``Simulation`` orders boundaries by ``str(boundary)``,
 i.e. by class path, and the class names alone reproduce the reference's order
 (AntiBounceBackOutlet < BounceBackBoundary < EquilibriumBoundaryPU < EquilibriumOutletP).
+
+``InterpolatedBounceBackBoundary`` and ``HalfwayBounceBackBoundary`` (linear interpolated bounce-back on the links of a
+body; the reference snapshot has neither) sort behind those four, so a body of this kind wins the nodes it shares with
+an inlet or an outlet, as the full-way body does not.
 """
 from typing import List, Optional
 
 import numpy as np
 import torch
 
-from ..util import LettuceException
+from ..util import LettuceException, NativeEngineError
 
 from .._flow import Boundary
 from ..native_desc import NativeBoundary
 from ._collision import BGKCollision
 
-__all__ = ["BounceBackBoundary", "EquilibriumBoundaryPU", "AntiBounceBackOutlet", "EquilibriumOutletP"]
+__all__ = ["BounceBackBoundary", "EquilibriumBoundaryPU", "AntiBounceBackOutlet", "EquilibriumOutletP",
+           "InterpolatedBounceBackBoundary", "HalfwayBounceBackBoundary", "sphere_link_fractions", "native_link_list"]
 
 
 class BounceBackBoundary(Boundary):
@@ -227,3 +232,244 @@ class EquilibriumOutletP(AntiBounceBackOutlet):
 
     def native_generator(self, index: int) -> "NativeBoundary":
         return NativeBoundary("pressure_outlet", index, params=self._engine_params)
+
+
+class _Links:
+    """The compact link list of a body: 1-D tensors over the links, sorted by node, then by direction."""
+
+    __slots__ = ("node", "direction", "opposite", "xf", "xff", "c1", "c2", "second", "b_q", "b_x")
+
+    def to(self, device):
+        out = _Links()
+        for name in self.__slots__:
+            setattr(out, name, getattr(self, name).to(device))
+        return out
+
+    def __len__(self):
+        return int(self.node.numel())
+
+
+def _link_slots(stencil, solid):
+    """bool [q, *res]: slot (r, x_s) is a link slot -- x_s solid, r >= 1 and x_s + e_r (periodic) not solid"""
+    d = stencil.d
+    axes = tuple(range(d))
+    link = torch.zeros([stencil.q, *solid.shape], dtype=torch.bool, device=solid.device)
+    for r in range(1, stencil.q):
+        e = [int(c) for c in stencil.e[r]]
+        link[r] = solid & ~torch.roll(solid, shifts=tuple(-c for c in e), dims=axes)
+    return link
+
+
+class InterpolatedBounceBackBoundary(Boundary):
+    """Linear interpolated bounce-back (Bouzidi, Firdaouss, Lallemand 2001) on the links of a body, in the step order
+    collide -> boundaries -> stream.  Not in the reference snapshot: the definition is this class's torch path.
+
+    A *link slot* is (r, x_s): x_s in ``mask``, r >= 1, x_f = x_s + e_r not in ``mask`` (neighbours wrap periodically, as
+    streaming wraps them).  With q = opposite(r), x_ff = x_f + e_r and d = ``fractions[r, x_s]`` in (0, 1] -- the
+    distance from x_f to the wall along -e_r over |e_r| -- the call returns ``flow.f`` with
+
+        g_r(x_s) = c1 * A + c2 * B,   A = f_q(x_f),
+        d <  1/2:  B = f_q(x_ff),  c1 = 2 d,        c2 = 1 - 2 d
+        d >= 1/2:  B = f_r(x_f),   c1 = 1 / (2 d),  c2 = (2 d - 1) / (2 d)
+
+    on the link slots, read from the collided ``flow.f``; a link whose x_ff is in ``mask`` (a gap one node wide) falls
+    back to d = 1/2 (c1 = 1, c2 = 0).  ``Simulation`` applies the result on the solid nodes, which are not collided, and
+    plain streaming carries slot (r, x_s) to (r, x_f): f_r(x_f, t + 1) is the interpolated reflection of the populations
+    collided at t, without the full-way rule's step of delay.  The other slots of solid nodes never reach the fluid.
+
+    ``fractions``: ``[q, *res]`` (entries that are no link slots are ignored) or None for 1/2 everywhere.  c1, c2 and the
+    choice of B are computed by torch in the context's dtype, once per lattice and dtype, and again after ``mask`` or
+    ``fractions`` was assigned; the expression is two products and a sum, each rounded on its own.  The HIP engine
+    uploads these numbers and reproduces the expression bit for bit (``lt_plan_set_links``)."""
+
+    def __init__(self, mask, fractions=None):
+        self._version = 0
+        self._cache = {}
+        self.mask = mask
+        self.fractions = fractions
+
+    # ---- what the user may assign ----
+    @property
+    def mask(self) -> torch.Tensor:
+        return self._mask
+
+    @mask.setter
+    def mask(self, value):
+        self._mask = torch.as_tensor(value) != 0
+        self._changed()
+
+    @property
+    def fractions(self) -> Optional[torch.Tensor]:
+        return self._fractions
+
+    @fractions.setter
+    def fractions(self, value):
+        self._fractions = None if value is None else torch.as_tensor(value)
+        self._changed()
+
+    def _changed(self):
+        self._version += 1
+        self._cache = {}
+
+    # ---- the link list ----
+    def links(self, stencil, dtype) -> "_Links":
+        """the compact list on the host, c1 / c2 in ``dtype``"""
+        key = (type(stencil).__name__, dtype)
+        if key not in self._cache:
+            self._cache = {key: self._build(stencil, dtype)}
+        return self._cache[key]
+
+    def _build(self, stencil, dtype) -> "_Links":
+        solid = self._mask.detach().cpu()
+        q, d = stencil.q, stencil.d
+        res = list(solid.shape)
+        if len(res) != d:
+            raise LettuceException(f"{type(self).__name__}: a {len(res)}-D mask on a {d}-D lattice")
+        fractions = self._fractions
+        if fractions is not None and list(fractions.shape) != [q] + res:
+            raise LettuceException(f"{type(self).__name__}: fractions of shape {list(fractions.shape)}, expected {[q] + res}")
+        link = _link_slots(stencil, solid)
+        # [nodes, q] in C order of the grid: nonzero() walks it by node, then by direction
+        pairs = link.reshape(q, -1).t().nonzero()
+        node, r = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+        e = torch.as_tensor(np.array(stencil.e), dtype=torch.int64)[r]                  # [n, d]
+        extent = torch.as_tensor(res, dtype=torch.int64)
+        coords = torch.stack(torch.unravel_index(node, res), dim=1) if len(node) else torch.zeros([0, d], dtype=torch.int64)
+        weights = torch.as_tensor([int(np.prod(res[a + 1:])) for a in range(d)], dtype=torch.int64)
+        xf = (((coords + e) % extent) * weights).sum(dim=1)
+        xff = (((coords + 2 * e) % extent) * weights).sum(dim=1)
+        gap = solid.reshape(-1)[xff]
+        if fractions is None:
+            frac = torch.full([len(node)], 0.5, dtype=dtype)
+        else:
+            # gathered where the tensor lives: [q, *res] may be large, the links are few
+            frac = fractions.detach().reshape(q, -1)[r.to(fractions.device), node.to(fractions.device)].cpu()
+            bad = ~((frac > 0) & (frac <= 1))
+            if bool(bad.any()):
+                k = int(bad.nonzero()[0])
+                raise LettuceException(f"{type(self).__name__}: fractions[{int(r[k])}, node {int(node[k])}] = "
+                                       f"{float(frac[k])} on a link; a fraction lies in (0, 1]")
+            frac = frac.to(dtype)
+        frac = torch.where(gap, torch.full_like(frac, 0.5), frac)
+        second = frac >= 0.5
+        two_d = 2 * frac
+        links = _Links()
+        links.node, links.direction = node, r
+        links.opposite = torch.as_tensor(np.array(stencil.opposite), dtype=torch.int64)[r]
+        links.xf, links.xff = xf, xff
+        links.c1 = torch.where(second, 1 / two_d, two_d)
+        links.c2 = torch.where(second, (two_d - 1) / two_d, 1 - two_d)
+        links.second = second
+        links.b_q = torch.where(second, r, links.opposite)
+        links.b_x = torch.where(second, xf, xff)
+        return links
+
+    def _links_on_device(self, stencil, dtype, device) -> "_Links":
+        key = ("device", type(stencil).__name__, dtype, device)
+        if key not in self._cache:
+            self._cache[key] = self.links(stencil, dtype).to(device)
+        return self._cache[key]
+
+    # ---- the Boundary protocol ----
+    def __call__(self, flow: "Flow"):
+        f = flow.f
+        links = self._links_on_device(flow.stencil, f.dtype, f.device)
+        flat = f.reshape(f.shape[0], -1)
+        a = flat[links.opposite, links.xf]
+        b = flat[links.b_q, links.b_x]
+        g = links.c1 * a + links.c2 * b
+        out = f.clone()
+        out.reshape(f.shape[0], -1)[links.direction, links.node] = g
+        return out
+
+    def make_no_streaming_mask(self, shape: List[int], context: "Context") -> Optional[torch.Tensor]:
+        return None
+
+    def make_no_collision_mask(self, shape: List[int], context: "Context") -> Optional[torch.Tensor]:
+        return self._mask.to(context.device)
+
+    def native_available(self) -> bool:
+        return True
+
+    def native_generator(self, index: int) -> "NativeBoundary":
+        return NativeBoundary("link_bounce_back", index)
+
+
+class HalfwayBounceBackBoundary(InterpolatedBounceBackBoundary):
+    """Half-way bounce-back: the interpolated rule with every fraction 1/2, f_r(x_f, t + 1) = f*_q(x_f, t) on every
+    link.  The wall stands half a link from the nearest fluid node, as with the full-way ``BounceBackBoundary``, but
+    the reflection takes no extra step."""
+
+    def __init__(self, mask):
+        super().__init__(mask, None)
+
+
+def native_link_list(boundary, index: int, no_collision_mask, stencil, dtype):
+    """The link list of ``boundary`` as the HIP engine takes it (``Plan.set_links``): host tensors ``(nodes int32,
+    directions uint8, c1, c2, second uint8)``, sorted by node index (C order of the grid), then by direction.
+
+    From masks alone it refuses, by name, what the engine's pass after the stepping kernel would not compute as the torch
+    path does: nodes of the body's mask that a boundary of a higher index took over (they do not reflect), nodes with
+    this index outside the mask, and a link whose x_f or x_ff belongs to another boundary (the torch path reads what
+    that boundary wrote before or after, depending on the sort order).  With the body clear of other boundaries the
+    pass reads collided fluid nodes only."""
+    ncm = torch.as_tensor(no_collision_mask).detach().cpu()
+    own = ncm == index
+    solid = boundary.mask.detach().cpu()
+    name = type(boundary).__name__
+    if list(own.shape) != list(solid.shape):
+        raise NativeEngineError(f"{name}: mask of shape {list(solid.shape)} on a grid {list(own.shape)}")
+    if bool((solid & ~own).any()):
+        raise NativeEngineError(f"{name} (index {index}): {int((solid & ~own).sum())} nodes of its mask belong to a boundary "
+                                f"of a higher index in no_collision_mask; the HIP engine's link pass has no such body")
+    if bool((own & ~solid).any()):
+        raise NativeEngineError(f"{name} (index {index}): no_collision_mask holds its index on {int((own & ~solid).sum())} "
+                                f"nodes outside its mask; the HIP engine's link pass has no such body")
+    links = boundary.links(stencil, dtype)
+    flat = ncm.reshape(-1)
+    foreign = (flat[links.xf] != 0) | ((flat[links.xff] != 0) & (flat[links.xff] != index))
+    if bool(foreign.any()):
+        k = int(foreign.nonzero()[0])
+        raise NativeEngineError(f"{name} (index {index}): the link from node {int(links.node[k])} along direction "
+                                f"{int(links.direction[k])} reads a node of another boundary ({int(foreign.sum())} such "
+                                f"links); the HIP engine's link pass needs the body clear of other boundaries")
+    return (links.node.to(torch.int32).contiguous(), links.direction.to(torch.uint8).contiguous(),
+            links.c1.contiguous(), links.c2.contiguous(), links.second.to(torch.uint8).contiguous())
+
+
+def sphere_link_fractions(stencil, grid, center, radius, mask=None):
+    """Fractions ``[q, *res]`` (fp64) for a circle / sphere of ``radius`` around ``center``: on each link from a node x_s
+    of ``mask`` (default: the nodes inside) to x_f = x_s + e_r, the first root t in (0, 1] of
+    |x_f - t e_r dx - center| = radius -- the distance from x_f to the surface along -e_r over the link's length.
+    ``grid``: the coordinate tensors of the nodes (``flow.grid``), uniformly spaced.  A link without such a root, and
+    every entry that is no link slot, gets 1/2.  Computed, and returned, on the device of ``grid``."""
+    d = stencil.d
+    grid = [torch.as_tensor(g).detach().double() for g in grid]
+    device = grid[0].device
+    res = list(grid[0].shape)
+    dx = []
+    for a in range(d):
+        if res[a] < 2:
+            dx.append(1.0)
+        else:
+            first = [0] * d
+            second = [0] * d
+            second[a] = 1
+            dx.append(float(grid[a][tuple(second)] - grid[a][tuple(first)]))
+    inside = sum((grid[a] - float(center[a])) ** 2 for a in range(d)) < float(radius) ** 2
+    solid = inside if mask is None else (torch.as_tensor(mask).detach().to(device) != 0)
+    link = _link_slots(stencil, solid)
+    out = torch.full([stencil.q, *res], 0.5, dtype=torch.float64, device=device)
+    for r in range(1, stencil.q):
+        e = [int(c) for c in stencil.e[r]]
+        # w = x_f - center (geometric, no wrap), v = -e_r dx:  |w + t v|^2 = R^2
+        w = [grid[a] + e[a] * dx[a] - float(center[a]) for a in range(d)]
+        v = [-e[a] * dx[a] for a in range(d)]
+        qa = sum(c * c for c in v)
+        qb = sum(w[a] * v[a] for a in range(d))
+        qc = sum(c * c for c in w) - float(radius) ** 2
+        disc = qb * qb - qa * qc
+        t = (-qb - torch.sqrt(disc.clamp(min=0))) / qa
+        ok = link[r] & (disc >= 0) & (t > 0) & (t <= 1)
+        out[r] = torch.where(ok, t, out[r])
+    return out

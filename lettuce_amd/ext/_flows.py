@@ -160,13 +160,19 @@ class Obstacle(ExtFlow):
     >>> flow = Obstacle(context, [101, 51], 100, 0.1, domain_length_x=10.1, stencil=D2Q9)
     >>> x, y = flow.grid
     >>> flow.mask = ((x - 2.5) ** 2 + (y - 2.5) ** 2) < 1.
+
+    ``solid_boundary`` (keyword only, not in the reference): a callable mask -> Boundary for the body, for instance
+    ``lt.HalfwayBounceBackBoundary``; None keeps ``BounceBackBoundary(mask)``.
     """
 
     def __init__(self, context: "Context", resolution: Union[int, List[int]], reynolds_number,
                  mach_number, domain_length_x, char_length=1, char_velocity=1,
                  stencil: Optional["Stencil"] = None, equilibrium: Optional["Equilibrium"] = None,
-                 slab: Optional["ZSlab"] = None):
+                 slab: Optional["ZSlab"] = None, *, solid_boundary=None):
         self.slab = slab          # multi-GPU extension, not in the reference (see _slab.py)
+        # the boundary of the body: a callable mask -> Boundary, e.g. HalfwayBounceBackBoundary or
+        # lambda mask: InterpolatedBounceBackBoundary(mask, fractions); None: the full-way BounceBackBoundary
+        self.solid_boundary = solid_boundary
         self.char_length_lu = resolution[0] / domain_length_x * char_length
         self.char_length = char_length
         self.char_velocity = char_velocity
@@ -217,7 +223,7 @@ class Obstacle(ExtFlow):
         return [EquilibriumBoundaryPU(context=self.context, mask=torch.abs(x) < 1e-6,
                                       velocity=inlet_velocity),
                 AntiBounceBackOutlet(self._unit_vector().tolist(), self),
-                BounceBackBoundary(self.mask)]
+                BounceBackBoundary(self.mask) if self.solid_boundary is None else self.solid_boundary(self.mask)]
 
     def _unit_vector(self, i=0):
         return torch.eye(self.stencil.d)[i]

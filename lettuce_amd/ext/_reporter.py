@@ -24,6 +24,7 @@ from .._errors import LettuceException
 from .._native import SPECTRUM_MAX_BINS
 from .._simulation import Reporter
 from ..util import torch_gradient
+from ._boundary import InterpolatedBounceBackBoundary
 
 __all__ = ["Observable", "ObservableReporter", "MaximumVelocity", "IncompressibleKineticEnergy",
            "Enstrophy", "EnergySpectrum", "Mass", "BoundaryForce", "DragCoefficient", "LiftCoefficient",
@@ -203,6 +204,22 @@ def momentum_exchange(stencil, f, solid):
     return total
 
 
+def link_momentum_exchange(stencil, f, links):
+    """The torch expression of ``BoundaryForce`` on a body with link bounce-back: fp64 ``[d]``,
+
+        F_c = sum over the links (r, x_s), q = opposite(r), of e_{q,c} (f_q(x_s) + f_r(x_f)),
+
+    on post-streaming populations ``f`` [q, *res]: f_q(x_s) left the fluid along the link during the last streaming
+    step, f_r(x_f) is the interpolated reflection that came back.  ``links``: the body's compact list
+    (``InterpolatedBounceBackBoundary.links``) on the device of ``f``.  With every fraction 1/2 both terms are equal and
+    this is ``momentum_exchange``."""
+    flat = f.reshape(f.shape[0], -1)
+    left = flat[links.opposite, links.node].to(torch.float64)
+    back = flat[links.direction, links.xf].to(torch.float64)
+    e = torch.as_tensor(np.array(stencil.e), dtype=torch.float64, device=f.device)[links.opposite]
+    return (e * (left + back)[:, None]).sum(dim=0)
+
+
 class BoundaryForce(Observable):
     """The force the fluid exerts on a body of full-way bounce-back nodes, per time step, in lattice units, by momentum
     exchange: ``[d]`` values in the context dtype,
@@ -217,11 +234,18 @@ class BoundaryForce(Observable):
     boundary of a higher index win on some of the body's nodes, those nodes do not bounce back: pass
     ``simulation.no_collision_mask == index`` instead.  On a native context one masked reduction on the device
     (``lt_boundary_force``: fp64, fixed order); elsewhere, and for D1Q3, one ``torch.roll`` of the mask per q and
-    sums in fp64.  Needs the whole field: not ``slab_aware``, a slab simulation refuses it by name."""
+    sums in fp64.  Needs the whole field: not ``slab_aware``, a slab simulation refuses it by name.
+
+    Given an ``InterpolatedBounceBackBoundary`` (or ``HalfwayBounceBackBoundary``) the sum runs over that body's links
+    with both populations of a link, F_c = sum e_{q,c} (f_q(x_s) + f_r(x_f)) (``link_momentum_exchange``): what left the
+    fluid and what the interpolation sent back.  On a native context ``lt_link_force`` over the same list the engine
+    steps with; the boundary's ``mask`` and ``fractions`` are read again whenever they were assigned."""
 
     def __init__(self, flow: "Flow", boundary):
         super().__init__(flow)
         self._solid = None
+        self._body = boundary if isinstance(boundary, InterpolatedBounceBackBoundary) else None
+        self._link_plan = None      # (body version, device, Plan holding the body's links)
         self.mask = boundary if isinstance(boundary, (torch.Tensor, np.ndarray)) else getattr(boundary, "_mask", boundary)
 
     @property
@@ -245,10 +269,27 @@ class BoundaryForce(Observable):
         flow = self.flow
         f = flow.f if f is None else f
         d = flow.stencil.d
+        if self._body is not None:
+            return self._link_force(f)
         plan = flow._engine_plan(f) if (d >= 2 and self._solid.device == f.device) else None
         if plan is not None:
             return plan.boundary_force(f, self._solid)
         return momentum_exchange(flow.stencil, f, self._solid.to(f.device) != 0)
+
+    def _link_force(self, f: torch.Tensor) -> torch.Tensor:
+        """the force on a body with link bounce-back: lt_link_force on a native context, else the torch expression"""
+        flow, body = self.flow, self._body
+        if flow.stencil.d >= 2 and flow._engine_plan(f) is not None:
+            from .._native import Plan
+            key = (body._version, f.device)
+            if self._link_plan is None or self._link_plan[0] != key:
+                links = body.links(flow.stencil, f.dtype)
+                plan = Plan(type(flow.stencil).__name__, f.dtype, "none", flow.resolution, [{"kind": "link_bounce_back"}],
+                            device=f.device)
+                plan.set_links(0, links.node, links.direction, links.c1, links.c2, links.second)
+                self._link_plan = (key, plan)
+            return self._link_plan[1].link_force(0, f)
+        return link_momentum_exchange(flow.stencil, f, body._links_on_device(flow.stencil, f.dtype, f.device))
 
     def __call__(self, f: Optional[torch.Tensor] = None):
         return self.force(f).to(self.context.dtype)

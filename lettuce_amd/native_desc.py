@@ -68,8 +68,8 @@ class NativeCollision:
 
 @dataclass
 class NativeBoundary:
-    kind: str                                  # 'bounce_back' | 'equilibrium' | 'abb_outlet' | 'pressure_outlet'
-    index: int
+    kind: str                                  # 'bounce_back' | 'equilibrium' | 'abb_outlet' | 'pressure_outlet' |
+    index: int                                 # 'link_bounce_back' (its link list goes to the plan apart: Plan.set_links)
     # engine parameters of this boundary for a given flow (dict for lettuce_amd._native.Plan)
     params: Optional[Callable[["Flow"], dict]] = None
 
