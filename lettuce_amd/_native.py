@@ -230,6 +230,11 @@ def _on_device(method):
     return wrapper
 
 
+def _f64_out(like: torch.Tensor, *shape: int) -> torch.Tensor:
+    """the float64 device tensor an observable writes: 0-d, or of ``shape``, on the device of ``like``"""
+    return torch.empty(shape, dtype=torch.float64, device=like.device)
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
@@ -316,7 +321,7 @@ class Plan:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._keepalive = {}            # boundary index -> field tensor the engine holds a pointer to
         self._const = {}                # answers of the engine that do not change while the masks stay
-        self._force_scratch = None      # lt_boundary_force's partial sums, allocated on first use
+        self._scratch = {}              # (name, device) -> the partial sums of an observable, allocated on first use
         self.resident_mode = -1         # lt_plan_set_resident: -1 automatic, 0 off, 1 requested
         self.pop_stride = 0             # elements between populations of the caller's buffers (0 = dense)
         desc = _PlanDesc()
@@ -606,6 +611,13 @@ class Plan:
     def resident_free(self):
         self._check(self.lib.lt_resident_free(self._handle))
 
+    def _partials(self, name, blocks, device):
+        """the [3, blocks] float64 scratch of the force observable ``name``, kept on the plan per device"""
+        scratch = self._scratch.get((name, device))
+        if scratch is None:
+            scratch = self._scratch[name, device] = torch.empty([3, blocks], dtype=torch.float64, device=device)
+        return scratch
+
     @_on_device
     def macroscopic(self, f, want_rho=True, want_u=True):
         self._tensor_ok(f, self.f_shape)
@@ -628,14 +640,14 @@ class Plan:
     def kinetic_energy_lu(self, f):
         """0-d float64 device tensor: sum over nodes of 0.5 u.u (lattice units)."""
         self._tensor_ok(f, self.f_shape)
-        out = torch.empty((), dtype=torch.float64, device=f.device)
+        out = _f64_out(f)
         self._check(self.lib.lt_kinetic_energy(self._handle, _ptr(f), _ptr(out), _stream_handle()))
         return out
 
     @_on_device
     def mass(self, f):
         self._tensor_ok(f, self.f_shape)
-        out = torch.empty((), dtype=torch.float64, device=f.device)
+        out = _f64_out(f)
         self._check(self.lib.lt_mass(self._handle, _ptr(f), _ptr(out), _stream_handle()))
         return out
 
@@ -643,7 +655,7 @@ class Plan:
     def max_velocity_lu(self, f):
         """0-d float64 device tensor: max over nodes of |u| (lattice units)"""
         self._tensor_ok(f, self.f_shape)
-        out = torch.empty((), dtype=torch.float64, device=f.device)
+        out = _f64_out(f)
         self._check(self.lib.lt_max_velocity(self._handle, _ptr(f), _ptr(out), _stream_handle()))
         return out
 
@@ -667,7 +679,7 @@ class Plan:
         differences times inv_dx); one [d, *res] scratch field for u, nothing else is materialised."""
         self._tensor_ok(f, self.f_shape)
         scratch = torch.empty([self.d] + self.f_shape[1:], dtype=self.dtype, device=f.device)
-        out = torch.empty((), dtype=torch.float64, device=f.device)
+        out = _f64_out(f)
         self._check(self.lib.lt_enstrophy(self._handle, _ptr(f), _ptr(scratch), float(u_scale), float(inv_dx),
                                           _ptr(out), _stream_handle()))
         scratch.record_stream(torch.cuda.current_stream())
@@ -684,7 +696,7 @@ class Plan:
         self._tensor_ok(uhat, [self.d] + self.f_shape[1:] + [2])
         n_bins = int(n_bins)
         scratch = torch.empty([SPECTRUM_BLOCKS, max(n_bins, 1)], dtype=torch.float64, device=uhat.device)
-        out = torch.empty([max(n_bins, 1)], dtype=torch.float64, device=uhat.device)
+        out = _f64_out(uhat, max(n_bins, 1))
         self._check(self.lib.lt_energy_spectrum(self._handle, _ptr(uhat), float(scale), n_bins, _ptr(scratch),
                                                 _ptr(out), _stream_handle()))
         for t in (uhat, scratch):
@@ -703,10 +715,8 @@ class Plan:
                 or list(solid_u8.shape) != list(grid)):
             raise NativeEngineError(f"solid mask: need a contiguous uint8 tensor {list(grid)} on {f.device}, got "
                                     f"{list(solid_u8.shape)} {solid_u8.dtype} on {solid_u8.device}")
-        scratch = self._force_scratch
-        if scratch is None or scratch.device != f.device:
-            scratch = self._force_scratch = torch.empty([3, BOUNDARY_FORCE_BLOCKS], dtype=torch.float64, device=f.device)
-        out = torch.empty([3], dtype=torch.float64, device=f.device)
+        scratch = self._partials("boundary_force", BOUNDARY_FORCE_BLOCKS, f.device)
+        out = _f64_out(f, 3)
         self._check(self.lib.lt_boundary_force(self._handle, _ptr(f), _ptr(solid_u8), _ptr(scratch), _ptr(out),
                                                _stream_handle()))
         for t in (solid_u8, scratch):
@@ -749,10 +759,8 @@ class Plan:
         (0-based) over its link list, sum of e_q (f_q(x_s) + f_r(x_f)) on the populations after streaming
         (lt_link_force: fp64, fixed summation order)."""
         self._tensor_ok(f, self.f_shape)
-        scratch = getattr(self, "_link_force_scratch", None)
-        if scratch is None or scratch.device != f.device:
-            scratch = self._link_force_scratch = torch.empty([3, LINK_FORCE_BLOCKS], dtype=torch.float64, device=f.device)
-        out = torch.empty([3], dtype=torch.float64, device=f.device)
+        scratch = self._partials("link_force", LINK_FORCE_BLOCKS, f.device)
+        out = _f64_out(f, 3)
         self._check(self.lib.lt_link_force(self._handle, int(index), _ptr(f), _ptr(scratch), _ptr(out), _stream_handle()))
         scratch.record_stream(torch.cuda.current_stream())
         return out[:self.d]
@@ -765,7 +773,7 @@ class Plan:
         mask = None
         if no_mass_mask is not None:
             mask = torch.broadcast_to(no_mass_mask, self.f_shape[1:]).to(device=f.device, dtype=torch.uint8).contiguous()
-        out = torch.empty((), dtype=torch.float64, device=f.device)
+        out = _f64_out(f)
         self._check(self.lib.lt_mass_interior(self._handle, _ptr(f), _ptr(mask), _ptr(out), _stream_handle()))
         if mask is not None:
             mask.record_stream(torch.cuda.current_stream())
@@ -787,7 +795,7 @@ class Plan:
         """0-d float64 device tensor: sum over this rank's own nodes of |curl(u_scale * u)|^2"""
         nx, ny, nz = self.resolution
         self._tensor_ok(u_ext, [3, nz + 6, ny, nx])
-        out = torch.empty((), dtype=torch.float64, device=u_ext.device)
+        out = _f64_out(u_ext)
         self._check(self.lib.lt_slab_enstrophy(self._handle, _ptr(u_ext), float(u_scale), float(inv_dx), _ptr(out),
                                                _stream_handle()))
         u_ext.record_stream(torch.cuda.current_stream())
@@ -802,7 +810,7 @@ class Plan:
             if list(no_mass_mask.shape) != self.f_shape[1:]:
                 raise NativeEngineError(f"no_mass_mask shape {list(no_mass_mask.shape)}, expected {self.f_shape[1:]}")
             mask = no_mass_mask.to(device=f.device, dtype=torch.uint8).contiguous()
-        out = torch.empty((), dtype=torch.float64, device=f.device)
+        out = _f64_out(f)
         self._check(self.lib.lt_slab_mass_interior(self._handle, _ptr(f), _ptr(mask), int(z_begin), int(nz_global),
                                                    _ptr(out), _stream_handle()))
         if mask is not None:

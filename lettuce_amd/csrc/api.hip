@@ -28,6 +28,17 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
+// What a unit's launcher returned: kNoKernel is LT_ERR_UNSUPPORTED with the caller's text, a hipError_t LT_ERR_HIP
+int launched(int r, const char *no_kernel_fmt, ...) {
+  if (r == 0) return LT_OK;
+  if (r != lt::kNoKernel) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  va_list ap;
+  va_start(ap, no_kernel_fmt);
+  vsnprintf(g_error, sizeof g_error, no_kernel_fmt, ap);
+  va_end(ap);
+  return LT_ERR_UNSUPPORTED;
+}
+
 #define LT_HIP(call)                                                                   \
   do {                                                                                 \
     hipError_t e_ = (call);                                                            \
@@ -661,7 +672,7 @@ int links_ready(const lt_plan *p) {
   return LT_OK;
 }
 
-lt::LinkArgs link_args(const lt_plan *p, const lt_plan::Links &l, int what, void *f, long long stride, void *stream) {
+lt::LinkArgs link_args(const lt_plan *p, const lt_plan::Links &l, lt::LinkKind what, void *f, long long stride, void *stream) {
   lt::LinkArgs a;
   memset(&a, 0, sizeof a);
   a.what = what; a.f = f; a.stride = stride;
@@ -678,9 +689,8 @@ int apply_links(const lt_plan *p, void *f, long long stride, void *stream) {
   for (int i = 0; i < p->desc.n_boundaries; ++i) {
     const lt_plan::Links &l = p->links[i];
     if (p->desc.boundaries[i].kind != LT_BOUNDARY_LINK_BOUNCE_BACK || l.n < 1) continue;
-    const int r = fn ? fn(link_args(p, l, 0, f, stride, stream)) : lt::kNoKernel;
-    if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no link kernel for this lattice");
-    if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+    const int r = fn ? fn(link_args(p, l, lt::kLinkBounce, f, stride, stream)) : lt::kNoKernel;
+    if (const int rc = launched(r, "no link kernel for this lattice")) return rc;
   }
   return LT_OK;
 }
@@ -787,11 +797,9 @@ int step(lt_plan *p, const Launch &l) {
     a.planes2 = (int)(l.end2 - l.begin2);
     if (a.planes2 > 0) a.pack_hi_plane = (int)l.end2 - 1;   // upper message: last plane of the second range
   }
-  const int r = p->unit.step(a);
-  if (r == lt::kNoKernel)
-    return fail(LT_ERR_UNSUPPORTED, "no kernel for layout %d collision %d mode %d masked %d",
-                a.layout, a.coll, a.mode, a.masked);
-  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  if (const int rc = launched(p->unit.step(a), "no kernel for layout %d collision %d mode %d masked %d", a.layout, a.coll,
+                              a.mode, a.masked))
+    return rc;
   if (links) return apply_links(p, l.out, a.stride_out > 0 ? a.stride_out : p->N, l.stream);
   return LT_OK;
 }
@@ -1136,33 +1144,46 @@ int run(lt_plan *p, bool from_fstar, void *a, void *b, double tau, long long n, 
   return LT_OK;
 }
 
-int aux(lt_plan *p, int what, const void *f, void *rho, void *u, double *out, void *stream,
-        double scale = 1.0, double inv_dx = 1.0, const unsigned char *mask = nullptr, long long u_stride = 0,
-        int z_begin = 0, int nz_global = 0) {
-  if (!p) return fail(LT_ERR_INVALID, "null plan");
-  if (!f && what != 8) return fail(LT_ERR_INVALID, "null population buffer");
+// An auxiliary launch starts from the fields the plan decides: layout, N, extents, stride, the interior planes' node
+// range, the plan's scratch, equilibrium, stream.  The entry point then sets what is its own by name.  (A null plan
+// leaves them zero: aux() refuses it.)
+lt::AuxArgs aux_args(const lt_plan *p, lt::AuxKind what, void *stream) {
   lt::AuxArgs a;
   memset(&a, 0, sizeof a);
-  a.what = what; a.layout = p->desc.layout;
-  a.f = f; a.rho = rho; a.u = u;
+  a.what = what;
+  if (!p) return a;
+  a.layout = p->desc.layout;
   a.N = p->N;
   a.stride = pop_stride_of(p);
-  a.u_stride = u_stride; a.z_begin = z_begin; a.nz_global = nz_global;
-  if (a.stride != a.N && what != 0 && what != 2 && what != 3 && what != 4 && what != 8 && what != 9)
-    return fail(LT_ERR_UNSUPPORTED, "auxiliary kernel %d reads dense population buffers only (the plan has a "
-                                    "population stride of %lld)", what, a.stride);
   const long long plane = (long long)p->n0 * p->n1;
   a.first = plane * p->interior_begin;
   a.count = plane * (p->interior_end - p->interior_begin);
-  a.partial = p->partial; a.reduce_blocks = kReduceBlocks; a.out = out;
-  a.n0 = p->n0; a.n1 = p->n1; a.n2 = what == 8 ? (p->interior_end - p->interior_begin) + 6 : p->n2;
-  a.scale = scale; a.inv_dx = inv_dx; a.mask = mask;
+  a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2;
+  a.partial = p->partial; a.reduce_blocks = kReduceBlocks;
   a.equilibrium = p->set.equilibrium; a.rho0 = p->set.rho0;
   a.stream = static_cast<hipStream_t>(stream);
-  const int r = p->unit.aux(a);
-  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no auxiliary kernel %d", what);
-  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  return a;
+}
+
+// The refusal of the kinds that exist for whole grids only (dispatch.hpp, kAuxTraits).  The entry point of such a kind
+// asks once, where its refusals always had this one: before the checks of its own arguments.  A null plan is left to
+// aux().
+int whole_grid_only(const lt_plan *p, lt::AuxKind what) {
+  const lt::AuxTraits &kind = lt::kAuxTraits[what];
+  if (p && kind.whole_grid && (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes))
+    return fail(LT_ERR_UNSUPPORTED, "%s: 2-D / 3-D grids in the reference layout without ghost planes", kind.name);
   return LT_OK;
+}
+
+// the checks every kind shares, what kAuxTraits says of the population stride, then the launch
+int aux(lt_plan *p, const lt::AuxArgs &a) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  const lt::AuxTraits &kind = lt::kAuxTraits[a.what];
+  if (!a.f && a.what != lt::kAuxSlabEnstrophy) return fail(LT_ERR_INVALID, "null population buffer");
+  if (a.stride != a.N && !kind.strided)
+    return fail(LT_ERR_UNSUPPORTED, "%s: reads dense population buffers only (the plan has a population stride of %lld)",
+                kind.name, a.stride);
+  return launched(p->unit.aux(a), "no %s kernel", kind.name);
 }
 
 // The admission tests of the masked two-step kernels (compile_masks_kernel) for the plan's present boundary table:
@@ -1466,60 +1487,67 @@ int lt_continue(lt_plan *p, void *a, void *b, double tau, int64_t n, void *s, in
 
 int lt_macroscopic(lt_plan *p, const void *f, void *rho, void *u, void *s) {
   if (!rho && !u) return fail(LT_ERR_INVALID, "both outputs null");
-  return aux(p, 0, f, rho, u, nullptr, s);
+  lt::AuxArgs a = aux_args(p, lt::kAuxMacroscopic, s);
+  a.f = f; a.rho = rho; a.u = u;
+  return aux(p, a);
 }
 int lt_equilibrium(lt_plan *p, const void *rho, const void *u, void *feq, void *s) {
   if (!rho || !u) return fail(LT_ERR_INVALID, "null rho/u");
-  return aux(p, 1, feq, const_cast<void *>(rho), const_cast<void *>(u), nullptr, s);
+  lt::AuxArgs a = aux_args(p, lt::kAuxEquilibrium, s);
+  a.f = feq; a.rho = const_cast<void *>(rho); a.u = const_cast<void *>(u);
+  return aux(p, a);
 }
-int lt_kinetic_energy(lt_plan *p, const void *f, double *out, void *s) {
+
+namespace {
+// the three reductions of the populations over the interior planes into one device scalar
+int reduce(lt_plan *p, lt::AuxKind what, const void *f, double *out, void *s) {
   if (!out) return fail(LT_ERR_INVALID, "null output");
-  return aux(p, 2, f, nullptr, nullptr, out, s);
+  lt::AuxArgs a = aux_args(p, what, s);
+  a.f = f; a.out = out;
+  return aux(p, a);
 }
-int lt_mass(lt_plan *p, const void *f, double *out, void *s) {
-  if (!out) return fail(LT_ERR_INVALID, "null output");
-  return aux(p, 3, f, nullptr, nullptr, out, s);
-}
-int lt_max_velocity(lt_plan *p, const void *f, double *out, void *s) {
-  if (!out) return fail(LT_ERR_INVALID, "null output");
-  return aux(p, 4, f, nullptr, nullptr, out, s);
-}
+}  // namespace
+int lt_kinetic_energy(lt_plan *p, const void *f, double *out, void *s) { return reduce(p, lt::kAuxKineticEnergy, f, out, s); }
+int lt_mass(lt_plan *p, const void *f, double *out, void *s) { return reduce(p, lt::kAuxMass, f, out, s); }
+int lt_max_velocity(lt_plan *p, const void *f, double *out, void *s) { return reduce(p, lt::kAuxMaxVelocity, f, out, s); }
 
 int lt_init_fneq(lt_plan *p, const void *rho, const void *u, double tau, double identity_cs2, void *f, void *s) {
   if (!rho || !u) return fail(LT_ERR_INVALID, "null rho/u");
-  if (p && (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes))
-    return fail(LT_ERR_UNSUPPORTED, "f_neq initialisation: 2-D / 3-D grids in the reference layout");
+  if (const int rc = whole_grid_only(p, lt::kAuxFneq)) return rc;
   if (!(tau > 0.0)) return fail(LT_ERR_INVALID, "relaxation time tau = %g", tau);
-  return aux(p, 7, f, const_cast<void *>(rho), const_cast<void *>(u), nullptr, s, tau, identity_cs2);
+  lt::AuxArgs a = aux_args(p, lt::kAuxFneq, s);
+  a.f = f; a.rho = const_cast<void *>(rho); a.u = const_cast<void *>(u);
+  a.scale = tau; a.inv_dx = identity_cs2;
+  return aux(p, a);
 }
 int lt_enstrophy(lt_plan *p, const void *f, void *u_scratch, double u_scale, double inv_dx, double *out, void *s) {
   if (!out || !u_scratch) return fail(LT_ERR_INVALID, "null output / scratch");
-  if (p && (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes))
-    return fail(LT_ERR_UNSUPPORTED, "enstrophy: 2-D / 3-D periodic grids in the reference layout");
-  return aux(p, 5, f, nullptr, u_scratch, out, s, u_scale, inv_dx);
+  if (const int rc = whole_grid_only(p, lt::kAuxEnstrophy)) return rc;
+  lt::AuxArgs a = aux_args(p, lt::kAuxEnstrophy, s);
+  a.f = f; a.u = u_scratch; a.out = out;
+  a.scale = u_scale; a.inv_dx = inv_dx;
+  return aux(p, a);
 }
 int lt_mass_interior(lt_plan *p, const void *f, const uint8_t *mask, double *out, void *s) {
   if (!out) return fail(LT_ERR_INVALID, "null output");
-  if (p && (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes))
-    return fail(LT_ERR_UNSUPPORTED, "interior mass: 2-D / 3-D grids in the reference layout");
-  return aux(p, 6, f, nullptr, nullptr, out, s, 1.0, 1.0, mask);
+  if (const int rc = whole_grid_only(p, lt::kAuxInteriorMass)) return rc;
+  lt::AuxArgs a = aux_args(p, lt::kAuxInteriorMass, s);
+  a.f = f; a.mask = mask; a.out = out;
+  return aux(p, a);
 }
 
 int lt_energy_spectrum(lt_plan *p, const void *uhat, double scale, int32_t n_bins, double *partial_scratch, double *out,
                        void *s) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (!uhat || !partial_scratch || !out) return fail(LT_ERR_INVALID, "null transformed field / scratch / output");
-  if (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
-    return fail(LT_ERR_UNSUPPORTED, "energy spectrum: 2-D / 3-D grids in the reference layout without ghost planes");
+  if (const int rc = whole_grid_only(p, lt::kAuxSpectrum)) return rc;
   if (n_bins < 1) return fail(LT_ERR_INVALID, "energy spectrum: %d bins", (int)n_bins);
   if (n_bins > LT_SPECTRUM_MAX_BINS)
     return fail(LT_ERR_UNSUPPORTED, "energy spectrum: %d bins, the kernel's table of bins per wave holds "
                                     "LT_SPECTRUM_MAX_BINS = %d", (int)n_bins, LT_SPECTRUM_MAX_BINS);
-  lt::AuxArgs a;
-  memset(&a, 0, sizeof a);
-  a.what = 10; a.layout = p->desc.layout;
+  lt::AuxArgs a = aux_args(p, lt::kAuxSpectrum, s);
   a.f = uhat; a.partial = partial_scratch; a.out = out;
-  a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2; a.N = p->N;
+  a.stride = a.N;                       // the transformed fields are dense, whatever the plan's populations are
   // fixed launch geometry: contiguous ranges of whole workgroup passes (256 modes), four passes or more, in at most
   // LT_SPECTRUM_BLOCKS workgroups
   const long long pass = 256;
@@ -1527,35 +1555,20 @@ int lt_energy_spectrum(lt_plan *p, const void *uhat, double scale, int32_t n_bin
   if (a.count < 4 * pass) a.count = 4 * pass;
   a.reduce_blocks = (int)((p->N + a.count - 1) / a.count);
   a.scale = scale; a.n_bins = n_bins;
-  a.stream = static_cast<hipStream_t>(s);
-  const int r = p->unit.aux(a);
-  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no energy spectrum kernel");
-  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
-  return LT_OK;
+  return aux(p, a);
 }
 
 int lt_boundary_force(lt_plan *p, const void *f, const uint8_t *solid, double *partial_scratch, double *out, void *s) {
   if (!p) return fail(LT_ERR_INVALID, "null plan");
   if (!f || !solid || !partial_scratch || !out)
     return fail(LT_ERR_INVALID, "null populations / solid mask / scratch / output");
-  if (p->unit.d < 2 || p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
-    return fail(LT_ERR_UNSUPPORTED, "boundary force: 2-D / 3-D grids in the reference layout without ghost planes");
-  if (pop_stride_of(p) != p->N)
-    return fail(LT_ERR_UNSUPPORTED, "boundary force: reads dense population buffers only (the plan has a population "
-                                    "stride of %lld)", pop_stride_of(p));
-  lt::AuxArgs a;
-  memset(&a, 0, sizeof a);
-  a.what = 11; a.layout = p->desc.layout;
+  if (const int rc = whole_grid_only(p, lt::kAuxBoundaryForce)) return rc;
+  lt::AuxArgs a = aux_args(p, lt::kAuxBoundaryForce, s);
   a.f = f; a.mask = solid; a.partial = partial_scratch; a.out = out;
-  a.n0 = p->n0; a.n1 = p->n1; a.n2 = p->n2; a.N = p->N; a.stride = p->N;
   // fixed launch geometry: a node per thread and pass, at most LT_BOUNDARY_FORCE_BLOCKS workgroups of 256
   const long long blocks = (p->N + 255) / 256;
   a.reduce_blocks = (int)(blocks < LT_BOUNDARY_FORCE_BLOCKS ? blocks : LT_BOUNDARY_FORCE_BLOCKS);
-  a.stream = static_cast<hipStream_t>(s);
-  const int r = p->unit.aux(a);
-  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no boundary force kernel");
-  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
-  return LT_OK;
+  return aux(p, a);
 }
 
 int lt_plan_set_links(lt_plan *p, int32_t index, int64_t n, const int32_t *nodes, const uint8_t *directions,
@@ -1627,15 +1640,12 @@ int lt_link_force(lt_plan *p, int32_t index, const void *f, double *partial_scra
   if (!l.set) return fail(LT_ERR_INVALID, "boundary %d is link bounce-back: lt_plan_set_links must give its links first", index);
   const LinkFn fn = kLinkUnits[2 * p->desc.stencil + p->desc.dtype];
   if (!fn) return fail(LT_ERR_UNSUPPORTED, "no link kernel for this lattice");
-  lt::LinkArgs a = link_args(p, l, 1, const_cast<void *>(f), pop_stride_of(p), stream);
+  lt::LinkArgs a = link_args(p, l, lt::kLinkForce, const_cast<void *>(f), pop_stride_of(p), stream);
   // fixed launch geometry: a link per thread and pass, at most LT_LINK_FORCE_BLOCKS workgroups of 256
   const long long blocks = ((long long)l.n + 255) / 256;
   a.blocks = (int)(blocks < LT_LINK_FORCE_BLOCKS ? blocks : LT_LINK_FORCE_BLOCKS);
   a.partial = partial_scratch; a.out = out;
-  const int r = fn(a);
-  if (r == lt::kNoKernel) return fail(LT_ERR_UNSUPPORTED, "no link force kernel");
-  if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
-  return LT_OK;
+  return launched(fn(a), "no link force kernel");
 }
 
 namespace {
@@ -1655,12 +1665,18 @@ int lt_slab_velocity(lt_plan *p, const void *f, void *u_ext, void *s) {
   const long long owned = p->interior_end - p->interior_begin;
   // node i of the plan (its ghost planes included) is node i + (3 - g) planes of the extended field
   char *u0 = static_cast<char *>(u_ext) + (3 - p->desc.ghost_planes) * plane * p->esize;
-  return aux(p, 0, f, nullptr, u0, nullptr, s, 1.0, 1.0, nullptr, (owned + 6) * plane);
+  lt::AuxArgs a = aux_args(p, lt::kAuxMacroscopic, s);
+  a.f = f; a.u = u0; a.u_stride = (owned + 6) * plane;
+  return aux(p, a);
 }
 int lt_slab_enstrophy(lt_plan *p, const void *u_ext, double u_scale, double inv_dx, double *out, void *s) {
   if (const int rc = slab_plan_ok(p, "lt_slab_enstrophy")) return rc;
   if (!out || !u_ext) return fail(LT_ERR_INVALID, "null output / velocity field");
-  return aux(p, 8, nullptr, nullptr, const_cast<void *>(u_ext), out, s, u_scale, inv_dx);
+  lt::AuxArgs a = aux_args(p, lt::kAuxSlabEnstrophy, s);
+  a.u = const_cast<void *>(u_ext); a.out = out;
+  a.n2 = (p->interior_end - p->interior_begin) + 6;
+  a.scale = u_scale; a.inv_dx = inv_dx;
+  return aux(p, a);
 }
 int lt_slab_mass_interior(lt_plan *p, const void *f, const uint8_t *mask, int32_t z_begin, int32_t nz_global,
                           double *out, void *s) {
@@ -1669,7 +1685,10 @@ int lt_slab_mass_interior(lt_plan *p, const void *f, const uint8_t *mask, int32_
   const int owned = p->interior_end - p->interior_begin;
   if (z_begin < 0 || nz_global < 1 || z_begin + owned > nz_global)
     return fail(LT_ERR_INVALID, "planes [%d, %d) of %d", z_begin, z_begin + owned, nz_global);
-  return aux(p, 9, f, nullptr, nullptr, out, s, 1.0, 1.0, mask, 0, z_begin, nz_global);
+  lt::AuxArgs a = aux_args(p, lt::kAuxSlabInteriorMass, s);
+  a.f = f; a.mask = mask; a.out = out;
+  a.z_begin = z_begin; a.nz_global = nz_global;
+  return aux(p, a);
 }
 
 int lt_plan_kernel_info(lt_plan *p, int32_t *vec, int32_t *tpb, int64_t *blocks) {
@@ -1747,8 +1766,7 @@ int lt_jacobi(void *p, void *p_scratch, const void *rhs, int32_t dtype, int32_t 
       a.p_in = buf[(k - 1) % 2];
       a.p_out = k == last ? nullptr : buf[k % 2];
       a.sweep = k; a.finish = k >= 2;
-      const int r = lt::jacobi_sweep(a);
-      if (r != 0) return fail(LT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+      if (const int rc = launched(lt::jacobi_sweep(a), "no Jacobi kernel")) return rc;
     }
     LT_HIP(hipMemcpyAsync(&record, state, sizeof record, hipMemcpyDeviceToHost, s));
     LT_HIP(hipStreamSynchronize(s));

@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include "lattice.hpp"
+#include "reduce.hpp"
 
 namespace lt {
 
-constexpr int kForceThreads = 256;                // four waves per workgroup
-constexpr int kForceWaves = kForceThreads / 64;
+constexpr int kForceThreads = kReduceThreads;     // four waves per workgroup
 constexpr int kForceMaxBlocks = 1024;             // == LT_BOUNDARY_FORCE_BLOCKS: the most workgroups of the first launch
+static_assert(kForceMaxBlocks <= kFinishMaxBlocks, "finish_components_kernel stages the partials of every workgroup");
 constexpr int kForceBatch = 16;                   // nodes of a thread whose bytes are in flight together
 constexpr int kForceSkew = 61;                    // slots a workgroup moves on from one pass to the next
 
@@ -33,9 +34,9 @@ __device__ __forceinline__ int force_wrap(int a, int n) {
 // q = 1 .. Q - 1 at compile time three times: the neighbours' bytes (independent loads); then, unless every neighbour is
 // solid, f_q of the fluid neighbours only (independent again: the other q re-read the node's f_0, one cached word, and
 // drop it); then the sums -- a link that carries nothing adds an exact 0.  fp64 from the first operation:
-// 2 * (double)f_q and the sign are exact.  Every thread adds its terms in the order of its nodes and of q, then one LDS
-// pass over the three sums: lanes by a shuffle tree, the four waves in wave order.  partial [3][gridDim.x]; no atomics;
-// the order depends on the grid alone.
+// 2 * (double)f_q and the sign are exact.  Every thread adds its terms in the order of its nodes and of q, then the
+// workgroup step of reduce.hpp over the three sums.  partial [3][gridDim.x]; no atomics; the order depends on the grid
+// alone.  Second launch: finish_components_kernel (reduce.hpp).
 template <typename T, class S>
 __global__ void __launch_bounds__(kForceThreads) boundary_force_kernel(const T *__restrict__ f,
                                                                       const unsigned char *__restrict__ solid,
@@ -44,7 +45,6 @@ __global__ void __launch_bounds__(kForceThreads) boundary_force_kernel(const T *
 #pragma clang fp contract(off)
   using M = MemMap<S, 0>;
   static_assert(S::Q <= 32, "a bit per population");
-  __shared__ double part[3][kForceWaves];
   double acc[3] = {0.0, 0.0, 0.0};
   const long long pass = (long long)gridDim.x * kForceThreads;
   const long long passes = (N + pass - 1) / pass;
@@ -96,43 +96,8 @@ __global__ void __launch_bounds__(kForceThreads) boundary_force_kernel(const T *
       });
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double v = acc[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    if (lane == 0) part[c][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = part[threadIdx.x][0];
-#pragma unroll
-    for (int w = 1; w < kForceWaves; ++w) s += part[threadIdx.x][w];
-    partial[(long long)threadIdx.x * gridDim.x + blockIdx.x] = s;
-  }
-}
-
-// Second launch, one workgroup: out[c] = partial[c][0] + partial[c][1] + ... in index order, c < D; out[c] = 0 for the
-// components beyond D.  All threads copy the partials into LDS (coalesced), then one thread per component adds them one
-// after the other.  Writes all three outputs whatever the first launch found.
-// (A template on the unit's scalar type only so that the objects that do not launch it do not hold it.)
-template <typename T, int D>
-__global__ void __launch_bounds__(kForceThreads) finish_force_kernel(const double *__restrict__ partial, int blocks,
-                                                                    double *__restrict__ out) {
-#pragma clang fp contract(off)
-  __shared__ double staged[3 * kForceMaxBlocks];
-  if (blocks > kForceMaxBlocks) blocks = kForceMaxBlocks;
-  for (int n = threadIdx.x; n < D * blocks; n += kForceThreads) staged[n] = partial[n];
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    if (threadIdx.x < D) {
-      const double *mine = staged + threadIdx.x * blocks;
-      for (int b = 0; b < blocks; ++b) s += mine[b];
-    }
-    out[threadIdx.x] = s;
-  }
+  const double s = block_reduce<3>(acc);
+  if (threadIdx.x < 3) partial[(long long)threadIdx.x * gridDim.x + blockIdx.x] = s;
 }
 
 }  // namespace lt

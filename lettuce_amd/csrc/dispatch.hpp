@@ -69,40 +69,74 @@ struct StepArgs {
   double rho0;
 };
 
+// The auxiliary launches of a unit (aux_<tag>; AuxArgs::what).  Nothing outside csrc/ sees the numbers.
+enum AuxKind {
+  kAuxMacroscopic = 0,    // rho, u <- f
+  kAuxEquilibrium,        // f <- feq(rho, u)
+  kAuxKineticEnergy,      // sum of u.u / 2 over the interior planes
+  kAuxMass,               // sum of rho over the interior planes
+  kAuxMaxVelocity,        // max |u| over the interior planes (NaN wins)
+  kAuxEnstrophy,          // u into the scratch field, then the vorticity stencil over it
+  kAuxInteriorMass,       // the mass observable: off the faces of the two fastest axes, minus the masked nodes
+  kAuxFneq,               // non-equilibrium initialisation: f <- feq(rho, u) - fneq(grad u)
+  kAuxSlabEnstrophy,      // the vorticity stencil over a slab's velocity field (three neighbour planes per side)
+  kAuxSlabInteriorMass,   // the mass observable over a rank's planes
+  kAuxSpectrum,           // energy spectrum of d Fourier-transformed fields: part spectrum
+  kAuxBoundaryForce,      // momentum-exchange force on the nodes of a mask: part boundary_force
+  kAuxKinds
+};
+// What api.hip asks about a kind before it launches: the name its messages use; whether the kernel takes a population
+// stride (the others read dense buffers only); whether it exists for whole grids only (d >= 2, reference layout, no
+// ghost planes).
+struct AuxTraits {
+  const char *name;
+  bool strided, whole_grid;
+};
+constexpr AuxTraits kAuxTraits[kAuxKinds] = {
+    {"macroscopic moments", true, false},   {"equilibrium", false, false},        {"kinetic energy", true, false},
+    {"mass", true, false},                  {"maximum velocity", true, false},    {"enstrophy", false, true},
+    {"interior mass", false, true},         {"f_neq initialisation", false, true}, {"slab enstrophy", true, false},
+    {"slab interior mass", true, false},    {"energy spectrum", false, true},     {"boundary force", false, true},
+};
+
+// Plan-derived fields first (api.hip, aux_args), then what the kind's entry point sets by name
 struct AuxArgs {
-  int what;              // 0 macroscopic, 1 equilibrium, 2 kinetic energy, 3 mass, 4 max |u|, 5 enstrophy, 6 interior mass,
-                         // 7 f_neq initialisation (scale = tau, inv_dx = the identity's cs^2), 8 enstrophy of a slab's
-                         // velocity field u [3][n2][n1][n0] (three neighbour planes per side), 9 interior mass of a slab,
-                         // 10 energy spectrum (f = d Fourier-transformed fields, partial = the caller's scratch of
-                         // reduce_blocks x n_bins doubles, count = modes per workgroup, out = n_bins doubles),
-                         // 11 momentum-exchange force on the nodes of mask (f = dense populations, partial = the caller's
-                         // scratch of 3 x reduce_blocks doubles, out = 3 doubles)
+  AuxKind what;
   int layout;
-  const void *f;         // populations (what 0, 2, 3) / feq output (what 1; cast away const)
-  void *rho;             // what 0: out, what 1: in
-  void *u;               // what 0: out, what 1: in
   long long N;           // nodes per population (incl. ghost planes)
-  long long stride;      // elements between consecutive populations of f (what 0, 2, 3, 4; dense = N elsewhere)
-  long long first, count;  // node range reduced (what 2, 3)
-  double *partial;       // plan scratch, >= reduce_blocks doubles
-  int reduce_blocks;
-  double *out;           // device scalar
-  int n0, n1, n2;        // memory extents (what 5, 6)
-  double scale, inv_dx;  // what 5: u_pu = scale * u_lu, 1 / dx_pu
-  int equilibrium;       // what 1, 7: lt_equilibrium_kind of the plan (0: quadratic) and, for kind 1, its rho0
+  long long stride;      // elements between consecutive populations of f (the kinds with AuxTraits::strided; dense = N
+                         // elsewhere)
+  long long first, count;  // the interior planes' node range (kAuxKineticEnergy, kAuxMass, kAuxMaxVelocity,
+                           // kAuxSlabInteriorMass); kAuxSpectrum: count = modes per workgroup
+  int n0, n1, n2;        // memory extents; kAuxSlabEnstrophy: n2 = the rank's planes + 6
+  double *partial;       // the plan's scratch, >= reduce_blocks doubles; kAuxSpectrum: the caller's, reduce_blocks x
+                         // n_bins doubles; kAuxBoundaryForce: the caller's, 3 x reduce_blocks doubles
+  int reduce_blocks;     // workgroups of the reducing launch
+  int equilibrium;       // kAuxEquilibrium, kAuxFneq: lt_equilibrium_kind of the plan (0: quadratic) and, for kind 1, its rho0
   double rho0;
-  const unsigned char *mask;   // what 6, 9: no-mass mask or null; what 11: the solid nodes
-  int z_begin, nz_global;      // what 9: global index of the rank's first plane, planes of the whole grid
-  long long u_stride;          // what 0: elements between the components of u (0 = N)
-  int n_bins;                  // what 10: bins of the spectrum
   hipStream_t stream;
+  const void *f;         // populations; kAuxEquilibrium, kAuxFneq: the output (cast away const); kAuxSpectrum: the d
+                         // transformed fields; null for kAuxSlabEnstrophy
+  void *rho;             // kAuxMacroscopic: out (or null); kAuxEquilibrium, kAuxFneq: in
+  void *u;               // kAuxMacroscopic: out (or null); kAuxEquilibrium, kAuxFneq: in; kAuxEnstrophy: the scratch
+                         // field; kAuxSlabEnstrophy: the slab's velocity field u [3][n2][n1][n0]
+  long long u_stride;    // kAuxMacroscopic: elements between the components of u (0 = N)
+  double *out;           // device result: a scalar; kAuxSpectrum: n_bins doubles; kAuxBoundaryForce: 3 doubles
+  double scale, inv_dx;  // kAuxEnstrophy, kAuxSlabEnstrophy: u_pu = scale * u_lu, 1 / dx_pu; kAuxFneq: tau, the identity's
+                         // cs^2; kAuxSpectrum: scale of the bins
+  const unsigned char *mask;   // kAuxInteriorMass, kAuxSlabInteriorMass: no-mass mask or null; kAuxBoundaryForce: the solid nodes
+  int z_begin, nz_global;      // kAuxSlabInteriorMass: global index of the rank's first plane, planes of the whole grid
+  int n_bins;                  // kAuxSpectrum: bins of the spectrum
 };
 
 // The link kernels of a plan with link bounce-back (link_bounce.hpp; the units' part links): one compact list of links
 // in plan-owned device memory, c1 / c2 in the plan's scalar type
+enum LinkKind {
+  kLinkBounce = 0,       // the bounce-back pass on f, in place
+  kLinkForce             // the momentum-exchange force over the list
+};
 struct LinkArgs {
-  int what;              // 0: the bounce-back pass on f, in place; 1: the momentum-exchange force over the list (partial =
-                         // the caller's scratch of 3 x blocks doubles, out = 3 doubles)
+  LinkKind what;
   void *f;               // populations [q][stride]
   long long stride;      // elements between consecutive populations of f
   const int *node;
@@ -111,9 +145,9 @@ struct LinkArgs {
   const unsigned char *second;
   int n_links;
   int n0, n1, n2;        // memory extents
-  double *partial;
-  int blocks;            // what 1: workgroups of the first launch (0 for an empty list)
-  double *out;
+  double *partial;       // kLinkForce: the caller's scratch of 3 x blocks doubles
+  int blocks;            // kLinkForce: workgroups of the first launch (0 for an empty list)
+  double *out;           // kLinkForce: 3 doubles
   hipStream_t stream;
 };
 

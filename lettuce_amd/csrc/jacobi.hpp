@@ -6,6 +6,8 @@
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+
+#include "reduce.hpp"
 #define LT_JACOBI_HD __host__ __device__ __forceinline__
 #else
 #define LT_JACOBI_HD inline
@@ -61,10 +63,12 @@ LT_JACOBI_HD void jacobi_node(const T *p, const T *rhs, long long i, int n0, int
 }
 
 #ifdef __HIPCC__
+static_assert(kJacobiThreads == kReduceThreads, "the workgroup reduce.hpp adds up");
+
 // One sweep.  Reads the done flag first and returns without writing once it is set.  Otherwise: p_out = the next iterate
 // (p_out == nullptr: not kept -- the sweep behind the last iteration, which is there for the error alone) and
 // partial[blockIdx.x] = the sum of r^2 over the workgroup's nodes, r widened to fp64: every thread adds its nodes in
-// index order, a wave its lanes in a fixed shuffle tree, the workgroup its waves in wave order.
+// index order, then the wave tree and the workgroup step of reduce.hpp.
 template <typename T, int D>
 __global__ void __launch_bounds__(kJacobiThreads) jacobi_sweep_kernel(const T *__restrict__ p_in, const T *__restrict__ rhs,
                                                                       T *__restrict__ p_out, int n0, int n1, int n2,
@@ -73,7 +77,6 @@ __global__ void __launch_bounds__(kJacobiThreads) jacobi_sweep_kernel(const T *_
                                                                       double *__restrict__ partial) {
 #pragma clang fp contract(off)
   if (state->done) return;
-  __shared__ double wave_sum[kJacobiWaves];
   const long long N = (long long)n0 * n1 * n2;
   const long long begin = (long long)blockIdx.x * chunk, end = begin + chunk < N ? begin + chunk : N;
   double sum = 0.0;
@@ -84,16 +87,8 @@ __global__ void __launch_bounds__(kJacobiThreads) jacobi_sweep_kernel(const T *_
     const double rd = (double)r;
     sum += rd * rd;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);      // lane 0 ends with the tree's sum
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = wave_sum[0];
-#pragma unroll
-    for (int w = 1; w < kJacobiWaves; ++w) s += wave_sum[w];
-    partial[blockIdx.x] = s;
-  }
+  const double s = block_sum(sum);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // One workgroup after sweep `sweep` (>= 2): error = (partial[0] + partial[1] + ...) / N is the error of iterate
@@ -105,17 +100,10 @@ __global__ void __launch_bounds__(kJacobiThreads) jacobi_finish_kernel(const dou
                                                                        JacobiState *__restrict__ state) {
 #pragma clang fp contract(off)
   if (state->done) return;
-  __shared__ double wave_sum[kJacobiWaves];
   double sum = 0.0;
   for (int b = threadIdx.x; b < blocks; b += kJacobiThreads) sum += partial[b];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
-  __syncthreads();
+  const double s = block_sum(sum);
   if (threadIdx.x == 0) {
-    double s = wave_sum[0];
-#pragma unroll
-    for (int w = 1; w < kJacobiWaves; ++w) s += wave_sum[w];
     const double error = s / (double)N;
     state->iterations = sweep - 1;
     state->error = error;

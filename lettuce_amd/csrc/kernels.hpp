@@ -26,11 +26,13 @@
 #include "dispatch.hpp"
 #include "lattice.hpp"
 #include "mrt.hpp"
+#include "reduce.hpp"
 #include "twostep_roles.hpp"
 
 namespace lt {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kReduceThreads, "the reducing kernels launch the workgroup reduce.hpp adds up");
 constexpr int kMaxB = 127;   // == LT_MAX_BOUNDARIES: what the node byte's seven index bits can name
 
 // boundary kinds (== lt_boundary_kind)
@@ -1596,31 +1598,6 @@ __global__ void __launch_bounds__(kThreads) fneq_inc_kernel(const T *__restrict_
 #undef LT_FNEQ_FOR_EACH_FEQ
 }
 
-// maximum that propagates NaN like torch.max: a NaN on either side wins and then stays (`m > acc` alone is false
-// for a NaN m, which would drop it); without a NaN the larger value, as before
-__device__ __forceinline__ double nan_max(double m, double acc) { return (m > acc || m != m) ? m : acc; }
-
-// wavefront (64-lane) + workgroup reduction of a double (sum, or max when MAX: NaN-propagating); result valid in
-// thread 0
-template <bool MAX = false>
-__device__ __forceinline__ double block_sum(double v) {
-  __shared__ double part[kThreads / 64];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_down(v, off);
-    v = MAX ? nan_max(o, v) : v + o;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) part[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) s = MAX ? nan_max(part[w], s) : s + part[w];
-  }
-  return s;
-}
-
 // per-block partial sums of 0.5*u.u (MODE 0) or of sum_q f (MODE 1), or per-block maximum of |u|
 // (MODE 2), over the planes
 // [p_begin, p_begin + planes) of a2; fixed grid -> fixed summation order.
@@ -1747,15 +1724,6 @@ __global__ void __launch_bounds__(kThreads) interior_mass_slab_kernel(const T *_
   }
   const double s = block_sum<false>(acc);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-template <bool MAX>
-static __global__ void __launch_bounds__(kThreads) finish_sum_kernel(const double *__restrict__ partial,
-                                                              int n, double *__restrict__ out) {
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < n; i += kThreads) acc = MAX ? nan_max(partial[i], acc) : acc + partial[i];
-  const double s = block_sum<MAX>(acc);
-  if (threadIdx.x == 0) *out = s;
 }
 
 // halo pack / unpack of the slab driver: the populations that cross a z cut (5 of 19, 9 of 27)

@@ -8,12 +8,13 @@
 #include <hip/hip_runtime.h>
 
 #include "lattice.hpp"
+#include "reduce.hpp"
 
 namespace lt {
 
-constexpr int kLinkThreads = 256;                 // four waves per workgroup
-constexpr int kLinkWaves = kLinkThreads / 64;
+constexpr int kLinkThreads = kReduceThreads;      // four waves per workgroup
 constexpr int kLinkMaxBlocks = 1024;              // == LT_LINK_FORCE_BLOCKS: the most workgroups of the force's first launch
+static_assert(kLinkMaxBlocks <= kFinishMaxBlocks, "finish_components_kernel stages the partials of every workgroup");
 
 // the lattice as the link kernels index it at run time (the direction of a link is data): the velocities along the
 // memory axes a0, a1, a2 of the reference layout, along the logical axes, and the opposite directions
@@ -90,14 +91,14 @@ __global__ void __launch_bounds__(kLinkThreads) link_bounce_kernel(T *__restrict
 // f_r(x_f) what came back;   acc[c] += e_{q,c} f_q(x_s);  acc[c] += e_{q,c} f_r(x_f),   c a LOGICAL axis
 // (for d = 1/2 the two are equal: the 2 e_q f_q(x_s) of boundary_force.hpp).  fp64 from the first operation, the sign
 // is exact.  A fixed grid: workgroup b, thread t takes the links b 256 + t + k gridDim.x 256, k = 0, 1, ..., and adds its
-// terms in that order; then one LDS pass over the three sums: lanes by a shuffle tree, the four waves in wave order.
-// partial [3][gridDim.x]; no atomics; the order depends on the list's length alone.
+// terms in that order; then the workgroup step of reduce.hpp over the three sums.  partial [3][gridDim.x]; no atomics;
+// the order depends on the list's length alone.  Second launch: finish_components_kernel (reduce.hpp; an empty list
+// launches it alone, with blocks = 0).
 template <typename T, class S>
 __global__ void __launch_bounds__(kLinkThreads) link_force_kernel(const T *__restrict__ f, long long stride,
                                                                   const LinkList<T> l, int n0, int n1, int n2,
                                                                   const LinkTable t, double *__restrict__ partial) {
 #pragma clang fp contract(off)
-  __shared__ double part[3][kLinkWaves];
   double acc[3] = {0.0, 0.0, 0.0};
   const long long pass = (long long)gridDim.x * kLinkThreads;
   for (long long i = (long long)blockIdx.x * kLinkThreads + threadIdx.x; i < l.n; i += pass) {
@@ -113,41 +114,8 @@ __global__ void __launch_bounds__(kLinkThreads) link_force_kernel(const T *__res
       if (e < 0) { acc[c] -= out; acc[c] -= back; }
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double v = acc[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    if (lane == 0) part[c][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = part[threadIdx.x][0];
-#pragma unroll
-    for (int w = 1; w < kLinkWaves; ++w) s += part[threadIdx.x][w];
-    partial[(long long)threadIdx.x * gridDim.x + blockIdx.x] = s;
-  }
-}
-
-// Second launch, one workgroup: out[c] = partial[c][0] + partial[c][1] + ... in index order, c < D; out[c] = 0 beyond D
-// and for an empty list (blocks = 0, nothing is read).  Writes all three outputs.
-template <typename T, int D>
-__global__ void __launch_bounds__(kLinkThreads) finish_link_force_kernel(const double *__restrict__ partial, int blocks,
-                                                                         double *__restrict__ out) {
-#pragma clang fp contract(off)
-  __shared__ double staged[3 * kLinkMaxBlocks];
-  if (blocks > kLinkMaxBlocks) blocks = kLinkMaxBlocks;
-  for (int n = threadIdx.x; n < 3 * blocks; n += kLinkThreads) staged[n] = partial[n];
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    if (threadIdx.x < D) {
-      const double *mine = staged + threadIdx.x * blocks;
-      for (int b = 0; b < blocks; ++b) s += mine[b];
-    }
-    out[threadIdx.x] = s;
-  }
+  const double s = block_reduce<3>(acc);
+  if (threadIdx.x < 3) partial[(long long)threadIdx.x * gridDim.x + blockIdx.x] = s;
 }
 
 }  // namespace lt

@@ -636,102 +636,80 @@ int dispatch(const StepArgs &a, const NameBuf *name) {
   return kNoKernel;
 }
 
+// A scalar observable: `kern` over the plan's fixed grid leaves a partial per workgroup, then one workgroup takes the
+// partials in index order (reduce.hpp; MAX: the NaN-propagating maximum)
+template <bool MAX = false, class K, class... A>
+void reduced(const AuxArgs &a, K kern, A... args) {
+  hipLaunchKernelGGL(kern, dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream, args..., a.partial);
+  hipLaunchKernelGGL(finish_sum_kernel<MAX>, dim3(1), dim3(kThreads), 0, a.stream, a.partial, a.reduce_blocks, a.out);
+}
+
 template <int LAYOUT>
 int aux_impl(const AuxArgs &a) {
   // feq with another equilibrium than the quadratic one: part incompressible
-  if (a.equilibrium != 0 && (a.what == 1 || a.what == 7)) return LT_CAT(incompressible_aux_, LT_TAG)(a);
+  if (a.equilibrium != 0 && (a.what == kAuxEquilibrium || a.what == kAuxFneq)) return LT_CAT(incompressible_aux_, LT_TAG)(a);
   const T *f = static_cast<const T *>(a.f);
   const unsigned grid = (unsigned)((a.N + kThreads - 1) / kThreads);
+  constexpr bool kWholeGrid = S::D >= 2 && LAYOUT == 0, kSlab = S::D == 3 && LAYOUT == 1;
   switch (a.what) {
-    case 0:
+    case kAuxMacroscopic:
       hipLaunchKernelGGL((macroscopic_kernel<T, S, LAYOUT>), dim3(grid), dim3(kThreads), 0,
                          a.stream, f, static_cast<T *>(a.rho), static_cast<T *>(a.u), a.N, a.stride,
                          a.u_stride ? a.u_stride : a.N);
       break;
-    case 1:
+    case kAuxEquilibrium:
       hipLaunchKernelGGL((equilibrium_kernel<T, S, LAYOUT>), dim3(grid), dim3(kThreads), 0,
                          a.stream, static_cast<const T *>(a.rho), static_cast<const T *>(a.u),
                          const_cast<T *>(f), a.N);
       break;
-    case 2:
-      hipLaunchKernelGGL((reduce_kernel<T, S, LAYOUT, 0>), dim3(a.reduce_blocks), dim3(kThreads),
-                         0, a.stream, f, a.stride, a.first, a.count, a.partial);
-      hipLaunchKernelGGL(finish_sum_kernel<false>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                         a.reduce_blocks, a.out);
+    case kAuxKineticEnergy:
+      reduced(a, reduce_kernel<T, S, LAYOUT, 0>, f, a.stride, a.first, a.count);
       break;
-    case 3:
-      hipLaunchKernelGGL((reduce_kernel<T, S, LAYOUT, 1>), dim3(a.reduce_blocks), dim3(kThreads),
-                         0, a.stream, f, a.stride, a.first, a.count, a.partial);
-      hipLaunchKernelGGL(finish_sum_kernel<false>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                         a.reduce_blocks, a.out);
+    case kAuxMass:
+      reduced(a, reduce_kernel<T, S, LAYOUT, 1>, f, a.stride, a.first, a.count);
       break;
-    case 4:
-      hipLaunchKernelGGL((reduce_kernel<T, S, LAYOUT, 2>), dim3(a.reduce_blocks), dim3(kThreads),
-                         0, a.stream, f, a.stride, a.first, a.count, a.partial);
-      hipLaunchKernelGGL(finish_sum_kernel<true>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                         a.reduce_blocks, a.out);
+    case kAuxMaxVelocity:
+      reduced<true>(a, reduce_kernel<T, S, LAYOUT, 2>, f, a.stride, a.first, a.count);
       break;
-    case 5:     // u into the scratch field, then the vorticity stencil over it
-      if constexpr (S::D >= 2 && LAYOUT == 0) {
+    case kAuxEnstrophy:     // u into the scratch field, then the vorticity stencil over it
+      if constexpr (!kWholeGrid) return kNoKernel;
+      else {
         hipLaunchKernelGGL((macroscopic_kernel<T, S, LAYOUT>), dim3(grid), dim3(kThreads), 0,
                            a.stream, f, static_cast<T *>(nullptr), static_cast<T *>(a.u), a.N, a.N, a.N);
-        hipLaunchKernelGGL((enstrophy_kernel<T, S::D>), dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream,
-                           static_cast<const T *>(a.u), a.n0, a.n1, a.n2, (T)a.scale, (T)a.inv_dx, a.partial);
-        hipLaunchKernelGGL(finish_sum_kernel<false>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                           a.reduce_blocks, a.out);
-        break;
-      } else {
-        return kNoKernel;
+        reduced(a, enstrophy_kernel<T, S::D>, static_cast<const T *>(a.u), a.n0, a.n1, a.n2, (T)a.scale, (T)a.inv_dx);
       }
-    case 7:     // non-equilibrium initialisation: f <- feq(rho, u) - fneq(grad u)
-      if constexpr (S::D >= 2 && LAYOUT == 0) {
+      break;
+    case kAuxInteriorMass:
+      if constexpr (!kWholeGrid) return kNoKernel;
+      else reduced(a, interior_mass_kernel<T, S::Q>, f, a.N, a.n0, a.n1, a.mask);
+      break;
+    case kAuxFneq:
+      if constexpr (!kWholeGrid) return kNoKernel;
+      else
         hipLaunchKernelGGL((fneq_kernel<T, S>), dim3(grid), dim3(kThreads), 0, a.stream,
                            static_cast<const T *>(a.rho), static_cast<const T *>(a.u), const_cast<T *>(f), a.n0, a.n1,
                            a.n2, (T)a.scale, (T)a.inv_dx);
-        break;
-      } else {
-        return kNoKernel;
-      }
-    case 6:
-      if constexpr (S::D >= 2 && LAYOUT == 0) {
-        hipLaunchKernelGGL((interior_mass_kernel<T, S::Q>), dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream,
-                           f, a.N, a.n0, a.n1, a.mask, a.partial);
-        hipLaunchKernelGGL(finish_sum_kernel<false>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                           a.reduce_blocks, a.out);
-        break;
-      } else {
-        return kNoKernel;
-      }
-    case 8:
-      if constexpr (S::D == 3 && LAYOUT == 1) {
-        hipLaunchKernelGGL((enstrophy_kernel<T, 3, true>), dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream,
-                           static_cast<const T *>(a.u), a.n0, a.n1, a.n2, (T)a.scale, (T)a.inv_dx, a.partial);
-        hipLaunchKernelGGL(finish_sum_kernel<false>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                           a.reduce_blocks, a.out);
-        break;
-      } else {
-        return kNoKernel;
-      }
-    case 10:    // energy spectrum of d Fourier-transformed fields: part spectrum
+      break;
+    case kAuxSlabEnstrophy:
+      if constexpr (!kSlab) return kNoKernel;
+      else reduced(a, enstrophy_kernel<T, 3, true>, static_cast<const T *>(a.u), a.n0, a.n1, a.n2, (T)a.scale, (T)a.inv_dx);
+      break;
+    case kAuxSlabInteriorMass:
+      if constexpr (!kSlab) return kNoKernel;
+      else
+        reduced(a, interior_mass_slab_kernel<T, S::Q>, f, a.stride, a.first, a.count, a.n0, a.n1, a.z_begin,
+                a.nz_global, a.mask);
+      break;
+    case kAuxSpectrum:
 #if LT_FIELD(d, LT_UNIT) >= 2
       if constexpr (LAYOUT == 0) return LT_CAT(spectrum_, LT_TAG)(a);
 #endif
       return kNoKernel;
-    case 11:    // momentum-exchange force on the nodes of a.mask: part boundary_force
+    case kAuxBoundaryForce:
 #if LT_FIELD(d, LT_UNIT) >= 2
       if constexpr (LAYOUT == 0) return LT_CAT(boundary_force_, LT_TAG)(a);
 #endif
       return kNoKernel;
-    case 9:
-      if constexpr (S::D == 3 && LAYOUT == 1) {
-        hipLaunchKernelGGL((interior_mass_slab_kernel<T, S::Q>), dim3(a.reduce_blocks), dim3(kThreads), 0, a.stream,
-                           f, a.stride, a.first, a.count, a.n0, a.n1, a.z_begin, a.nz_global, a.mask, a.partial);
-        hipLaunchKernelGGL(finish_sum_kernel<false>, dim3(1), dim3(kThreads), 0, a.stream, a.partial,
-                           a.reduce_blocks, a.out);
-        break;
-      } else {
-        return kNoKernel;
-      }
     default:
       return kNoKernel;
   }
@@ -832,18 +810,18 @@ int LT_CAT(incompressible_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
   return kNoKernel;
 }
 
-// lt_equilibrium (what 1) and lt_init_fneq (what 7) of a plan with the incompressible equilibrium, reference layout
+// lt_equilibrium (kAuxEquilibrium) and lt_init_fneq (kAuxFneq) of a plan with the incompressible equilibrium, reference layout
 int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
   if (a.equilibrium != 1 || a.layout != 0) return kNoKernel;
   const unsigned grid = (unsigned)((a.N + kThreads - 1) / kThreads);
-  if (a.what == 1) {
+  if (a.what == kAuxEquilibrium) {
     hipLaunchKernelGGL((equilibrium_inc_kernel<T, S, 0>), dim3(grid), dim3(kThreads), 0, a.stream,
                        static_cast<const T *>(a.rho), static_cast<const T *>(a.u),
                        const_cast<T *>(static_cast<const T *>(a.f)), a.N, (T)a.rho0);
     return (int)hipGetLastError();
   }
   if constexpr (S::D >= 2) {
-    if (a.what == 7) {
+    if (a.what == kAuxFneq) {
       hipLaunchKernelGGL((fneq_inc_kernel<T, S>), dim3(grid), dim3(kThreads), 0, a.stream, static_cast<const T *>(a.rho),
                          static_cast<const T *>(a.u), const_cast<T *>(static_cast<const T *>(a.f)), a.n0, a.n1, a.n2,
                          (T)a.scale, (T)a.inv_dx, (T)a.rho0);
@@ -853,10 +831,10 @@ int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
   return kNoKernel;
 }
 #elif LT_PART_IS(spectrum)
-// lt_energy_spectrum (what 10): a.f the transformed fields, a.partial the caller's [a.reduce_blocks][a.n_bins] scratch;
+// lt_energy_spectrum (kAuxSpectrum): a.f the transformed fields, a.partial the caller's [a.reduce_blocks][a.n_bins] scratch;
 // a.count modes per workgroup
 int LT_CAT(spectrum_, LT_TAG)(const AuxArgs &a) {
-  if (a.what != 10 || a.layout != 0 || a.n_bins < 1 || a.n_bins > kSpectrumMaxBins) return kNoKernel;
+  if (a.what != kAuxSpectrum || a.layout != 0 || a.n_bins < 1 || a.n_bins > kSpectrumMaxBins) return kNoKernel;
   hipLaunchKernelGGL((energy_spectrum_kernel<T, S::D>), dim3(a.reduce_blocks), dim3(kSpectrumThreads),
                      kSpectrumWaves * a.n_bins * sizeof(double), a.stream, static_cast<const T *>(a.f), a.n0, a.n1, a.n2,
                      a.count, a.n_bins, a.partial);
@@ -865,33 +843,33 @@ int LT_CAT(spectrum_, LT_TAG)(const AuxArgs &a) {
   return (int)hipGetLastError();
 }
 #elif LT_PART_IS(boundary_force)
-// lt_boundary_force (what 11): a.f the dense populations, a.mask the solid bytes, a.partial the caller's
+// lt_boundary_force (kAuxBoundaryForce): a.f the dense populations, a.mask the solid bytes, a.partial the caller's
 // [3][a.reduce_blocks] scratch, a.out three doubles
 int LT_CAT(boundary_force_, LT_TAG)(const AuxArgs &a) {
-  if (a.what != 11 || a.layout != 0 || a.reduce_blocks < 1 || a.reduce_blocks > kForceMaxBlocks) return kNoKernel;
+  if (a.what != kAuxBoundaryForce || a.layout != 0 || a.reduce_blocks < 1 || a.reduce_blocks > kForceMaxBlocks) return kNoKernel;
   hipLaunchKernelGGL((boundary_force_kernel<T, S>), dim3(a.reduce_blocks), dim3(kForceThreads), 0, a.stream,
                      static_cast<const T *>(a.f), a.mask, a.N, a.n0, a.n1, a.n2, a.partial);
-  hipLaunchKernelGGL((finish_force_kernel<T, S::D>), dim3(1), dim3(kForceThreads), 0, a.stream, a.partial,
+  hipLaunchKernelGGL((finish_components_kernel<T, S::D>), dim3(1), dim3(kForceThreads), 0, a.stream, a.partial,
                      a.reduce_blocks, a.out);
   return (int)hipGetLastError();
 }
 #elif LT_PART_IS(links)
-// lt_apply_links and step() (what 0), lt_link_force (what 1): a.f the populations, the list in plan-owned memory
+// lt_apply_links and step() (kLinkBounce), lt_link_force (kLinkForce): a.f the populations, the list in plan-owned memory
 int LT_CAT(links_, LT_TAG)(const LinkArgs &a) {
   const LinkList<T> l = {a.node, a.dir, static_cast<const T *>(a.c1), static_cast<const T *>(a.c2), a.second, a.n_links};
   const LinkTable t = link_table<S>();
-  if (a.what == 0) {
+  if (a.what == kLinkBounce) {
     if (a.n_links < 1) return 0;
     const unsigned grid = ((unsigned)a.n_links + kLinkThreads - 1) / kLinkThreads;
     hipLaunchKernelGGL((link_bounce_kernel<T, S>), dim3(grid), dim3(kLinkThreads), 0, a.stream, static_cast<T *>(a.f),
                        a.stride, l, a.n0, a.n1, a.n2, t);
     return (int)hipGetLastError();
   }
-  if (a.what != 1 || a.blocks < 0 || a.blocks > kLinkMaxBlocks) return kNoKernel;
+  if (a.what != kLinkForce || a.blocks < 0 || a.blocks > kLinkMaxBlocks) return kNoKernel;
   if (a.blocks > 0)
     hipLaunchKernelGGL((link_force_kernel<T, S>), dim3(a.blocks), dim3(kLinkThreads), 0, a.stream,
                        static_cast<const T *>(a.f), a.stride, l, a.n0, a.n1, a.n2, t, a.partial);
-  hipLaunchKernelGGL((finish_link_force_kernel<T, S::D>), dim3(1), dim3(kLinkThreads), 0, a.stream, a.partial, a.blocks,
+  hipLaunchKernelGGL((finish_components_kernel<T, S::D>), dim3(1), dim3(kLinkThreads), 0, a.stream, a.partial, a.blocks,
                      a.out);
   return (int)hipGetLastError();
 }

@@ -305,6 +305,30 @@ def test_interior_mass_of_a_grid_without_interior(lat, res, dt):
     assert float(plan.mass_interior(f, mask.cuda())) == pytest.approx(want, rel=1e-12)
 
 
+@pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("res", [(5, 7), (520, 510)], ids=["5x7", "520x510"])
+def test_interior_mass_has_the_bits_of_the_documented_summation_order(res, dt, masked):
+    """The summation order of reduce.hpp, emulated on the host (fixed_order_sum.py), predicts the observable's bytes.
+    [5, 7]: 35 nodes in one partial wave, 1023 empty partials; [520, 510]: 265 200 nodes > 1024 * 256, so some threads
+    add two nodes.  Terms as interior_mass_kernel writes them: sum_q (double)f_q in q order, then inner - masked.
+    What pins the ORDER are the fp64 plans: fp32 terms widened to fp64 add exactly whatever the order, so the fp32 cases
+    show only that every item is taken exactly once."""
+    import fixed_order_sum as fos
+    f_host, ref = _field("D2Q9", res, dt)
+    mask = torch.rand(list(res), generator=torch.Generator().manual_seed(7)) < 0.3 if masked else None
+    node = fos.in_order(ref.numpy().reshape(9, -1).T)
+    inner = np.zeros(res, dtype=bool)
+    inner[1:-1, 1:-1] = True
+    inner = inner.ravel()
+    out = mask.numpy().ravel() if masked else np.zeros_like(inner)
+    terms = np.where(inner, node, 0.0) - np.where(out, node, 0.0)
+    want = np.float64(fos.scalar_observable(terms))
+    got = _plan("D2Q9", dt, res).mass_interior(dev(f_host), mask.cuda() if masked else None).cpu().numpy()
+    print(f"{res} {dt} masked={masked}: got {float(got)!r}, emulation {float(want)!r}")
+    assert got.dtype == np.float64 and got.tobytes() == want.tobytes()
+
+
 # --------------------------------------------------------------------------- d. moments and equilibrium on slab plans
 @pytest.mark.parametrize("res,ghosts", [((10, 6, 4), 1), ((9, 5, 3), 2)], ids=["10x6x4-g1", "9x5x3-g2"])
 @pytest.mark.parametrize("dt", ["f64", "f32"])

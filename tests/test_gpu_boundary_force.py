@@ -74,6 +74,40 @@ def test_two_calls_give_the_same_bits(lat, dt):
     assert torch.equal(first, second) and bool((first != 0).all())
 
 
+def force_terms(stencil, f, solid):
+    """[d, nodes, q - 1] float64: what boundary_force_kernel adds for node i (C order of the grid) and q = 1 .. Q - 1, per
+    logical component -- +-2 (double)f_q where x_s is solid and x_s - e_q is not and e_{q,c} != 0, +0.0 elsewhere"""
+    d = stencil.d
+    f = f.double().numpy().reshape(stencil.q, -1)
+    items = np.zeros((d, f.shape[1], stencil.q - 1))
+    for q in range(1, stencil.q):
+        e = [int(x) for x in stencil.e[q]]
+        link = (solid & ~torch.roll(solid, shifts=tuple(e), dims=tuple(range(d)))).numpy().ravel()
+        v = np.where(link, 2.0 * f[q], 0.0)
+        for c in range(d):
+            if e[c]:
+                items[c, :, q - 1] = v if e[c] > 0 else -v
+    return items
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+@pytest.mark.parametrize("lat,res", [("D2Q9", (5, 7)), ("D3Q19", (6, 5, 67)), ("D2Q9", (520, 510))],
+                         ids=["d2q9-5x7", "d3q19-6x5x67", "d2q9-520x510"])
+def test_the_force_has_the_bits_of_the_documented_summation_order(lat, res, dt):
+    """The order of boundary_force.hpp and reduce.hpp, emulated on the host (fixed_order_sum.py), predicts the bytes:
+    one workgroup; 8 workgroups with the last one partial; 1024 workgroups and two passes, where the rotation of the
+    slots by 61 per pass decides which thread takes a node of the second pass.
+    What pins the ORDER are the fp64 plans: fp32 terms widened to fp64 add exactly whatever the order, so the fp32 cases
+    show only that every item is taken exactly once."""
+    import fixed_order_sum as fos
+    stencil = STENCIL[lat]()
+    f, solid = populations(lat, res, dt), solid_mask("checkerboard", res)
+    want = np.asarray(fos.boundary_force(force_terms(stencil, f, solid)), dtype=np.float64)
+    got = plan_of(lat, res, dt).boundary_force(f.cuda(), on_device(solid)).cpu().numpy()
+    print(f"{lat} {res} {dt}: got {got.tolist()!r}, emulation {want.tolist()!r}")
+    assert got.dtype == np.float64 and bool((got != 0).all()) and got.tobytes() == want.tobytes()
+
+
 # ------------------------------------------------------------------------------------------ through Simulation
 class _CopyState(lt.Reporter):
     """keeps a host copy of flow.f at the steps the observable reporter acts on; placed before it in the list, so both

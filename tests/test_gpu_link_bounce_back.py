@@ -402,6 +402,44 @@ def test_link_force_against_an_exact_host_sum(case, dt):
 
 
 @pytest.mark.parametrize("dt", ["f32", "f64"])
+@pytest.mark.parametrize("n_links", [5, 320000], ids=["5-links", "every-node-8-directions"])
+def test_link_force_has_the_bits_of_the_documented_summation_order(n_links, dt):
+    """A synthetic sorted list on D2Q9 [200, 200], every node x the directions 1 .. 8: 320 000 links > 1024 * 256, so a
+    thread of the first workgroups adds two links; and its first 5 links alone.  The order of link_bounce.hpp and
+    reduce.hpp, emulated on the host (fixed_order_sum.py), predicts the bytes.  Terms as link_force_kernel adds them:
+    +- out, +- back per link, out = f_q(x_s), back = f_r(x_f), the sign that of e_{q,c}.
+    What pins the ORDER are the fp64 plans: fp32 terms widened to fp64 add exactly whatever the order, so the fp32 cases
+    show only that every item is taken exactly once."""
+    import fixed_order_sum as fos
+    from lettuce_amd import _native
+    lat, res = "D2Q9", [200, 200]
+    stencil = STENCIL[lat]()
+    nodes = np.repeat(np.arange(res[0] * res[1]), 8)[:n_links]
+    directions = np.tile(np.arange(1, 9), res[0] * res[1])[:n_links]
+    f = signed_state(lat, res, dt)
+    e = np.array(stencil.e, dtype=np.int64)
+    opposite = np.array([int(o) for o in stencil.opposite])
+    x_s = np.stack(np.unravel_index(nodes, res), axis=1)
+    x_f = (x_s + e[directions]) % np.array(res)
+    q = opposite[directions]
+    values = f.double().numpy()
+    out, back = values[q, x_s[:, 0], x_s[:, 1]], values[directions, x_f[:, 0], x_f[:, 1]]
+    items = np.zeros((stencil.d, n_links, 2))
+    for c in range(stencil.d):
+        sign = np.sign(e[q, c]).astype(np.float64)
+        items[c, :, 0], items[c, :, 1] = np.where(sign != 0, sign * out, 0.0), np.where(sign != 0, sign * back, 0.0)
+    want = np.asarray(fos.link_force(items), dtype=np.float64)
+    plan = _native.Plan(lat, TORCH_DT[dt], "none", res, [{"kind": "link_bounce_back"}])
+    coefficient = torch.zeros(n_links, dtype=TORCH_DT[dt])
+    assert plan.set_links(0, nodes, directions, coefficient, coefficient, np.zeros(n_links, dtype=np.uint8)) == n_links
+    got = plan.link_force(0, f.cuda()).cpu().numpy()
+    print(f"{n_links} links {dt}: got {got.tolist()!r}, emulation {want.tolist()!r}")
+    # (over every node and direction the terms cancel -- each population leaves one node and comes back to another: what
+    # is left in fp64 is the rounding of this very order, 5e-15 and 2e-14 on an MI355X; the fp32 terms add exactly, to 0.0)
+    assert got.dtype == np.float64 and (n_links > 5 or bool((got != 0).all())) and got.tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
 @pytest.mark.parametrize("lat,res", [("D2Q9", [16, 12]), ("D3Q27", [8, 8, 8])], ids=["d2q9", "d3q27"])
 def test_drag_coefficient_on_native_and_cpu_contexts(lat, res, dt):
     """the same populations on both contexts: lt_link_force there, the torch expression here, both within the summation
