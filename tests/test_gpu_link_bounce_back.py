@@ -9,7 +9,7 @@ before it asserts.
 
 Measured on an MI355X: the pass alone and the runs without a collision differ from the torch path by 0 on every slot; with
 a collision the largest difference after 4 steps is 1.5e-7 (fp32, KBC) and 2.2e-16 (fp64); the force kernel stays within
-0.05 of its bound (largest error 1.1e-16); 214 tests in 4 s."""
+0.05 of its bound (largest error 1.1e-16); with the two D3Q15 grids 290 tests in 4 s."""
 import functools
 import math
 
@@ -27,7 +27,8 @@ from test_link_bounce_back_host import STENCIL, body_mask, dense_definition, ran
 pytestmark = pytest.mark.gpu
 
 # small extents make x_ff wrap onto the far side (and onto the body itself); 67 makes the last workgroup ragged
-GRIDS = [("D2Q9", [5, 67]), ("D2Q9", [3, 4]), ("D3Q19", [6, 5, 67]), ("D3Q27", [4, 4, 4]), ("D3Q27", [3, 3, 5])]
+GRIDS = [("D2Q9", [5, 67]), ("D2Q9", [3, 4]), ("D3Q19", [6, 5, 67]), ("D3Q27", [4, 4, 4]), ("D3Q27", [3, 3, 5]),
+         ("D3Q15", [6, 5, 7]), ("D3Q15", [3, 3, 5])]
 MASKS = ["isolated", "plate", "block", "seam", "sphere", "none"]
 CASES = [(lat, res, mask) for lat, res in GRIDS for mask in MASKS]
 

@@ -22,8 +22,8 @@ from conftest import TORCH_DT
 from test_boundary_force_host import U, assert_within_bound, exact_force
 from test_host_api import ctx, UniformFlow
 
-STENCIL = {"D2Q9": lt.D2Q9, "D3Q19": lt.D3Q19, "D3Q27": lt.D3Q27}
-GRIDS = [("D2Q9", [5, 7]), ("D3Q19", [4, 5, 6]), ("D3Q27", [4, 4, 4])]
+STENCIL = {"D2Q9": lt.D2Q9, "D3Q15": lt.D3Q15, "D3Q19": lt.D3Q19, "D3Q27": lt.D3Q27}
+GRIDS = [("D2Q9", [5, 7]), ("D3Q19", [4, 5, 6]), ("D3Q27", [4, 4, 4]), ("D3Q15", [5, 4, 6])]
 MASKS = ["isolated", "plate", "block", "seam"]
 
 
