@@ -12,6 +12,7 @@
 
 #include "dispatch.hpp"
 #include "kernels.hpp"
+#include "launch_limits.hpp"
 #include "lettuce_hip.h"
 
 namespace {
@@ -51,10 +52,12 @@ struct Unit {
   lt::AuxFn aux;
   lt::NameFn name;
   int q, d;
+  lt::UnitTile tile;     // the unit's 3-D two-step tile (launch_limits.hpp)
 };
 
 // every unit of dispatch.hpp's list, which is in the order of the ABI's enums: kUnits[2 * stencil + dtype]
-#define LT_UNIT_ROW(tag) {lt::step_##tag, lt::aux_##tag, lt::name_##tag, LT_FIELD(q, tag), LT_FIELD(d, tag)},
+#define LT_UNIT_ROW(tag) {lt::step_##tag, lt::aux_##tag, lt::name_##tag, LT_FIELD(q, tag), LT_FIELD(d, tag), \
+                          lt::two_step_tile<lt::LT_FIELD(lattice, tag), LT_FIELD(scalar, tag)>()},
 const Unit kUnits[] = {LT_UNITS(LT_UNIT_ROW)};
 #undef LT_UNIT_ROW
 static_assert(LT_D2Q9 == 0 && LT_D3Q19 == 1 && LT_D3Q27 == 2 && LT_D1Q3 == 3 && LT_D3Q15 == 4 && LT_F32 == 0 && LT_F64 == 1 &&
@@ -383,7 +386,7 @@ int resolve_lds(const lt_plan *p, long long workgroups) {
     n = (bytes > (128ll << 20) && workgroups >= 8192) ? (kbc32 ? 4 : 3) : 0;
   }
   if (n <= 0 || n >= 8) return 0;
-  const int per_wg = (160 * 1024 / n) & ~2047;   // the LDS allocator rounds up: stay below 160 KB / n
+  const int per_wg = ((int)lt::kLdsBudget / n) & ~2047;   // the LDS allocator rounds up: stay below 160 KB / n
   return per_wg > 65536 ? 65536 : per_wg;
 }
 
@@ -425,46 +428,20 @@ int resident_alloc(lt_plan *p) {
   return LT_OK;
 }
 
-// the two-step tile (the rule of unit.inc): rows of 256 bytes, 8 or 4 of them; rows = 0: no kernel
-struct TwoStepTile { int width, rows; };
-TwoStepTile two_step_tile_of(int d, int q, int esize, int n0, bool masked = false) {
-  if (d == 2) {
-    // 2-D (twostep2d.hpp): strips of `width` columns, the widest that divides the contiguous extent; one "row"
-    for (int w = 512; w >= 64; w /= 2)
-      if (n0 % w == 0) return {w, 1};
-    return {0, 0};
-  }
-  const long long per_node = (long long)esize * 3 * q;
-  const int width = 256 / esize;
-  int rows = per_node * (width + 2) * 10 <= 160 * 1024
-                 ? 8 : (esize == 4 && per_node * (width + 2) * 6 <= 160 * 1024 ? 4 : 0);
-  if (masked && rows == 8) {
-    // with boundaries the downward populations have a third LDS slot (lbm2m_kernel): where 8 rows then exceed
-    // the 160 KB, 4 rows are used (D3Q19 fp64: 168.6 KB -> 32 x 4 tiles, 101 KB); unit.inc applies the same rule
-    const int in_plane = q == 15 ? 5 : 9, crossing = (q - in_plane) / 2;
-    const long long lds8 = (long long)esize * ((width + 2) * 10 * (4 * crossing + 3 * in_plane + 3 * crossing) + 2 * q);
-    if (lds8 > 160 * 1024) rows = 0;   // (no masked two-step kernel there: 4-row tiles lost their A/B)
-  }
-  return {width, rows};
-}
+// the tile of the plan's two-step launch (launch_limits.hpp); rows = 0: no kernel
+using lt::TwoStepTile;
 TwoStepTile two_step_tile(const lt_plan *p) {
-  return two_step_tile_of(p->unit.d, p->unit.q, p->esize, p->n0, p->set.masked != 0);
+  return lt::two_step_tile_on(p->unit.tile, p->unit.d, p->n0, p->set.masked != 0);
 }
 
-// The 3-D two-step kernels address with 32-bit byte offsets: lbm2_kernel within a plane, lbm2m_kernel (buffer
-// instructions) within the whole field -- the rule of unit.inc's launch_twice / launch_twice_masked, which return
-// kNoKernel beyond it.  Asked BEFORE a plan is put on the two-step path, so that lt_run falls back to the one-step
-// kernel instead of failing at the first launch (Obstacle D3Q19 fp32 at 384^3 is 4.0 GiB).  With BGK in the reference
-// layout lbm2m_kernel has, for D3Q15 / D3Q19, a second instantiation with one buffer descriptor per population (BIG):
-// there a POPULATION must stay below 4 GiB, not the field.
-bool two_step_addressable(int d, int q, int esize, long long n0, long long n1, long long n2, bool masked,
-                          bool per_population = false) {
-  if (d != 3) return true;
-  if (masked) return (per_population ? 1ll : (long long)q) * n0 * n1 * n2 * esize < (1ll << 32);
-  return n0 * n1 * esize < (1ll << 32);
-}
-bool masked_big_exists(int layout, int collision, int q) {
-  return layout == LT_LAYOUT_REFERENCE && collision == LT_COLLISION_BGK && q <= 19;      // unit.inc, kHasBig
+// Can the 3-D two-step kernel of the plan's kind address the grid (launch_limits.hpp)?  Asked BEFORE a plan is put on
+// the two-step path, so that lt_run falls back to the one-step kernel instead of failing at the first launch (Obstacle
+// D3Q19 fp32 at 384^3 is 4.0 GiB).  distance: elements between the populations of the widest buffer in use
+bool two_step_addressable(const Unit &unit, int esize, long long n0, long long n1, long long distance, bool masked,
+                          int layout, int collision) {
+  if (unit.d != 3) return true;
+  if (!masked) return lt::plane_addressable(n0, n1, esize);
+  return lt::field_addressable(unit.q, distance, esize, lt::masked_per_population(layout, collision, unit.q));
 }
 
 // planes per workgroup of the two-step kernel.  One workgroup occupies a CU (150 KB of LDS), so the
@@ -475,9 +452,10 @@ bool masked_big_exists(int layout, int collision, int q) {
 // `override` > 0: the launch's own segment length in place of the plan's (lt_plan_set_two_step).
 int resolve_seg_len(const lt_plan *p, int planes, int override = 0) {
   const int asked = override > 0 ? override : p->seg_len;
-  if (asked > (p->set.masked ? 1 : 0)) return asked;
+  if (asked >= lt::min_segment(p->set.masked != 0)) return asked;
   const TwoStepTile tile = two_step_tile(p);
-  long long tiles = (long long)(p->n0 / tile.width) * (p->n1 / (tile.rows ? tile.rows : 8));
+  if (tile.rows == 0) return 1;                  // no kernel: the unit's launcher says so
+  long long tiles = (long long)(p->n0 / tile.width) * (p->n1 / tile.rows);
   long long cus = p->n_cu > 0 ? p->n_cu : 256;
   if (p->unit.d == 2) {
     // the sweep runs along a1.  Two workgroups would fit a CU in fp32 (27 row slots of width + 2 values =
@@ -487,7 +465,7 @@ int resolve_seg_len(const lt_plan *p, int planes, int override = 0) {
   }
   int best = 1;
   double best_score = -1.0;
-  for (int len = p->set.masked ? 2 : 1; len <= planes; ++len) {   // masked: the outlet's plane never opens a segment
+  for (int len = lt::min_segment(p->set.masked != 0); len <= planes; ++len) {
     const long long segs = (planes + len - 1) / len;
     if (!p->desc.ghost_planes && planes % len) continue;   // keep whole-grid launches evenly cut
     const long long blocks = tiles * segs;
@@ -542,7 +520,7 @@ int halo2(lt_plan *p, bool do_pack, void *f, int side, void *buf, void *stream) 
 // Returns the memory axis of the outlet (2 without one), or -1: not admitted.
 int masked_two_step_axis(const lt_plan *p) {
   if (!p->nsm_confined) return -1;
-  if (p->desc.n_boundaries > 15) return -1;          // two bits of kind per slot in one 32-bit register (MaskedPlanInfo)
+  if (p->desc.n_boundaries > lt::kMaskedTwoStepBoundaries) return -1;
   const int sweep = p->unit.d == 2 ? 1 : 2;          // the slowest memory axis
   if (p->unit.d < 2) return -1;
   int n_abb = 0, axis = 2;
@@ -552,7 +530,7 @@ int masked_two_step_axis(const lt_plan *p) {
     if (++n_abb > 1) return -1;
     const int ax = mem_axis_of(p, b.axis);
     if (ax == sweep) {
-      if (b.side != 1 || (sweep == 2 ? p->n2 : p->n1) < 3) return -1;
+      if (b.side != 1 || (sweep == 2 ? p->n2 : p->n1) < lt::kOutletSweepMin) return -1;
       axis = 2;                                      // "at the last plane / row of the sweep"
     } else if (ax == 0 && p->unit.d == 3) {
       if (!p->inlet_faces_outlet) return -1;
@@ -868,16 +846,13 @@ bool two_step_possible(lt_plan *p, const char **why) {
     *why = refused;
     return false;
   }
-  const TwoStepTile tile = two_step_tile(p);
-  if (tile.rows == 0 || p->n0 % tile.width != 0 || p->n1 % tile.rows != 0) {
+  if (!lt::tiles(two_step_tile(p), p->n0, p->n1)) {
     *why = "the grid does not tile (contiguous extent % 64 (fp32) / 32 (fp64), middle extent % 8 or 4)";
     return false;
   }
   // with masks the whole (padded) field is addressed with 32-bit offsets
-  const long long widest = std::max(pop_stride_of(p), p->resident != 0 ? resident_stride(p) : 0ll);
-  const bool big = masked_big_exists(p->desc.layout, p->desc.collision, p->unit.q);
-  if (!two_step_addressable(p->unit.d, p->unit.q, p->esize, p->n0, p->n1, p->n2, p->set.masked != 0, big) ||
-      (p->set.masked && p->unit.d == 3 && (big ? 1ll : (long long)p->unit.q) * widest * p->esize >= (1ll << 32))) {
+  const long long widest = std::max({p->N, pop_stride_of(p), p->resident != 0 ? resident_stride(p) : 0ll});
+  if (!two_step_addressable(p->unit, p->esize, p->n0, p->n1, widest, p->set.masked != 0, p->desc.layout, p->desc.collision)) {
     *why = p->set.masked ? "with boundaries the two-step kernel addresses with 32-bit offsets: q * nodes * sizeof(scalar) (BGK, "
                        "reference layout: nodes * sizeof(scalar)) must stay below 4 GiB"
                      : "a plane of the grid exceeds the two-step kernel's 32-bit in-plane offsets";
@@ -1028,10 +1003,9 @@ bool canary_ok(lt_plan *p) {
   return p->canary > 0;
 }
 
-constexpr int kManyMax = 8;        // == kManyMax of unit.inc
-// steps per many-step launch: a plan with an outlet recomputes one more ring of nodes around each tile.  3-D plans
-// have no many-step kernel (lt_stream_collide_many: LT_ERR_UNSUPPORTED); their range stays the removed kernel's two
-int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->set.masked && p->n_abb > 0) ? 1 : 0); }
+// steps per many-step launch (launch_limits.hpp).  3-D plans have no many-step kernel (lt_stream_collide_many:
+// LT_ERR_UNSUPPORTED); their range stays the removed kernel's two
+int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : lt::many_steps_max(p->set.masked && p->n_abb > 0); }
 
 // Several steps per launch (lbm_many_kernel): 2-D, tiles of 8 x 8, with masks at most one outlet.  Every
 // workgroup recomputes a halo of K - 1 nodes around its tile (K with an outlet), so this only pays while the
@@ -1046,7 +1020,7 @@ int many_max(const lt_plan *p) { return p->unit.d == 3 ? 2 : kManyMax - ((p->set
 bool many_step_wanted(lt_plan *p) {
   if (p->many == 0 || p->desc.ghost_planes || p->unit.d != 2 || multi_step_refusal(p, lt::kFusedMany) != nullptr) return false;
   if (p->set.masked && p->n_abb > 1) return false;
-  if (p->n0 % 8 != 0 || p->n1 % 8 != 0) return false;
+  if (p->n0 % lt::kManyTile != 0 || p->n1 % lt::kManyTile != 0) return false;
   if (!has_kernel(p->unit, kernel_selector(p, lt::kFusedMany))) return false;
   if (p->many == 1) return true;
   // automatic only where the many-step kernel is bit-identical to the one-step kernel, so that the
@@ -1989,7 +1963,7 @@ int lt_stream_collide_twice_slab(lt_plan *p, const void *f, void *out, double ta
     p->signal_target = 0;
   }
   const TwoStepTile tile = two_step_tile(p);
-  if (tile.rows == 0 || p->n0 % tile.width != 0 || p->n1 % tile.rows != 0)
+  if (!lt::tiles(tile, p->n0, p->n1))
     return fail(LT_ERR_UNSUPPORTED, "two steps per launch: the grid does not tile");
   // upper edge = second range [hi - 2, hi): one short segment; first range [lo, hi - 2) in segments of at least
   // two planes
@@ -2038,12 +2012,11 @@ int lt_two_step_limits(const lt_plan_desc *d, int32_t masked, int32_t *tile_widt
   if (d->dims != unit.d) return fail(LT_ERR_INVALID, "stencil is %d-dimensional, dims = %d", unit.d, d->dims);
   const int esize = d->dtype == LT_F32 ? 4 : 8;
   const auto [e0, e1, e2] = extents_of(*d, unit.d);
-  const TwoStepTile tile = unit.d >= 2 ? two_step_tile_of(unit.d, unit.q, esize, (int)e0, masked != 0) : TwoStepTile{0, 0};
+  const TwoStepTile tile = lt::two_step_tile_on(unit.tile, unit.d, (int)e0, masked != 0);
   if (tile_width) *tile_width = tile.width;
   if (tile_rows) *tile_rows = tile.rows;
   if (addressable)
-    *addressable = two_step_addressable(unit.d, unit.q, esize, e0, e1, e2, masked != 0,
-                                        masked_big_exists(d->layout, d->collision, unit.q)) ? 1 : 0;
+    *addressable = two_step_addressable(unit, esize, e0, e1, e0 * e1 * e2, masked != 0, d->layout, d->collision) ? 1 : 0;
   return LT_OK;
 }
 int lt_slab_two_step_message_blocks(lt_plan *p, int32_t *blocks) {

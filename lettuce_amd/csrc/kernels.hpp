@@ -25,6 +25,7 @@
 
 #include "dispatch.hpp"
 #include "lattice.hpp"
+#include "launch_limits.hpp"
 #include "mrt.hpp"
 #include "reduce.hpp"
 #include "twostep_roles.hpp"
@@ -1270,19 +1271,7 @@ __global__ void __launch_bounds__(kThreads, 4) lbm_kernel_occ4(const KParams<T> 
 // those of two lbm_kernel launches.  Redundant work: (T0+2)(T1+2)/(T0 T1) in the first step and
 // two extra planes per segment.  HBM traffic (PMC, 256^3): reads 1.05x one pass, writes 1.00x.
 // PACK: slab edge launches that also write the halo message.
-template <typename T, class S, int T0_, int T1>
-struct TwoStep {
-  static constexpr int T0 = T0_, H0 = T0 + 2, H1 = T1 + 2;
-  static constexpr int NI = H0 * H1;                    // intermediate nodes per plane
-  static constexpr int NO = T0 * T1;                    // output nodes per plane
-  static constexpr int THREADS = (NI + 63) / 64 * 64;
-  template <int LAYOUT, int E2>
-  static constexpr int count() {                        // populations with e along a2 == E2
-    int n = 0;
-    for (int q = 0; q < S::Q; ++q) n += MemMap<S, LAYOUT>::e(q, 2) == E2 ? 1 : 0;
-    return n;
-  }
-};
+// The tile geometry (TwoStep<T, S, T0, T1>) and its LDS footprint: launch_limits.hpp.
 
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

@@ -70,15 +70,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t field_rsrc(const T *field, uns
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(field), 0, (int)bytes, 0x00020000);
 }
 
-// LDS bytes of lbm2m_kernel: 4 slots of the upward, 3 of the in-plane, 3 of the downward populations, and the
-// populations of two uniform equilibrium boundaries
-constexpr int kEqCached = 2;
-template <typename T, class S, int LAYOUT, int T0, int T1>
-constexpr size_t two_step_masked_lds() {
-  using B = TwoStep<T, S, T0, T1>;
-  return sizeof(T) * ((size_t)B::NI * (4 * B::template count<LAYOUT, 1>() + 3 * B::template count<LAYOUT, 0>() +
-                                       3 * B::template count<LAYOUT, -1>()) + (size_t)kEqCached * S::Q);
-}
+// (LDS bytes of lbm2m_kernel, two_step_masked_lds, and kEqCached: launch_limits.hpp)
 
 // kinds of the plan's boundaries, two bits per slot, and the outlet's slot / plane (slot 0: no outlet)
 struct MaskedPlanInfo {
@@ -90,6 +82,8 @@ struct MaskedPlanInfo {
                                     // into VECTOR registers -- every test on the plan then looks divergent
   int abb_slot, abb_side, abb_plane, abb_axis;
 };
+static_assert(2 * (kMaskedTwoStepBoundaries + 1) == 8 * sizeof(unsigned),
+              "two bits of kind per slot, slot 0 and the boundaries of a plan, fill MaskedPlanInfo::kinds");
 template <typename T>
 __device__ __forceinline__ MaskedPlanInfo masked_plan_info(const KParams<T> &p) {
   MaskedPlanInfo m = {0u, 0u, 0, 0, 0, 1, -1, 2};

@@ -6,6 +6,7 @@
 
 #include "dispatch.hpp"
 #include "kernels.hpp"
+#include "launch_limits.hpp"
 #include "twostep_masked.hpp"
 #include "twostep2d.hpp"
 #include "spectrum.hpp"
@@ -127,15 +128,8 @@ namespace {
 
 using S = LT_S;
 using T = LT_T;
-// two-step tile: rows of 256 bytes (64 fp32 / 32 fp64 nodes -- narrower rows measured 12-39 % slower) and
-// as many rows (8, else 4) as three planes of all populations leave room for in the 160 KB of LDS:
-// D3Q15 / D3Q19 get 8 rows, D3Q27 fp32 gets 4 (0.63 -> 0.49 ms per update at 256^3); D3Q27 fp64
-// would fit with 32 x 4 tiles (4 waves per workgroup) but measured slower than one step (1.40 vs
-// 1.23 ms) and is not built
-constexpr size_t kTwicePerNode = sizeof(T) * 3 * S::Q;
-constexpr int kTwiceW = 256 / (int)sizeof(T);
-constexpr int kTwiceR = kTwicePerNode * (kTwiceW + 2) * 10 <= 160 * 1024 ? 8
-                        : (sizeof(T) == 4 && kTwicePerNode * (kTwiceW + 2) * 6 <= 160 * 1024 ? 4 : 0);
+// the unit's 3-D two-step tile (launch_limits.hpp)
+constexpr UnitTile kTile = two_step_tile<S, T>();
 
 // The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
 // to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
@@ -380,9 +374,8 @@ int launch_twice(const StepArgs &a, const NameBuf *name) {
                   S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
     using B = TwoStep<T, S, T0, T1>;
     if (name) return kernel_name(*name, "lbm2_kernel", LAYOUT, COLL, T0, T1, 1, MODE, 1, elided(SCHED));
-    // in-plane byte offsets are 32-bit in the kernel
-    if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 1 || a.masked || a.planes < 1 || a.p_stride != 1 ||
-        (long long)a.n0 * a.n1 * (long long)sizeof(T) >= (1ll << 32))
+    if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < min_segment(false) || a.masked || a.planes < 1 || a.p_stride != 1 ||
+        !plane_addressable(a.n0, a.n1, sizeof(T)))
       return kNoKernel;
     if (MODE == 2 && (!a.signal || a.planes2 < 2 || a.planes2 > a.seg_len || a.seg_len < 2)) return kNoKernel;
     using P = ParamsOf<COLL>;
@@ -412,7 +405,7 @@ int launch_twice(const StepArgs &a, const NameBuf *name) {
 
 // the sweeps of this object
 int sweep(const StepArgs &a, const NameBuf *name) {
-  constexpr int W = kTwiceW, R = kTwiceR;
+  constexpr int W = kTile.width, R = kTile.rows;
   if constexpr (R > 0) {
 #if LT_PART_IS(roles)
     // BGK with separate producer and consumer waves, where they won their A/B (DESIGN.md section 7)
@@ -464,42 +457,37 @@ int sweep(const StepArgs &a, const NameBuf *name) {
 
 #if LT_PART_IS(main)
 // Two fused steps per launch for plans with boundaries (twostep_masked.hpp, lbm2m_kernel): whole periodic
-// grid, reference layout.  api.hip admits the plan (masked_two_step_ok); here: the grid tiles, the field is
-// below 4 GiB (32-bit buffer offsets; BGK in the reference layout: a population is, and fields beyond 4 GiB run
-// the instantiation with a descriptor per population) and three LDS slots of the downward populations fit.
+// grid, reference layout.  api.hip admits the plan (masked_two_step_ok); here: the grid tiles and the field can be
+// addressed (launch_limits.hpp: fields beyond 4 GiB run the instantiation with a descriptor per population).
+// T1: the unit's rows with masks, 0 where the kernel's LDS does not fit
 template <int LAYOUT, int COLL, int T0, int T1, int AX = 2>
 int launch_twice_masked(const StepArgs &a, const NameBuf *name) {
-  // BGK / streaming on tiles of 8 rows (4 for D3Q27 fp32).  KBC inside this kernel (256 VGPRs, spills: not faster
-  // than one update per launch) and 4-row fp64 tiles of D3Q19 (slower than one update per launch) lost their A/B
+  // BGK / streaming.  KBC inside this kernel (256 VGPRs, spills: not faster than one update per launch) lost its A/B
   // (DESIGN.md section 4)
-  if constexpr (S::D == 3 && T0 > 0 && (COLL == kCollNone || COLL == kCollBgk) && !(sizeof(T) == 8 && T1 == 4)) {
-    if constexpr (two_step_masked_lds<T, S, LAYOUT, T0, T1>() <= 160 * 1024) {
-      using B = TwoStep<T, S, T0, T1>;
-      if (name) return kernel_name(*name, "lbm2m_kernel", LAYOUT, COLL, T0, T1, AX);
-      // (D3Q27: 26.7 GLUPS at 384^3 against 27.2 with one update per launch -- its 2 x 27 population bases spill;
-      // D3Q19: 52-55 GLUPS at 384^3 / 512^3 against 38: profiles/r04y_large_obstacle.jsonl)
-      constexpr bool kHasBig = LAYOUT == 0 && COLL == kCollBgk && S::Q <= 19;
-      const long long pop_bytes = std::max(std::max(a.stride_in, a.stride_out), (long long)a.n0 * a.n1 * a.n2) * (long long)sizeof(T);
-      const bool big = (long long)S::Q * pop_bytes >= (1ll << 32);
-      if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < 2 || !a.masked || a.planes < 2 || a.p_stride != 1 ||
-          a.planes2 != 0 || a.pack_lo || a.pack_hi || (big && (!kHasBig || pop_bytes >= (1ll << 32))))
-        return kNoKernel;
-      KParams<T> p = params_of<KParams<T>>(a, a.n2);
-      p.p_end = a.p_begin + a.planes;      // the output planes, a.seg_len of them per workgroup
-      const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len));
-      if constexpr (kHasBig) {
-        if (big) {
-          hipLaunchKernelGGL((lbm2m_kernel<T, S, LAYOUT, COLL, T0, T1, AX, true>), dim3(grid), dim3(B::THREADS), 0,
-                             a.stream, p, a.seg_len);
-          return (int)hipGetLastError();
-        }
-      }
-      hipLaunchKernelGGL((lbm2m_kernel<T, S, LAYOUT, COLL, T0, T1, AX>), dim3(grid), dim3(B::THREADS), 0, a.stream,
-                         p, a.seg_len);
-      return (int)hipGetLastError();
-    } else {
+  if constexpr (S::D == 3 && T1 > 0 && (COLL == kCollNone || COLL == kCollBgk)) {
+    static_assert(two_step_masked_lds<T, S, LAYOUT, T0, T1>() <= kLdsBudget, "the unit's tile with masks fits the LDS");
+    using B = TwoStep<T, S, T0, T1>;
+    if (name) return kernel_name(*name, "lbm2m_kernel", LAYOUT, COLL, T0, T1, AX);
+    // (D3Q27: 26.7 GLUPS at 384^3 against 27.2 with one update per launch -- its 2 x 27 population bases spill;
+    // D3Q19: 52-55 GLUPS at 384^3 / 512^3 against 38: profiles/r04y_large_obstacle.jsonl)
+    constexpr bool kHasBig = masked_per_population(LAYOUT, COLL, S::Q);
+    const long long distance = std::max(std::max(a.stride_in, a.stride_out), (long long)a.n0 * a.n1 * a.n2);
+    if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < min_segment(true) || !a.masked || a.planes < min_segment(true) ||
+        a.p_stride != 1 || a.planes2 != 0 || a.pack_lo || a.pack_hi || !field_addressable(S::Q, distance, sizeof(T), kHasBig))
       return kNoKernel;
+    KParams<T> p = params_of<KParams<T>>(a, a.n2);
+    p.p_end = a.p_begin + a.planes;      // the output planes, a.seg_len of them per workgroup
+    const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len));
+    if constexpr (kHasBig) {
+      if (!field_addressable(S::Q, distance, sizeof(T), false)) {
+        hipLaunchKernelGGL((lbm2m_kernel<T, S, LAYOUT, COLL, T0, T1, AX, true>), dim3(grid), dim3(B::THREADS), 0,
+                           a.stream, p, a.seg_len);
+        return (int)hipGetLastError();
+      }
     }
+    hipLaunchKernelGGL((lbm2m_kernel<T, S, LAYOUT, COLL, T0, T1, AX>), dim3(grid), dim3(B::THREADS), 0, a.stream,
+                       p, a.seg_len);
+    return (int)hipGetLastError();
   } else {
     return kNoKernel;
   }
@@ -512,8 +500,8 @@ template <int COLL, int W, bool MASKED>
 int launch_twice2d(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 2 && (COLL == kCollNone || COLL == kCollBgk)) {
     if (name) return kernel_name(*name, MASKED ? "lbm2d2m_kernel" : "lbm2d2_kernel", COLL, W);
-    if (a.layout != 0 || (a.masked != 0) != MASKED || a.n0 % W != 0 || a.seg_len < (MASKED ? 2 : 1) ||
-        a.n1 < (MASKED ? 3 : 1) || a.n2 != 1)
+    if (a.layout != 0 || (a.masked != 0) != MASKED || a.n0 % W != 0 || a.seg_len < min_segment(MASKED) ||
+        a.n1 < (MASKED ? kOutletSweepMin : 1) || a.n2 != 1)
       return kNoKernel;
     const KParams<T> p = params_of<KParams<T>>(a, 1);      // n2 = 1: the field is one plane
     const unsigned grid = (unsigned)((a.n0 / W) * ((a.n1 + a.seg_len - 1) / a.seg_len));
@@ -526,17 +514,15 @@ int launch_twice2d(const StepArgs &a, const NameBuf *name) {
   }
 }
 
-// Up to kManyMax steps per launch on small 2-D grids (kernels.hpp, lbm_many_kernel)
-constexpr int kManyTile = 8, kManyMax = 8;
+// Up to kManyMax steps per launch on small 2-D grids (kernels.hpp, lbm_many_kernel; launch_limits.hpp)
 template <int COLL, bool MASKED>
 int launch_many(const StepArgs &a, const NameBuf *name) {
   if constexpr (S::D == 2 && (COLL != kCollKbc || LT_HAS_KBC)) {
     using G = ManyStep2D<kManyTile, kManyTile, kManyMax>;
     if (name) return kernel_name(*name, "lbm_many_kernel", COLL, kManyTile, kManyTile, kManyMax, elided(MASKED));
-    // plans with an outlet recompute one more ring: one step fewer per launch
     const int outlets = MASKED ? a.n_abb : 0;
     if (a.layout != 0 || (a.masked != 0) != MASKED || a.n0 % kManyTile != 0 || a.n1 % kManyTile != 0 || a.seg_len < 1 ||
-        a.seg_len > kManyMax - (outlets ? 1 : 0) || a.planes != a.n2 || outlets > 1)
+        a.seg_len > many_steps_max(outlets > 0) || a.planes != a.n2 || outlets > 1)
       return kNoKernel;
     KParams<T> p = params_of<KParams<T>>(a, 1);      // n2 = 1: the field is one plane ...
     p.wrap2 = 1;                                     // ... which is its own neighbour along a2
@@ -555,12 +541,12 @@ int many_of(const StepArgs &a, const NameBuf *name) {
   return a.masked ? launch_many<C, true>(a, name) : launch_many<C, false>(a, name);
 }
 
-// strips of a.strip columns (api.hip: the widest of 512 / 256 / 128 / 64 that divides the contiguous extent)
+// strips of a.strip columns (launch_limits.hpp, strip_width)
 template <int C>
 int strips_of(const StepArgs &a, const NameBuf *name) {
 #define LT_TRY_STRIP(W) \
   if (a.strip == W) return a.masked ? launch_twice2d<C, W, true>(a, name) : launch_twice2d<C, W, false>(a, name);
-  LT_TRY_STRIP(512) LT_TRY_STRIP(256) LT_TRY_STRIP(128) LT_TRY_STRIP(64)
+  LT_STRIP_WIDTHS(LT_TRY_STRIP)
 #undef LT_TRY_STRIP
   return kNoKernel;
 }
@@ -568,13 +554,11 @@ int strips_of(const StepArgs &a, const NameBuf *name) {
 #if LT_IS_3D
 // two steps per launch of a 3-D unit: with boundaries here, without in the unit's part sweeps
 int twice_3d(const StepArgs &a, const NameBuf *name) {
-  constexpr int W = kTwiceW, R = kTwiceR;
+  constexpr int W = kTile.width, R = kTile.rows;
   if constexpr (R > 0) {
     if (!a.masked) return LT_CAT(twice_, LT_TAG)(a, name);
     // a.abb_axis: memory axis of the plan's outlet (2 also for plans without one)
-    // rows of the tile with boundaries: the third slot of the downward populations must fit too (D3Q19 fp64:
-    // 8 rows are 168.6 KB -> 4 rows; the rule of api.hip's two_step_tile_of)
-    constexpr int RM = (R == 8 && two_step_masked_lds<T, S, 0, W, 8>() > 160 * 1024) ? 4 : R;
+    constexpr int RM = kTile.rows_masked;
 #define LT_TRY_MASKED_TWICE(LAYOUT_, COLL_, AX_)                       \
   if (a.layout == LAYOUT_ && a.coll == COLL_ && a.abb_axis == AX_)     \
     return launch_twice_masked<LAYOUT_, COLL_, W, RM, AX_>(a, name);

@@ -318,6 +318,22 @@ def test_two_step_admission_by_descriptor_knows_the_4_gib_limit(engine_library):
     assert limits("D3Q19", torch.float32, [512, 512, 212], True, layout=1, ghosts=2) == (64, 8, False)
     assert limits("D3Q19", torch.float32, [512, 512, 208], True, layout=1, ghosts=2) == (64, 8, True)
     assert limits("D2Q9", torch.float32, [4096, 4096], True) == (512, 1, True)
+    # every unit's tile, without and with masks (csrc/launch_limits.hpp): rows of 256 bytes; 8 of them where the kernel's
+    # LDS fits the 163 840 B of a CU, else 4 in fp32 only.  Hand-checked against the LDS arithmetic: D3Q19 fp32 64 x 8
+    # with masks 163 832 B; D3Q19 fp64 32 x 8 with masks 168 944 B: none; D3Q27 fp32 64 x 4 with masks 142 776 B
+    table = {("D3Q15", torch.float32): (64, 8, 8), ("D3Q15", torch.float64): (32, 8, 8),
+             ("D3Q19", torch.float32): (64, 8, 8), ("D3Q19", torch.float64): (32, 8, 0),
+             ("D3Q27", torch.float32): (64, 4, 4), ("D3Q27", torch.float64): (32, 0, 0)}
+    for (stencil, dtype), (width, rows, rows_masked) in table.items():
+        assert limits(stencil, dtype, [256] * 3, False) == (width, rows, True), (stencil, dtype)
+        assert limits(stencil, dtype, [256] * 3, True) == (width, rows_masked, True), (stencil, dtype)
+    for dtype in (torch.float32, torch.float64):
+        for masked in (False, True):
+            # D2Q9: the widest strip of 512 / 256 / 128 / 64 columns that divides the contiguous extent, as one "row"
+            assert limits("D2Q9", dtype, [4096, 4096], masked) == (512, 1, True)
+            assert limits("D2Q9", dtype, [4096, 192], masked) == (64, 1, True)
+            assert limits("D2Q9", dtype, [4096, 96], masked) == (0, 0, True)
+            assert limits("D1Q3", dtype, [256], masked) == (0, 0, True)
     bad = _native._PlanDesc()
     bad.abi_version, bad.stencil, bad.dims = 2, 1, 2
     assert lib.lt_two_step_limits(c.byref(bad), 0, None, None, None) == 1 and b"3-dimensional" in lib.lt_last_error()
