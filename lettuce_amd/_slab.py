@@ -23,6 +23,8 @@ Transports (``transport=``):
             receiver waits for the signal and unpacks.  No copy kernel competes with the interior
             launch for HBM.  Two window parities make the reuse safe without a barrier (see
             ``_PeerWindow``).
+All three are one interface to the drivers (``_HaloTransport``: ``targets`` / ``start`` / ``finish``), and received
+messages are always named in the order (from below, from above).
 
 Schedule of one fused step (pull scheme, state = post-collision populations f*):
   communication stream (high priority)          compute stream
@@ -111,7 +113,7 @@ def _copy_streams(device, n):
     """the streams the copy transport issues its two directions on (one pair per device for the whole process, like
     the communication stream); n = 1: both directions on one stream"""
     if n == 1:
-        return [None, None]                      # the stream that is current when send() is called
+        return [None, None]                      # the stream that is current when start() is called
     out = []
     for k in (0, 1):
         key = (str(device), "copy", k)
@@ -128,7 +130,81 @@ def _crossing_sets(stencil):
     return up, down
 
 
-class _PeerWindow:
+def _ring_requests(send_down, send_up, from_below, from_above, slab: ZSlab, group, tags):
+    """One batched point-to-point swap with both z-neighbours: ``send_down`` goes to the lower neighbour under
+    ``tags[0]``, ``send_up`` to the upper one under ``tags[1]``, and theirs arrive in ``from_above`` /
+    ``from_below``.  Returns the requests to wait for."""
+    down, up = tags
+    ops = [dist.P2POp(dist.isend, send_down, slab.prev, group, tag=down),
+           dist.P2POp(dist.irecv, from_above, slab.next, group, tag=down),
+           dist.P2POp(dist.isend, send_up, slab.next, group, tag=up),
+           dist.P2POp(dist.irecv, from_below, slab.prev, group, tag=up)]
+    return dist.batch_isend_irecv(ops)
+
+
+class _HaloTransport:
+    """What a driver asks of a halo transport.  A message is a ``[blocks, ny, nx]`` tensor; "down" is the message to
+    the lower neighbour, "up" the one to the upper neighbour.
+
+    ``targets()``        (down, up): the buffers that the pack launch -- or a launch that packs by itself -- writes for
+                         the coming exchange.
+    ``start(down, up)``  on the current stream: the two messages travel from there.
+    ``finish()``         on the current stream: waits for the neighbours' messages of the exchange that was started and
+                         returns them as (from_below, from_above) -- the one order of this file.
+    ``timed_out()``      did a wait give up since the last call?  (Only the copy transport can say yes.)
+    ``close()``          release what the transport mapped.
+
+    Every transport holds the four message buffers a driver has always allocated: the point-to-point transport uses
+    all of them, the copy transport the send pair, the peer window none (its launches store into the neighbours'
+    windows)."""
+
+    def __init__(self, shape, dtype, device, slab: ZSlab, group):
+        new = lambda: torch.empty(list(shape), dtype=dtype, device=device)   # noqa: E731
+        self.send_up, self.send_down, self.from_below, self.from_above = new(), new(), new(), new()
+        self.slab, self.group = slab, group
+        # rehearsal switch: send to / receive from oneself through the process group even with a
+        # single rank, to exercise the point-to-point path on a one-GPU box
+        self.forced_p2p = (os.environ.get("LT_SLAB_FORCE_P2P") == "1" and dist.is_available()
+                           and dist.is_initialized())
+        # the process group moves device tensors from the host side (gloo): also asked by the observables
+        self.host = (slab.world_size > 1 or self.forced_p2p) and dist.get_backend(group) != "nccl"
+
+    def targets(self):
+        return self.send_down, self.send_up
+
+    def timed_out(self) -> bool:
+        return False
+
+    def close(self):
+        pass
+
+
+class _PointToPoint(_HaloTransport):
+    """``transport="rccl"``: batched isend / irecv through the process group (RCCL over xGMI, gloo in the CPU tests),
+    and the self-exchange of a single rank, which needs no transport at all: what left upwards arrives from below."""
+
+    _requests, _arrived = (), None
+
+    def start(self, down, up):
+        if self.slab.world_size == 1 and not self.forced_p2p:
+            self._requests, self._arrived = (), (up, down)
+            return
+        if self.host and down.is_cuda:
+            # gloo moves device tensors from the host side without stream semantics (only
+            # used by tests that put two ranks on one GPU): make the packed data visible
+            torch.cuda.current_stream().synchronize()
+        self._requests = _ring_requests(down, up, self.from_below, self.from_above, self.slab, self.group, (1, 2))
+        self._arrived = (self.from_below, self.from_above)
+
+    def finish(self):
+        for r in self._requests:
+            r.wait()
+        if self._requests and self.host and self._arrived[0].is_cuda:
+            torch.cuda.current_stream().synchronize()
+        return self._arrived
+
+
+class _PeerWindow(_HaloTransport):
     """Receive windows for the one-sided ghost-plane transfer.
 
     ``local[p, 0]`` receives the e_z = +1 populations from the lower neighbour (they fill my lower
@@ -143,7 +219,7 @@ class _PeerWindow:
 
     def __init__(self, shape, dtype, device, slab: ZSlab, group):
         import torch.distributed._symmetric_memory as symm
-        self.slab = slab
+        super().__init__(shape, dtype, device, slab, group)
         full = (2, 2) + tuple(shape)
         with torch.cuda.device(device):
             self.buf = symm.empty(full, dtype=dtype, device=device)
@@ -161,19 +237,20 @@ class _PeerWindow:
         p = self.count & 1
         return self.at_prev[p, 1], self.at_next[p, 0]
 
-    def signal(self):
-        """after the stores of this exchange (same stream): tell both neighbours"""
+    def start(self, down, up):
+        """after the stores of this exchange into ``targets()`` (same stream): tell both neighbours -- the messages
+        themselves are in their windows already"""
         s, h = self.slab, self.handle
         h.put_signal(s.prev, 1, self.WAIT_MS)
         h.put_signal(s.next, 0, self.WAIT_MS)
 
-    def wait(self):
-        """wait for both neighbours' signals; returns (message from above, message from below)"""
+    def finish(self):
+        """wait for both neighbours' signals; returns (message from below, message from above)"""
         p, s, h = self.count & 1, self.slab, self.handle
         h.wait_signal(s.next, 1, self.WAIT_MS)
         h.wait_signal(s.prev, 0, self.WAIT_MS)
         self.count += 1
-        return self.local[p, 1], self.local[p, 0]
+        return self.local[p, 0], self.local[p, 1]
 
 
 class _DevicePointer:
@@ -184,7 +261,7 @@ class _DevicePointer:
                                          "data": (int(ptr), False), "version": 2}
 
 
-class _CopyWindow:
+class _CopyWindow(_HaloTransport):
     """Receive windows for the halo transport that needs no compute unit (``transport="copy"``).
 
     Every rank allocates one block of device memory the other processes of the node can map (``lt_ipc_alloc``):
@@ -215,8 +292,9 @@ class _CopyWindow:
                  streams: Optional[int] = None):
         import ctypes
         from ._native import load_library
+        super().__init__(shape, dtype, device, slab, group)
         self.lib = load_library()
-        self.slab, self.device, self.dtype = slab, torch.device(device), dtype
+        self.device, self.dtype = torch.device(device), dtype
         self.shape = tuple(int(v) for v in shape)
         self.engine, self.flag_how = int(engine), int(flag_how)
         esize = torch.empty((), dtype=dtype).element_size()
@@ -279,7 +357,7 @@ class _CopyWindow:
         if code != 0:
             raise LettuceException(f"copy transport: {self.lib.lt_last_error().decode('utf-8', 'replace')}")
 
-    def send(self, send_down: torch.Tensor, send_up: torch.Tensor):
+    def start(self, send_down: torch.Tensor, send_up: torch.Tensor):
         """behind what the current stream holds so far: my downward message into the lower neighbour's slot (p, 1), my
         upward one into the upper neighbour's slot (p, 0), each followed by the counter of this exchange -- on the
         current stream, or (LT_SLAB_COPY_STREAMS=2) on a stream of its own per direction, after which the current
@@ -305,16 +383,16 @@ class _CopyWindow:
             if side is not cur:
                 cur.wait_stream(side)
 
-    def wait(self):
-        """on the current stream: wait for both neighbours' messages of this exchange; returns (message from above,
-        message from below)"""
+    def finish(self):
+        """on the current stream: wait for both neighbours' messages of this exchange; returns (message from below,
+        message from above)"""
         import ctypes
         p, stream = self.count & 1, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         for d in (1, 0):
             self._check(self.lib.lt_flag_wait(ctypes.c_void_p(self.flags + 8 * d), self.count + 1,
                                               ctypes.c_void_p(self._timed_out.data_ptr()), stream))
         self.count += 1
-        return self._local[p][1], self._local[p][0]
+        return self._local[p][0], self._local[p][1]
 
     def timed_out(self) -> bool:
         """did a polling wave give up since the last call?  (synchronises)"""
@@ -514,32 +592,27 @@ class SlabSimulation:
         flow._f_next = None
         # one contiguous message per direction: [n_crossing, ny, nx]
         shape = [self._message_blocks(flow.stencil), ny, nx]
-        new = lambda: torch.empty(shape, dtype=self.f.dtype, device=self.f.device)   # noqa: E731
-        self._send_up, self._send_down, self._recv_up, self._recv_down = new(), new(), new(), new()
         self._comm = _comm_stream(self.context.device, comm_priority) if self.overlap else None
-        # rehearsal switch: send to / receive from oneself through the process group even with a
-        # single rank, to exercise the point-to-point path on a one-GPU box
-        self._force_p2p = (os.environ.get("LT_SLAB_FORCE_P2P") == "1" and dist.is_available()
-                           and dist.is_initialized())
-        self._host_transport = ((slab.world_size > 1 or self._force_p2p)
-                                and dist.get_backend(group) != "nccl")
         if transport not in ("rccl", "window", "copy"):
             raise LettuceException(f"unknown slab transport '{transport}'")
         self.transport = transport
-        self._window = None
+        self._window = None          # the transport again, under the name of its kind (bench.py and the tests ask)
         self._cw = None
         if transport == "copy":
             if self.context.device.type != "cuda" or (slab.world_size > 1 and not (dist.is_available() and dist.is_initialized())):
                 raise LettuceException("the copy transport needs device memory (and an initialised process group "
                                        "with more than one rank)")
-            self._cw = _CopyWindow(shape, self.f.dtype, self.f.device, slab, group,
-                                   engine=int(os.environ.get("LT_SLAB_COPY_ENGINE", "0")),
-                                   flag_how=int(os.environ.get("LT_SLAB_FLAG_HOW", "1")), streams=copy_streams)
-        if transport == "window":
+            self._halo = self._cw = _CopyWindow(shape, self.f.dtype, self.f.device, slab, group,
+                                                engine=int(os.environ.get("LT_SLAB_COPY_ENGINE", "0")),
+                                                flag_how=int(os.environ.get("LT_SLAB_FLAG_HOW", "1")),
+                                                streams=copy_streams)
+        elif transport == "window":
             if self.context.device.type != "cuda" or not (dist.is_available() and dist.is_initialized()):
                 raise LettuceException("the window transport needs device memory and an initialised "
                                        "process group")
-            self._window = _PeerWindow(shape, self.f.dtype, self.f.device, slab, group)
+            self._halo = self._window = _PeerWindow(shape, self.f.dtype, self.f.device, slab, group)
+        else:
+            self._halo = _PointToPoint(shape, self.f.dtype, self.f.device, slab, group)
         # window transport: the exchange can ride on the compute stream (see _fused_step); measured
         # on one MI355X the single-step driver is better off with two streams (0.437 vs 0.454
         # ms/step), the two-step driver marginally with one (0.356 vs 0.361) -- see
@@ -548,6 +621,14 @@ class SlabSimulation:
 
     def _message_blocks(self, stencil) -> int:
         return len(self.up)
+
+    @property
+    def _force_p2p(self) -> bool:
+        return self._halo.forced_p2p
+
+    @property
+    def _host_transport(self) -> bool:
+        return self._halo.host
 
     # ---- the populations -------------------------------------------------------------------------
     # ``f`` holds post-streaming populations (lettuce's convention) whenever somebody looks; between batches
@@ -644,65 +725,32 @@ class SlabSimulation:
         the e_z = -1 populations of my plane 1 go to the lower neighbour's upper ghost plane, the
         e_z = +1 populations of my top plane to the upper neighbour's lower ghost plane.  One
         packed message per direction.  Returns a callable that completes the exchange (waits
-        for the transfers and unpacks)."""
-        nzl, s = self.nzl, self.slab
-        if self._cw is not None:
-            if not packed:
-                self._pack(buf, 1, -1, self._send_down)
-                self._pack(buf, nzl, +1, self._send_up)
-            self._cw.send(self._send_down, self._send_up)
-
-            def finish_copy():
-                from_above, from_below = self._cw.wait()
-                self._unpack(buf, nzl + 1, -1, from_above)
-                self._unpack(buf, 0, +1, from_below)
-            return finish_copy
-        nzl, s = self.nzl, self.slab
-        if self._window is not None:
-            if not packed:
-                to_prev, to_next = self._window.targets()
-                self._pack(buf, 1, -1, to_prev)
-                self._pack(buf, nzl, +1, to_next)
-            self._window.signal()
-
-            def finish_window():
-                from_above, from_below = self._window.wait()
-                self._unpack(buf, nzl + 1, -1, from_above)
-                self._unpack(buf, 0, +1, from_below)
-            return finish_window
+        for the transfers and unpacks).  What a driver adds is how a message is packed from ``buf`` and unpacked
+        into it (``_pack_messages``, ``_unpack_messages``)."""
+        halo = self._halo
+        down, up = halo.targets()
         if not packed:
-            self._pack(buf, 1, -1, self._send_down)
-            self._pack(buf, nzl, +1, self._send_up)
-        if s.world_size == 1 and not self._force_p2p:
-            recv_down, recv_up, reqs = self._send_down, self._send_up, []
-        else:
-            recv_down, recv_up = self._recv_down, self._recv_up
-            if self._host_transport and buf.is_cuda:
-                # gloo moves device tensors from the host side without stream semantics (only
-                # used by tests that put two ranks on one GPU): make the packed data visible
-                torch.cuda.current_stream().synchronize()
-            ops = [dist.P2POp(dist.isend, self._send_down, s.prev, self.group, tag=1),
-                   dist.P2POp(dist.irecv, recv_down, s.next, self.group, tag=1),
-                   dist.P2POp(dist.isend, self._send_up, s.next, self.group, tag=2),
-                   dist.P2POp(dist.irecv, recv_up, s.prev, self.group, tag=2)]
-            reqs = dist.batch_isend_irecv(ops)
+            self._pack_messages(buf, down, up)
+        halo.start(down, up)
 
         def finish():
-            for r in reqs:
-                r.wait()
-            if reqs and self._host_transport and buf.is_cuda:
-                torch.cuda.current_stream().synchronize()
-            self._unpack(buf, nzl + 1, -1, recv_down)
-            self._unpack(buf, 0, +1, recv_up)
+            self._unpack_messages(buf, *halo.finish())
         return finish
+
+    def _pack_messages(self, buf, down, up):
+        self._pack(buf, 1, -1, down)
+        self._pack(buf, self.nzl, +1, up)
+
+    def _unpack_messages(self, buf, from_below, from_above):
+        self._unpack(buf, self.nzl + 1, -1, from_above)
+        self._unpack(buf, 0, +1, from_below)
 
     # ---- stepping --------------------------------------------------------------------------------
     def _boundary_planes(self, cur, nxt, tau) -> bool:
         """Stream-collide planes 1 and nz_local; returns True when the launch also packed the
-        crossing populations into the send buffers."""
+        crossing populations into the transport's ``targets()``."""
         if hasattr(self.engine, "stream_collide_plane_pair_packed"):
-            down, up = ((self._send_down, self._send_up) if self._window is None
-                        else self._window.targets())
+            down, up = self._halo.targets()
             self.engine.stream_collide_plane_pair_packed(cur, nxt, tau, 1, self.nzl, down, up)
             return True
         self.engine.stream_collide_planes(cur, nxt, tau, 1, 2)
@@ -782,7 +830,7 @@ class SlabSimulation:
         if self.context.device.type == "cuda":
             torch.cuda.synchronize(self.context.device)
         elapsed = timer() - beg
-        if self._cw is not None and self._cw.timed_out():
+        if self._halo.timed_out():
             # a polling wave gave up (it waits about a second): the launch behind it read a message that had not
             # arrived.  Raised here, after the exchanges of the call, so that the ranks stay in step
             raise LettuceException("copy transport: timed out waiting for a neighbour's halo message; the "
@@ -839,11 +887,7 @@ class SlabSimulation:
         if host:
             send_down, send_up = send_down.cpu(), send_up.cpu()
         from_above, from_below = torch.empty_like(send_down), torch.empty_like(send_up)
-        ops = [dist.P2POp(dist.isend, send_down, s.prev, self.group, tag=11),
-               dist.P2POp(dist.irecv, from_above, s.next, self.group, tag=11),
-               dist.P2POp(dist.isend, send_up, s.next, self.group, tag=12),
-               dist.P2POp(dist.irecv, from_below, s.prev, self.group, tag=12)]
-        for r in dist.batch_isend_irecv(ops):
+        for r in _ring_requests(send_down, send_up, from_below, from_above, s, self.group, (11, 12)):
             r.wait()
         u_ext[:, nzl + 3:] = from_above.to(u_ext.device)
         u_ext[:, :3] = from_below.to(u_ext.device)
@@ -953,8 +997,9 @@ class TwoStepSlabSimulation(SlabSimulation):
         if direct is None:
             direct = os.environ.get("LT_SLAB_DIRECT", "1") == "1" and not self._signalled
         self._direct = bool(direct)
-        self._ghost_src = None        # (message from below, message from above) while the ghost planes of the
-        self._parity = 0              # current populations are still in the receive buffers (direct schedule)
+        self._ghost_src = None        # (message from below, message from above) while the ghost planes of the current
+        #                               populations are still in the receive buffers (direct schedule)
+        self._parity = 0              # the pair of send buffers the next direct double step writes
         if fused_remote_pack is None:
             self._fused_remote = os.environ.get("LT_SLAB_FUSED_REMOTE_PACK") == "1"
             self.ONE_STREAM_WINDOWS = os.environ.get("LT_SLAB_ONE_STREAM") == "1"
@@ -1014,46 +1059,23 @@ class TwoStepSlabSimulation(SlabSimulation):
         """the ghost planes of ``buf`` are about to be read by a launch that takes them from the field: scatter
         the messages the direct schedule left in the receive buffers"""
         if self._ghost_src is not None:
-            from_below, from_above = self._ghost_src
-            self._ghost_src = None
-            self.engine.unpack_two_step(buf, +1, from_above)
-            self.engine.unpack_two_step(buf, -1, from_below)
+            self._unpack_messages(buf, *self._ghost_src)
 
     def _present(self):
         if self._pending is not None:
             self._field_ghosts(self._pending[0])
         super()._present()
 
-    def _transfer(self, send_down, send_up):
-        """the halo messages of one double step travel (no packing, no unpacking); returns (message from below,
-        message from above) once they have arrived -- in stream order"""
-        s = self.slab
-        if self._cw is not None:
-            self._cw.send(send_down, send_up)
-            from_above, from_below = self._cw.wait()
-            return from_below, from_above
-        if s.world_size == 1 and not self._force_p2p:
-            return send_up, send_down                 # my own messages: what left upwards arrives from below
-        host = self._host_transport and send_down.is_cuda
-        if host:
-            torch.cuda.current_stream().synchronize()
-        ops = [dist.P2POp(dist.isend, send_down, s.prev, self.group, tag=1),
-               dist.P2POp(dist.irecv, self._recv_down, s.next, self.group, tag=1),
-               dist.P2POp(dist.isend, send_up, s.next, self.group, tag=2),
-               dist.P2POp(dist.irecv, self._recv_up, s.prev, self.group, tag=2)]
-        for r in dist.batch_isend_irecv(ops):
-            r.wait()
-        if host:
-            torch.cuda.current_stream().synchronize()
-        return self._recv_up, self._recv_down
-
     def _double_step_direct(self, cur, nxt, tau):
-        eng, lo, hi, edge = self.engine, self.lo, self.hi, self.edge_planes
+        eng, lo, hi, edge, halo = self.engine, self.lo, self.hi, self.edge_planes, self._halo
+        send_down, send_up = halo.targets()
         if self._send2 is None:
             # the messages of consecutive double steps alternate between two pairs of buffers: without a transport
-            # (one rank) the launch that reads the last messages writes the next ones
-            self._send2 = (torch.empty_like(self._send_down), torch.empty_like(self._send_up))
-        send_down, send_up = (self._send_down, self._send_up) if self._parity == 0 else self._send2
+            # (one rank) ``finish()`` hands back the send buffers themselves, and the launch that reads the last
+            # messages writes the next ones
+            self._send2 = (torch.empty_like(send_down), torch.empty_like(send_up))
+        if self._parity:
+            send_down, send_up = self._send2
         self._parity ^= 1
         below, above = self._ghost_src if self._ghost_src is not None else (None, None)
         eng.stream_collide_twice_edges_direct(cur, nxt, tau, edge, below, above, send_down, send_up)
@@ -1065,66 +1087,26 @@ class TwoStepSlabSimulation(SlabSimulation):
                 eng.stream_collide_twice_planes(cur, nxt, tau, lo + edge, hi - edge)
             self._comm.wait_event(edges_done)
             with torch.cuda.stream(self._comm):
-                self._ghost_src = self._transfer(send_down, send_up)
+                halo.start(send_down, send_up)
+                self._ghost_src = halo.finish()
             compute.wait_stream(self._comm)
         else:
-            self._ghost_src = self._transfer(send_down, send_up)
+            halo.start(send_down, send_up)
+            self._ghost_src = halo.finish()
             if hi - lo > 2 * edge:
                 eng.stream_collide_twice_planes(cur, nxt, tau, lo + edge, hi - edge)
 
     # ---- halo exchange -------------------------------------------------------------------------
-    def _exchange(self, buf: torch.Tensor, packed: bool = False):
-        """Fill the four ghost planes of ``buf`` (post-collision populations).  My message for the
-        lower neighbour comes from my two lowest interior planes and lands in its upper ghost
-        planes, and vice versa."""
-        eng, s = self.engine, self.slab
-        self._ghost_src = None                        # this exchange ends in the ghost planes of ``buf``
-        if self._cw is not None:
-            if not packed:
-                eng.pack_two_step(buf, -1, self._send_down)
-                eng.pack_two_step(buf, +1, self._send_up)
-            self._cw.send(self._send_down, self._send_up)
+    # ``_exchange`` fills the four ghost planes of ``buf`` (post-collision populations).  My message for the
+    # lower neighbour comes from my two lowest interior planes and lands in its upper ghost planes, and vice versa.
+    def _pack_messages(self, buf, down, up):
+        self.engine.pack_two_step(buf, -1, down)
+        self.engine.pack_two_step(buf, +1, up)
 
-            def finish_copy():
-                from_above, from_below = self._cw.wait()
-                eng.unpack_two_step(buf, +1, from_above)
-                eng.unpack_two_step(buf, -1, from_below)
-            return finish_copy
-        if self._window is not None:
-            if not packed:
-                to_prev, to_next = self._window.targets()
-                eng.pack_two_step(buf, -1, to_prev)
-                eng.pack_two_step(buf, +1, to_next)
-            self._window.signal()
-
-            def finish_window():
-                from_above, from_below = self._window.wait()
-                eng.unpack_two_step(buf, +1, from_above)
-                eng.unpack_two_step(buf, -1, from_below)
-            return finish_window
-        if not packed:
-            eng.pack_two_step(buf, -1, self._send_down)
-            eng.pack_two_step(buf, +1, self._send_up)
-        if s.world_size == 1 and not self._force_p2p:
-            from_above, from_below, reqs = self._send_down, self._send_up, []
-        else:
-            from_above, from_below = self._recv_down, self._recv_up
-            if self._host_transport and buf.is_cuda:
-                torch.cuda.current_stream().synchronize()
-            ops = [dist.P2POp(dist.isend, self._send_down, s.prev, self.group, tag=1),
-                   dist.P2POp(dist.irecv, from_above, s.next, self.group, tag=1),
-                   dist.P2POp(dist.isend, self._send_up, s.next, self.group, tag=2),
-                   dist.P2POp(dist.irecv, from_below, s.prev, self.group, tag=2)]
-            reqs = dist.batch_isend_irecv(ops)
-
-        def finish():
-            for r in reqs:
-                r.wait()
-            if reqs and self._host_transport and buf.is_cuda:
-                torch.cuda.current_stream().synchronize()
-            eng.unpack_two_step(buf, +1, from_above)
-            eng.unpack_two_step(buf, -1, from_below)
-        return finish
+    def _unpack_messages(self, buf, from_below, from_above):
+        self._ghost_src = None                        # these messages end in the ghost planes of ``buf``
+        self.engine.unpack_two_step(buf, +1, from_above)
+        self.engine.unpack_two_step(buf, -1, from_below)
 
     # ---- stepping --------------------------------------------------------------------------------
     def _edges(self, cur, nxt, tau) -> bool:
@@ -1143,15 +1125,13 @@ class TwoStepSlabSimulation(SlabSimulation):
         if (hasattr(eng, "stream_collide_twice_edges") and os.environ.get("LT_SLAB_MERGED_EDGES") == "1"
                 and not self._masked):
             if fuse:
-                down, up = ((self._send_down, self._send_up) if self._window is None
-                            else self._window.targets())
+                down, up = self._halo.targets()
                 eng.stream_collide_twice_edges(cur, nxt, tau, edge, pack_lower=down, pack_upper=up)
             else:
                 eng.stream_collide_twice_edges(cur, nxt, tau, edge)
             return fuse
         if fuse and hasattr(eng, "stream_collide_twice_planes_packed"):
-            down, up = ((self._send_down, self._send_up) if self._window is None
-                        else self._window.targets())
+            down, up = self._halo.targets()
             eng.stream_collide_twice_planes_packed(cur, nxt, tau, lo, lo + edge, pack_lower=down)
             eng.stream_collide_twice_planes_packed(cur, nxt, tau, hi - edge, hi, pack_upper=up)
             return True
