@@ -174,6 +174,11 @@ class Flow(ABC):
             return None
         return desc.plan_args()
 
+    def _stepper_equilibrium(self):
+        """what the time-step drivers hand to their plans: ``_engine_equilibrium()``, None included, and the quadratic
+        equilibrium for a flow without an equilibrium object"""
+        return ("quadratic", 1.0) if self.equilibrium is None else self._engine_equilibrium()
+
     # ---- moments (lettuce/_flow.py:136-181) ---------------------------------------------------
     def rho(self, f: Optional[torch.Tensor] = None) -> torch.Tensor:
         """density, shape [1, *resolution]"""

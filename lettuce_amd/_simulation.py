@@ -98,7 +98,7 @@ class _NativeStepper:
             problems.append(f"stencil '{lattice}' (kernels exist for {sorted(STENCIL_IDS)})")
         if ctx.dtype not in (torch.float32, torch.float64):
             problems.append(f"dtype {ctx.dtype} (float32/float64 only)")
-        equilibrium = flow._engine_equilibrium() if flow.equilibrium is not None else ("quadratic", 1.0)
+        equilibrium = flow._stepper_equilibrium()
         if equilibrium is None:
             problems.append(f"equilibrium '{type(flow.equilibrium).__name__}'")
         if not sim.collision.native_available():
@@ -211,33 +211,17 @@ class _NativeStepper:
         self._sync_masks()
         self._sync_boundaries()
         tau = float(self.collision.tau(flow))
-        key = tau               # what a batch must share with the one before it to carry on from its state
-        if self.collision.constant is not None:
-            # Smagorinsky: the constant is re-read per batch like tau and handed to the plan (no new plan)
-            constant = float(self.collision.constant(flow))
-            self.plan.set_smagorinsky(constant)
-            key = (tau, constant)
-        if self.collision.tau_minus is not None:
-            # TRT: tau_minus is re-read per batch and handed to the plan in the same way
-            tau_minus = float(self.collision.tau_minus(flow))
-            self.plan.set_trt(tau_minus)
-            key = (tau, tau_minus)
-        if self.collision.rates is not None:
-            # MRT: the rates are re-read per batch (one copy from the device) and handed to the plan with the transform
-            rates = tuple(self.collision.rates(flow))
-            self.plan.set_mrt(self.collision.transform, rates)
-            key = (tau, self.collision.transform, rates)
-        if self.collision.force is not None:
-            # a body force: acceleration and scales are re-read per batch too; a changed force starts from flow.f
-            force = self.collision.force.plan_args()
-            self.plan.set_force(*force)
-            key = (key, force)
-        # the flow's equilibrium: kind and rho0 are re-read per batch too; a change starts from flow.f
-        equilibrium = flow._engine_equilibrium() if flow.equilibrium is not None else ("quadratic", 1.0)
+        # the collision's settings (Smagorinsky's constant, tau_minus, MRT's rates, a body force) are re-read per batch
+        # like tau and handed to the plan (no new plan)
+        settings = self.collision.settings(flow)
+        settings.apply(self.plan)
+        # the flow's equilibrium: kind and rho0 are re-read per batch too
+        equilibrium = flow._stepper_equilibrium()
         if equilibrium is None:
             raise NativeEngineError(f"the HIP engine has no kernel for equilibrium '{type(flow.equilibrium).__name__}'")
         self.plan.set_equilibrium(*equilibrium)
-        key = (key, equilibrium)
+        # what a batch must share with the one before it to carry on from its state: a change starts from flow.f
+        key = (tau, settings, equilibrium)
         if self.plan.resident_enabled()[0]:
             try:
                 return self._batch_resident(k, tau, key)

@@ -486,7 +486,7 @@ class SlabSimulation:
                  overlap: bool = True, comm_priority: int = -1, transport: str = "rccl",
                  copy_streams: Optional[int] = None):
         # the slab kernels evaluate the quadratic equilibrium (lt_plan_set_equilibrium: reference layout only)
-        equilibrium = flow._engine_equilibrium() if flow.equilibrium is not None else ("quadratic", 1.0)
+        equilibrium = flow._stepper_equilibrium()
         if equilibrium is None or equilibrium[0] != "quadratic":
             raise LettuceException(f"equilibrium '{type(flow.equilibrium).__name__}' has no slab kernel: the slab "
                                    f"simulations run the quadratic equilibrium only")
@@ -518,12 +518,7 @@ class SlabSimulation:
         self.up, self.down = _crossing_sets(flow.stencil)
         if not collision.native_available() and getattr(collision, "force", None) is not None:
             raise LettuceException(f"collision '{type(collision).__name__}' with this force has no engine kernel")
-        desc = collision.native_generator()
-        self._tau = desc.tau
-        self._constant = desc.constant      # Smagorinsky: re-read per batch like tau (else None)
-        self._tau_minus = desc.tau_minus    # TRT: re-read per batch like tau (else None)
-        self._force = desc.force            # body force: re-read per batch as well (else None)
-        self._mrt = (desc.transform, desc.rates) if desc.rates is not None else None   # MRT: the rates likewise
+        self._collision = desc = collision.native_generator()    # tau and the settings are re-read per batch
         # boundaries: same ordering and masks as Simulation (built on the extended slab, then cut
         # to this rank's planes + one ghost plane per side and laid out z-slowest)
         from ._simulation import build_masks
@@ -560,18 +555,12 @@ class SlabSimulation:
                 engine.ghosts = g
             engine.set_boundaries(entries, ncm, nsm, flow.units)      # test stand-ins
         self.engine = engine
-        if self._constant is not None and not hasattr(engine, "set_smagorinsky"):
-            raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
-        if self._tau_minus is not None and not hasattr(engine, "set_trt"):
-            raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
-        if self._mrt is not None:
-            if not hasattr(engine, "set_mrt"):
-                raise LettuceException(f"engine {type(engine).__name__} has no {desc.kind} collision")
-            engine.set_mrt(self._mrt[0], self._mrt[1](self.flow))     # now: the two-step driver asks the engine below
-        if self._force is not None:
-            if not hasattr(engine, "set_force"):
-                raise LettuceException(f"engine {type(engine).__name__} has no body force")
-            engine.set_force(*self._force.plan_args())     # now: the two-step driver asks the engine below
+        settings = desc.settings(flow)
+        for setter in settings.setters:
+            if not hasattr(engine, setter):
+                lacks = "body force" if setter == "set_force" else f"{desc.kind} collision"
+                raise LettuceException(f"engine {type(engine).__name__} has no {lacks}")
+        settings.apply(engine)                      # now: the two-step driver asks the engine below
         # [q, nx, ny, nzl + 2g] incl. the ghost planes -> [q, nzl + 2g, ny, nx]
         core = flow.f[..., h - g:h + nzl + g]
         # The slab tensors are this driver's own (the reference never sees them), so the populations need not be
@@ -674,6 +663,9 @@ class SlabSimulation:
     def _start_batch(self, tau):
         """(f*, scratch, fused steps already owed): the post-collision populations to carry on from -- kept from
         the batch before, or one collide pass + exchange away from ``f``"""
+        # Unlike the single-GPU stepper, whose carry key holds tau and the collision's settings, the slab drivers carry
+        # on from the kept post-collision populations even when tau or a setting changed between two batches: the last
+        # collide of the batch before then ran with the earlier values.
         from ._simulation import _version
         if self._pending is not None:
             (cur, nxt), self._pending = self._pending, None
@@ -784,18 +776,16 @@ class SlabSimulation:
                 eng.stream_collide_planes(cur, nxt, tau, 2, nzl)
             finish()
 
+    def _read_collision(self) -> float:
+        """once per batch: the collision's settings, re-read and handed to the engine, and its tau"""
+        tau = float(self._collision.tau(self.flow))
+        self._collision.settings(self.flow).apply(self.engine)
+        return tau
+
     def _advance(self, n: int):
         """n whole steps: (collide, exchange,) n - 1 or -- carrying on from the batch before -- n fused steps; the
         streaming pass that completes the last one runs when ``f`` is read (as Flow.f does on one GPU)."""
-        tau = float(self._tau(self.flow))
-        if self._constant is not None:
-            self.engine.set_smagorinsky(float(self._constant(self.flow)))
-        if self._tau_minus is not None:
-            self.engine.set_trt(float(self._tau_minus(self.flow)))
-        if self._mrt is not None:
-            self.engine.set_mrt(self._mrt[0], self._mrt[1](self.flow))
-        if self._force is not None:
-            self.engine.set_force(*self._force.plan_args())
+        tau = self._read_collision()
         cur, nxt, carried = self._start_batch(tau)
         for _ in range(n if carried else n - 1):
             self._fused_step(cur, nxt, tau)
@@ -1177,7 +1167,7 @@ class TwoStepSlabSimulation(SlabSimulation):
         """n whole steps: (collide, exchange,) the n - 1 or -- carrying on from the batch before -- n fused steps
         as double steps (+ one single fused step when their number is odd); the streaming pass that completes
         the last one runs when ``f`` is read."""
-        tau = float(self._tau(self.flow))
+        tau = self._read_collision()
         eng, lo, hi = self.engine, self.lo, self.hi
         cur, nxt, carried = self._start_batch(tau)
         fused = n if carried else n - 1

@@ -31,11 +31,11 @@ FEQ_COLLISIONS = ("bgk", "kbc", "smagorinsky", "trt", "regularized")
 INCOMPRESSIBLE_COLLISIONS = ("none", "bgk", "trt", "regularized")
 
 
-def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None, mrt=None):
-    """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``constant``: the
-    Smagorinsky constant, ``tau_minus``: TRT's second relaxation time, ``force``: the collision's body force (a Force
-    or None), ``mrt``: (transform name, rates) of MRT -- per-launch settings of the kind's one plan, handed over before
-    every collide."""
+def _engine_collide(flow, desc: NativeCollision):
+    """C(flow.f) through the HIP engine, or None when flow.f is not engine-shaped.  ``desc``: the collision's own
+    ``native_generator()``; its settings and its tau are read here and handed to the kind's one plan before every
+    collide."""
+    kind = desc.kind
     if flow._engine_plan(flow.f) is None:
         return None
     # the flow's equilibrium is a property of the plan, handed over like the other settings.  An equilibrium the engine
@@ -48,20 +48,15 @@ def _engine_collide(flow, kind, tau, constant=None, force=None, tau_minus=None, 
         from .._native import Plan
         plans[kind] = Plan(type(flow.stencil).__name__, flow.context.dtype, kind, flow.resolution,
                            device=flow.f.device)
+    plan = plans[kind]
     if kind in FEQ_COLLISIONS:
-        plans[kind].set_equilibrium(*equilibrium)
-    if constant is not None:
-        plans[kind].set_smagorinsky(constant)
-    if tau_minus is not None:
-        plans[kind].set_trt(tau_minus)
-    if mrt is not None:
-        plans[kind].set_mrt(*mrt)
-    if kind in ("bgk", "smagorinsky"):
-        if force is None:
-            plans[kind].set_force(None)
-        else:
-            plans[kind].set_force(*force.native_generator().plan_args())
-    return plans[kind].collide(flow.f, torch.empty_like(flow.f), tau)
+        plan.set_equilibrium(*equilibrium)
+    settings = desc.settings(flow)
+    settings.apply(plan)
+    if kind in ("bgk", "smagorinsky") and settings.force is None:
+        # the plan is shared by every collision object of this kind on the flow: one with a force may have used it last
+        plan.set_force(None)
+    return plan.collide(flow.f, torch.empty_like(flow.f), desc.tau(flow))
 
 
 class BGKCollision(Collision):
@@ -78,7 +73,7 @@ class BGKCollision(Collision):
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
         if self.native_available():
-            out = _engine_collide(flow, "bgk", self.tau, force=self.force)
+            out = _engine_collide(flow, self.native_generator())
             if out is not None:
                 return out
         if self.force is None:
@@ -171,7 +166,7 @@ class KBCCollision(Collision):
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
         self._prepare(flow)
-        out = _engine_collide(flow, "kbc", self.tau)
+        out = _engine_collide(flow, self.native_generator())
         if out is not None:
             return out
         feq = flow.equilibrium(flow)
@@ -224,7 +219,7 @@ class SmagorinskyCollision(Collision):
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
         if self.native_available():
-            out = _engine_collide(flow, "smagorinsky", self.tau, self.constant, force=self.force)
+            out = _engine_collide(flow, self.native_generator())
             if out is not None:
                 return out
         rho = flow.rho()
@@ -270,7 +265,7 @@ class TRTCollision(Collision):
         self.tau_minus = tau_minus
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
-        out = _engine_collide(flow, "trt", self.tau_plus, tau_minus=self.tau_minus)
+        out = _engine_collide(flow, self.native_generator())
         if out is not None:
             return out
         opposite = flow.stencil.opposite
@@ -309,7 +304,7 @@ class RegularizedCollision(Collision):
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
         self._prepare(flow)
-        out = _engine_collide(flow, "regularized", self.tau)
+        out = _engine_collide(flow, self.native_generator())
         if out is not None:
             return out
         feq = flow.equilibrium(flow)
@@ -368,9 +363,8 @@ class MRTCollision(Collision):
         return tuple(float(s) for s in self.relaxation_parameters.tolist())
 
     def __call__(self, flow: "Flow") -> torch.Tensor:
-        name = self._native_transform()
-        if name is not None:
-            out = _engine_collide(flow, "mrt", 1.0, mrt=(name, self._rates()))
+        if self._native_transform() is not None:
+            out = _engine_collide(flow, self.native_generator())
             if out is not None:
                 return out
         m = self.transform.transform(flow.f)

@@ -5,11 +5,17 @@ The reference's components return *code emitters* from ``native_generator()``
 generated and JIT-compiled per configuration.  The engine here is prebuilt, so the same
 protocol returns plain descriptors: an enum-like ``kind`` plus the scalar parameters the
 kernels take.
+
+What a collision hands to a plan before a launch, apart from ``tau``, is one value record: ``CollisionSettings``.
+``NativeCollision.settings(flow)`` reads it and ``CollisionSettings.apply(engine)`` calls the plan's setters; the
+steppers (``Simulation``, the slab drivers) and ``collision(flow)`` do nothing else with these values.  A new per-batch
+setting is therefore added in three places of this file: its late-bound field in ``NativeCollision``, its line in
+``settings()``, and its field and line in ``CollisionSettings`` (``calls()``).
 """
 from dataclasses import dataclass, field
 from typing import Callable, Optional, Tuple
 
-__all__ = ["NativeEquilibrium", "NativeCollision", "NativeBoundary", "NativeForce"]
+__all__ = ["NativeEquilibrium", "NativeCollision", "CollisionSettings", "NativeBoundary", "NativeForce"]
 
 
 @dataclass
@@ -40,6 +46,43 @@ class NativeForce:
         return (tuple(float(a) for a in self.acceleration()), float(self.ueq_scale()), float(self.source_scale()))
 
 
+@dataclass(frozen=True)
+class CollisionSettings:
+    """The values a collision hands to a plan before a launch, read now: what ``Plan.set_*`` take, nothing late-bound.
+    Hashable and compared by value: part of the steppers' carry key.  ``tau`` is not among them: it is a launch argument
+    of the engine, and KBC and the regularised collision fix theirs at the first read."""
+    smagorinsky: Optional[float] = None        # the constant
+    tau_minus: Optional[float] = None          # TRT
+    mrt: Optional[Tuple[str, Tuple[float, ...]]] = None                    # the transform's name and its q rates
+    force: Optional[Tuple[Tuple[float, ...], float, float]] = None         # NativeForce.plan_args()
+
+    def calls(self):
+        """(setter, its arguments) for every value that is not None, in the one order every site calls them"""
+        calls = []
+        if self.smagorinsky is not None:
+            calls.append(("set_smagorinsky", (self.smagorinsky,)))
+        if self.tau_minus is not None:
+            calls.append(("set_trt", (self.tau_minus,)))
+        if self.mrt is not None:
+            calls.append(("set_mrt", self.mrt))
+        if self.force is not None:
+            calls.append(("set_force", self.force))
+        return calls
+
+    @property
+    def setters(self) -> Tuple[str, ...]:
+        """the methods ``apply`` will call: a driver asks its engine for them before the first launch"""
+        return tuple(name for name, _ in self.calls())
+
+    def apply(self, engine):
+        """hand the values to ``engine``: a ``lettuce_amd._native.Plan`` or anything else with these methods"""
+        for name, args in self.calls():
+            getattr(engine, name)(*args)
+
+
+# ``kind``, ``tau`` and ``arithmetic`` say which kernels run and with which launch argument.  The fields after them are
+# the per-batch settings, late-bound; they reach a plan only through settings() and CollisionSettings.apply().  A new one
+# needs its field here, its line in settings(), and its field and line in CollisionSettings -- nothing in the steppers.
 @dataclass
 class NativeCollision:
     kind: str                                  # 'none' | 'bgk' | 'kbc' | 'smagorinsky' | 'trt' | 'regularized' | 'mrt'
@@ -64,6 +107,15 @@ class NativeCollision:
     # `tau` is not read); None for the other kinds
     transform: Optional[str] = None
     rates: Optional[Callable[["Flow"], Tuple[float, ...]]] = None
+
+    def settings(self, flow) -> CollisionSettings:
+        """the per-batch settings now: every callable is read once, in this order (the rates of MRT are one copy from
+        the device)"""
+        return CollisionSettings(
+            smagorinsky=None if self.constant is None else float(self.constant(flow)),
+            tau_minus=None if self.tau_minus is None else float(self.tau_minus(flow)),
+            mrt=None if self.rates is None else (self.transform, tuple(self.rates(flow))),
+            force=None if self.force is None else self.force.plan_args())
 
 
 @dataclass
