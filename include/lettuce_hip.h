@@ -587,6 +587,26 @@ int lt_plan_set_mrt(lt_plan *plan, int transform, const double *relaxation, int 
  * lt_plan_two_step_admitted return LT_ERR_UNSUPPORTED with a reason that names the force. */
 int lt_plan_set_force(lt_plan *plan, const double *acceleration /* dims values, or NULL */, double ueq_scale,
                       double source_scale);
+/* The same body force with an acceleration that varies in space: `acceleration` is a DEVICE pointer to dense
+ * [dims][nodes] values in the plan's dtype, lattice units, logical axis order x, y, z, the nodes in the reference's
+ * order (the order of a population).  The formulas are those of lt_plan_set_force with a = a(x), the node's own value;
+ * the shift ueq_scale * a(x) is formed in the plan's dtype, as the uniform call forms it on the host, so a field that
+ * is constant in space gives the uniform force's populations bit for bit.  The kernels read the memory at EVERY launch:
+ * it must stay allocated while the plan may launch, the caller may rewrite it between launches (ordered on the launch
+ * stream), and its VALUES ARE NOT VALIDATED -- the function checks what the host can check: a non-null plan, finite
+ * scales (LT_ERR_INVALID), the plan's collision (BGK and Smagorinsky; else LT_ERR_UNSUPPORTED).  acceleration == NULL
+ * removes the field.  lt_plan_set_force and lt_plan_set_force_field exclude each other: the later call wins.  A changed
+ * pointer is a changed setting (a captured graph is dropped).
+ * The field has the one-step kernels of the reference layout (kernels' COLL 37 and 39): every lattice and dtype, fused
+ * and collide-only (lt_collide takes the latter), with or without masks -- bounce-back, equilibrium boundaries (table
+ * and per-node) and link bounce-back are supported; a boundary node does not read the field.  LT_ERR_UNSUPPORTED, with
+ * a message that names the pair and the plan unchanged, at the call that first knows both: a slab-layout plan or ghost
+ * planes; an anti-bounce-back or constant-pressure outlet in the plan; the incompressible equilibrium
+ * (lt_plan_set_equilibrium refuses in turn on a plan with a field); lt_plan_set_two_step(plan, 1, ...) and
+ * lt_plan_set_many_step(plan, 1) before or after it.  lt_run, lt_continue and lt_resident_advance keep one update per
+ * launch; the explicit multi-step entry points and lt_plan_two_step_admitted return LT_ERR_UNSUPPORTED. */
+int lt_plan_set_force_field(lt_plan *plan, const void *acceleration /* device, [dims][nodes], or NULL */,
+                            double ueq_scale, double source_scale);
 /* The equilibrium of the plan, lt_equilibrium_kind: LT_EQUILIBRIUM_QUADRATIC (what every plan has until this is called;
  * rho0 is not read) or LT_EQUILIBRIUM_INCOMPRESSIBLE,
  *   feq_q = w_q (rho + rho0 ((2 e_q.u - u.u) / (2 cs^2) + (e_q.u / cs^2)^2 / 2)),   u = j / rho

@@ -124,6 +124,7 @@ SYMBOLS = {
     "lt_plan_set_trt": (ctypes.c_int, [_vp, _dbl]),
     "lt_plan_set_mrt": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(ctypes.c_double), _i32]),
     "lt_plan_set_force": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _dbl, _dbl]),
+    "lt_plan_set_force_field": (ctypes.c_int, [_vp, _vp, _dbl, _dbl]),
     "lt_plan_set_equilibrium": (ctypes.c_int, [_vp, ctypes.c_int, _dbl]),
     "lt_stream_collide_twice_planes": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp]),
     "lt_stream_collide_twice_planes_packed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _i64, _i64, _vp, _vp, _vp]),
@@ -893,12 +894,40 @@ class Plan:
         1 - 1 / (2 tau); Shan-Chen: ``ueq_scale`` tau, ``source_scale`` 0 (include/lettuce_hip.h)."""
         if acceleration is None:
             self._check(self.lib.lt_plan_set_force(self._handle, None, float(ueq_scale), float(source_scale)))
+            self._release_force_field()                      # the call removes a field as well
             return
         values = [float(a) for a in acceleration]
         if len(values) != len(self.resolution):
             raise NativeEngineError(f"acceleration has {len(values)} components, the lattice {len(self.resolution)}")
         array = (ctypes.c_double * len(values))(*values)
         self._check(self.lib.lt_plan_set_force(self._handle, array, float(ueq_scale), float(source_scale)))
+        self._release_force_field()                          # the later call wins (lt_plan_set_force cleared the field)
+
+    def set_force_field(self, field=None, ueq_scale: float = 0.5, source_scale: float = 0.0):
+        """A body force on a BGK / Smagorinsky plan whose acceleration varies in space (lt_plan_set_force_field):
+        ``field`` is a dense device tensor ``[d, *resolution]`` of the plan's dtype, lattice units; None removes it.  The
+        kernels read its memory at every launch: values edited in place are seen, and the plan keeps a reference to the
+        tensor so that it outlives the launches.  ``set_force`` and ``set_force_field`` exclude each other, the later
+        call wins.  The scales as for ``set_force``."""
+        if field is None:
+            self._check(self.lib.lt_plan_set_force_field(self._handle, None, float(ueq_scale), float(source_scale)))
+            self._release_force_field()
+            return
+        if self.layout != LAYOUT_REFERENCE or self.ghost_planes:
+            raise NativeEngineError("a force field on a slab plan: its kernels exist for the reference layout without "
+                                    "ghost planes only")
+        self._tensor_ok(field, [self.d] + self.resolution)     # per-node fields stay dense
+        if field.device != self.device:
+            raise NativeEngineError(f"force field on {field.device}, the plan's device is {self.device}")
+        self._check(self.lib.lt_plan_set_force_field(self._handle, _ptr(field), float(ueq_scale), float(source_scale)))
+        if self._keepalive.get("force_field") is not field:
+            self._release_force_field()
+            self._keepalive["force_field"] = field
+
+    def _release_force_field(self):
+        old = self._keepalive.pop("force_field", None)
+        if old is not None and old.is_cuda:
+            old.record_stream(torch.cuda.current_stream(old.device))   # launches in flight may still read it
 
     def set_equilibrium(self, kind: str = "quadratic", rho0: float = 1.0):
         """The plan's equilibrium (lt_plan_set_equilibrium), read at every launch like tau: "quadratic" or

@@ -111,6 +111,16 @@ class _NativeStepper:
         for b in sim.boundaries[1:]:
             if not b.native_available():
                 problems.append(f"boundary '{type(b).__name__}'")
+        # a force field has the one-step kernels of plans without outlets and with the quadratic equilibrium only
+        # (lt_plan_set_force_field): said here, by name, before anything touches a device
+        force = sim.collision.native_generator().force if sim.collision.native_available() else None
+        if force is not None and force.field is not None:
+            field_name = type(sim.collision.force).__name__
+            for i, b in enumerate(sim.boundaries[1:], start=1):
+                if b.native_available() and b.native_generator(i).kind in ("abb_outlet", "pressure_outlet"):
+                    problems.append(f"force field '{field_name}' with the outlet '{type(b).__name__}'")
+            if equilibrium is not None and equilibrium[0] != "quadratic":
+                problems.append(f"force field '{field_name}' with equilibrium '{type(flow.equilibrium).__name__}'")
         if problems:
             raise NativeEngineError(
                 "the HIP engine was requested (Context.use_native) but has no kernel for: "

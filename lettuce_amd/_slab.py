@@ -519,6 +519,11 @@ class SlabSimulation:
         if not collision.native_available() and getattr(collision, "force", None) is not None:
             raise LettuceException(f"collision '{type(collision).__name__}' with this force has no engine kernel")
         self._collision = desc = collision.native_generator()    # tau and the settings are re-read per batch
+        if desc.force is not None and desc.force.field is not None:
+            # a force field is given on the whole grid and has one-step kernels of the reference layout only
+            raise LettuceException(f"collision '{type(collision).__name__}' with the force field "
+                                   f"'{type(collision.force).__name__}' has no slab kernel: the slab simulations take a "
+                                   f"uniform body force (Guo, ShanChen) only")
         # boundaries: same ordering and masks as Simulation (built on the extended slab, then cut
         # to this rank's planes + one ghost plane per side and laid out z-slowest)
         from ._simulation import build_masks

@@ -160,6 +160,10 @@ struct lt_plan {
     struct Mrt { int transform = 0; double rates[27] = {}; } mrt;
     // uniform body force (lt_plan_set_force).  on: the kernels with COLL = 4 + collision
     struct Force { bool on = false; double a[3] = {0.0, 0.0, 0.0}, ueq_scale = 0.0, source_scale = 0.0; } force;
+    // ... or one whose acceleration is a per-node field (lt_plan_set_force_field; the two exclude each other).  a: the
+    // caller's device memory, [dims][N] in the plan's dtype; non-null: the kernels with COLL = 36 + collision.  A changed
+    // pointer is a changed setting
+    struct ForceField { const void *a = nullptr; double ueq_scale = 0.0, source_scale = 0.0; } field;
     // the equilibrium (lt_plan_set_equilibrium): lt_equilibrium_kind and, for the incompressible one, its rho0
     int equilibrium = LT_EQUILIBRIUM_QUADRATIC;
     double rho0 = 1.0;
@@ -171,7 +175,8 @@ struct lt_plan {
       return smagorinsky == o.smagorinsky && tau_minus == o.tau_minus && mrt.transform == o.mrt.transform &&
              std::equal(mrt.rates, mrt.rates + 27, o.mrt.rates) && force.on == o.force.on &&
              std::equal(force.a, force.a + 3, o.force.a) && force.ueq_scale == o.force.ueq_scale &&
-             force.source_scale == o.force.source_scale && equilibrium == o.equilibrium && rho0 == o.rho0 &&
+             force.source_scale == o.force.source_scale && field.a == o.field.a &&
+             field.ueq_scale == o.field.ueq_scale && field.source_scale == o.field.source_scale && equilibrium == o.equilibrium && rho0 == o.rho0 &&
              masked == o.masked && tune == o.tune && shift == o.shift && residency == o.residency;
     }
     void fill(lt::StepArgs &a) const {
@@ -181,6 +186,8 @@ struct lt_plan {
       std::copy(mrt.rates, mrt.rates + 27, a.mrt_rates);
       std::copy(force.a, force.a + 3, a.accel);
       a.ueq_scale = force.ueq_scale; a.source_scale = force.source_scale;
+      a.accel_field = field.a;
+      if (field.a) { a.ueq_scale = field.ueq_scale; a.source_scale = field.source_scale; }
       a.rho0 = rho0;
     }
   } set;
@@ -550,6 +557,8 @@ int kernel_coll(const lt_plan *p) {
     return p->set.mrt.transform == LT_MRT_D2Q9_LALLEMAND ? lt::kCollMrtLallemand : lt::kCollMrt;
   // the incompressible equilibrium: the collisions that evaluate feq get kernels of their own (no collision does not)
   const bool incompressible = p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE && p->desc.collision != LT_COLLISION_NONE;
+  // a force field: numbers of its own (it excludes the uniform force and the incompressible equilibrium)
+  if (p->set.field.a) return p->desc.collision | lt::kCollForce | lt::kCollField;
   return p->desc.collision | (p->set.force.on ? lt::kCollForce : 0) | (incompressible ? lt::kCollIncompressible : 0);
 }
 static_assert(lt::kCollNone == LT_COLLISION_NONE && lt::kCollBgk == LT_COLLISION_BGK && lt::kCollKbc == LT_COLLISION_KBC &&
@@ -588,6 +597,8 @@ const char *const kForceMultiStep = "a body force (lt_plan_set_force) has the on
                                     "or slab two-step kernel takes it";
 const char *const kForceSmagorinskyTwice = "Smagorinsky with a body force (lt_plan_set_force) does not fit the two-step "
                                            "sweep's occupancy step without scratch: it keeps the one-step kernel";
+const char *const kForceFieldMultiStep = "a per-node force field (lt_plan_set_force_field) has the one-step kernels only: no "
+                                         "two-step or many-step kernel takes it";
 const char *const kTrtMultiStep = "the TRT collision has the one-step kernels and the plain two-step sweep of periodic D3Q19 "
                                   "fp32 plans without masks only: no many-step, 2-D, masked, role-wave, edge, packed or "
                                   "signalling two-step kernel takes it";
@@ -626,6 +637,7 @@ const char *multi_step_refusal(const lt_plan *p, int mode) {
   const bool plain_sweep = twice && p->unit.d == 3 && !p->set.masked && !p->desc.ghost_planes && p->desc.stencil == LT_D3Q19 &&
                            p->desc.dtype == LT_F32;
   if (p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE) return kIncompressibleMultiStep;   // (unit.inc, part incompressible)
+  if (p->set.field.a) return kForceFieldMultiStep;                     // (unit.inc, part force_field)
   if (p->set.force.on) {
     if (!plain_sweep) return kForceMultiStep;
     if (!has_kernel(p->unit, kernel_selector(p, lt::kFusedTwice))) return p->desc.collision == LT_COLLISION_SMAGORINSKY ? kForceSmagorinskyTwice : kForceMultiStep;
@@ -2064,6 +2076,7 @@ int lt_plan_set_many_step(lt_plan *p, int32_t mode) {
   if (mode == 1 && p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
     return fail(LT_ERR_UNSUPPORTED, "several steps per launch: %s", kIncompressibleMultiStep);
   if (mode == 1 && p->n_link_kind > 0) return fail(LT_ERR_UNSUPPORTED, "several steps per launch with %s", kLinkMultiStep);
+  if (mode == 1 && p->set.field.a) return fail(LT_ERR_UNSUPPORTED, "several steps per launch: %s", kForceFieldMultiStep);
   p->many = mode;
   return LT_OK;
 }
@@ -2125,6 +2138,41 @@ int lt_plan_set_force(lt_plan *p, const double *acceleration, double ueq_scale, 
                   f.a[1], f.a[2], ueq_scale, source_scale);
   }
   p->set.force = f;
+  p->set.field = lt_plan::Settings::ForceField();      // the later call wins
+  return LT_OK;
+}
+
+int lt_plan_set_force_field(lt_plan *p, const void *acceleration, double ueq_scale, double source_scale) {
+  if (!p) return fail(LT_ERR_INVALID, "null plan");
+  if (p->desc.collision != LT_COLLISION_BGK && p->desc.collision != LT_COLLISION_SMAGORINSKY)
+    return fail(LT_ERR_UNSUPPORTED, "a body force exists for the BGK and Smagorinsky collisions; the plan's collision "
+                                    "is %d", p->desc.collision);
+  if (!acceleration) {
+    p->set.field = lt_plan::Settings::ForceField();
+    return LT_OK;
+  }
+  if (!std::isfinite(ueq_scale) || !std::isfinite(source_scale))
+    return fail(LT_ERR_INVALID, "force field: scales %g and %g must be finite", ueq_scale, source_scale);
+  // what has no kernel with a field (unit.inc, part force_field: one-step kernels of the reference layout, no outlet)
+  if (p->desc.layout != LT_LAYOUT_REFERENCE || p->desc.ghost_planes)
+    return fail(LT_ERR_UNSUPPORTED, "a force field (lt_plan_set_force_field) on a slab plan: its kernels exist for the "
+                                    "reference layout without ghost planes only");
+  for (int i = 0; i < p->desc.n_boundaries; ++i) {
+    const int kind = p->desc.boundaries[i].kind;
+    if (kind == LT_BOUNDARY_ABB_OUTLET || kind == LT_BOUNDARY_PRESSURE_OUTLET)
+      return fail(LT_ERR_UNSUPPORTED, "a force field (lt_plan_set_force_field) on a plan with %s (boundary %d): an outlet "
+                                      "collides its neighbour node again, and no kernel does that with a field",
+                  kind == LT_BOUNDARY_ABB_OUTLET ? "an anti-bounce-back outlet" : "a constant-pressure outlet", i);
+  }
+  if (p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
+    return fail(LT_ERR_UNSUPPORTED, "a force field (lt_plan_set_force_field) and the incompressible equilibrium "
+                                    "(lt_plan_set_equilibrium): no kernel has the pair");
+  if (p->two_step == 1) return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kForceFieldMultiStep);
+  if (p->many == 1) return fail(LT_ERR_UNSUPPORTED, "several steps per launch: %s", kForceFieldMultiStep);
+  p->set.field.a = acceleration;
+  p->set.field.ueq_scale = ueq_scale;
+  p->set.field.source_scale = source_scale;
+  p->set.force = lt_plan::Settings::Force();           // the later call wins
   return LT_OK;
 }
 
@@ -2135,6 +2183,9 @@ int lt_plan_set_equilibrium(lt_plan *p, int kind, double rho0) {
   if (!std::isfinite(rho0)) return fail(LT_ERR_INVALID, "equilibrium: rho0 = %g must be finite", rho0);
   if (kind == LT_EQUILIBRIUM_INCOMPRESSIBLE) {
     const int c = p->desc.collision;
+    if (p->set.field.a)
+      return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium on a plan with a force field "
+                                      "(lt_plan_set_force_field): no kernel has the pair");
     if (c == LT_COLLISION_KBC || c == LT_COLLISION_SMAGORINSKY)
       return fail(LT_ERR_UNSUPPORTED, "the incompressible equilibrium has kernels for no collision, BGK (with or without a "
                                       "body force), TRT and the regularised collision; the plan's collision is %d (%s)", c,
@@ -2162,6 +2213,7 @@ int lt_plan_set_two_step(lt_plan *p, int32_t mode, int32_t planes_per_workgroup)
   if (mode == 1 && p->set.equilibrium == LT_EQUILIBRIUM_INCOMPRESSIBLE)
     return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kIncompressibleMultiStep);
   if (mode == 1 && p->n_link_kind > 0) return fail(LT_ERR_UNSUPPORTED, "two steps per launch with %s", kLinkMultiStep);
+  if (mode == 1 && p->set.field.a) return fail(LT_ERR_UNSUPPORTED, "two steps per launch: %s", kForceFieldMultiStep);
   const int sweep = p->unit.d == 2 ? p->n1 : p->n2;          // extent of the sweep axis
   if (planes_per_workgroup < 0 ||
       (planes_per_workgroup > 0 && !p->desc.ghost_planes && sweep % planes_per_workgroup != 0))

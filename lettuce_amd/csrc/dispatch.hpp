@@ -24,6 +24,14 @@ constexpr bool coll_forced(int coll) {
   return (coll & ~kCollIncompressible) == (kCollBgk | kCollForce) || coll == (kCollSmagorinsky | kCollForce);
 }
 constexpr int coll_base(int coll) { return coll_forced(coll) ? coll & ~kCollForce : coll; }   // the collision under the force
+// ... and kCollField added to BGK and Smagorinsky with a body force whose acceleration is a per-node field
+// (lt_plan_set_force_field): 37 and 39.  A bit above every number so far (0-25), and numbers of their own rather than
+// forced ones: coll_forced says "takes KParamsF", these take KParamsFF.
+constexpr int kCollField = 32;
+constexpr bool coll_field(int coll) {
+  return coll == (kCollBgk | kCollForce | kCollField) || coll == (kCollSmagorinsky | kCollForce | kCollField);
+}
+constexpr int coll_field_base(int coll) { return coll & ~(kCollForce | kCollField); }   // the collision under the field
 
 struct StepArgs {
   const void *in;
@@ -67,6 +75,10 @@ struct StepArgs {
   // the incompressible equilibrium (coll & 16, lt_plan_set_equilibrium): its reference density; the units round it to
   // the plan's scalar type
   double rho0;
+  // per-node body force (coll & 32, lt_plan_set_force_field): the acceleration [dims][n0 * n1 * n2] in the plan's scalar
+  // type on the device, logical axis order, reference node order; null: no field.  Its two scales travel in ueq_scale
+  // and source_scale above
+  const void *accel_field;
 };
 
 // The auxiliary launches of a unit (aux_<tag>; AuxArgs::what).  Nothing outside csrc/ sees the numbers.
@@ -191,7 +203,7 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 // What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
 // on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
 // collision) and outlets (plans with a constant-pressure outlet) and incompressible (the kernels of the incompressible
-// equilibrium), every unit, sweeps and smagorinsky (3-D
+// equilibrium) and force_field (the kernels with a per-node body force), every unit, sweeps and smagorinsky (3-D
 // units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27), spectrum, boundary_force and links (2-D and 3-D units).  Declared for every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
@@ -209,6 +221,7 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
   int mrt_outlets_##tag(const StepArgs &, const NameBuf *);    \
   int incompressible_##tag(const StepArgs &, const NameBuf *); \
   int incompressible_aux_##tag(const AuxArgs &);               \
+  int force_field_##tag(const StepArgs &, const NameBuf *);    \
   int spectrum_##tag(const AuxArgs &);                         \
   int boundary_force_##tag(const AuxArgs &);                   \
   int links_##tag(const LinkArgs &);

@@ -113,6 +113,23 @@ struct KParamsF : KParams<T> {
   T source_scale;            // Guo: 1 - 1 / (2 force.tau), Shan-Chen: 0
 };
 
+// The parameters of a kernel with a body force whose acceleration is a per-node field (COLL & 32; dispatch.hpp,
+// kCollField): KParams and, behind it, the field and the two scales of the scheme.  A type of its own again: the
+// kernels of the uniform force keep their argument block.
+template <typename T>
+struct KParamsFF : KParams<T> {
+  const T *accel_field;      // [D][N]: component c (LOGICAL axis) of node `own` at c * N + own; dense, read-only
+  T ueq_scale;               // Guo 1/2, Shan-Chen force.tau: the node's shift is ueq_scale * a(x), formed in T
+  T source_scale;            // Guo: 1 - 1 / (2 force.tau), Shan-Chen: 0
+};
+
+// The acceleration of one node and its velocity shift, along the MEMORY axes: what collide_forced takes.  The kernels of
+// the uniform force hand over KParamsF's two arrays, those of a field load theirs (load_node_force).
+template <typename T>
+struct NodeForce {
+  T accel[3], shift[3];
+};
+
 // The parameters of a kernel with the multiple-relaxation-time collision (COLL 10, 11; mrt.hpp): KParams and, behind it,
 // the reciprocal relaxation rates of the q moments.  A type of its own for the same reason.
 template <typename T>
@@ -752,8 +769,12 @@ __device__ __forceinline__ void collide_regularized(T (&f)[S::Q][VEC], T c, T rh
 // one per population, and the sweep has none to spare.  Compared with the reference at rounding level.  No
 // contraction by the compiler (every kernel this is inlined into returns the same bits); the multiply-adds of the
 // source term are written as fma_t.
-template <typename T, class S, int LAYOUT, int VEC, int k, int BASE, int EQ = 0>
-__device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF<T> &p, T rho0 = T(0)) {
+// accel, shift: the node's acceleration and ueq_scale times it along the memory axes -- KParamsF's arrays (uniform
+// force), or the values a field kernel loaded for this node (NodeForce).  p: the block with tau_inv, tau, smag_c2 and
+// source_scale (KParamsF, KParamsFI, KParamsFF)
+template <typename T, class S, int LAYOUT, int VEC, int k, int BASE, int EQ = 0, class P>
+__device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const P &p, const T (&accel)[3], const T (&shift)[3],
+                                               T rho0 = T(0)) {
 #pragma clang fp contract(off)
   static_assert(BASE == 1 || BASE == 3, "a body force exists for BGK and Smagorinsky");
   static_assert(EQ == 0 || BASE == 1, "the incompressible equilibrium exists under BGK with a force, not Smagorinsky");
@@ -762,13 +783,13 @@ __device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF
   moments<T, S, LAYOUT, VEC, k>(f, rho, j);
   static_for<3>([&](auto mc) {
     constexpr int m = decltype(mc)::value;
-    u[m] = j[m] / rho + p.shift[m] / rho;
+    u[m] = j[m] / rho + shift[m] / rho;
   });
   const T uxu = square_norm<S, LAYOUT>(u);
   // u* . a over the logical axes
-  T ua = u[M::memory(0)] * p.accel[M::memory(0)];
-  if constexpr (S::D > 1) ua = ua + u[M::memory(1)] * p.accel[M::memory(1)];
-  if constexpr (S::D > 2) ua = ua + u[M::memory(2)] * p.accel[M::memory(2)];
+  T ua = u[M::memory(0)] * accel[M::memory(0)];
+  if constexpr (S::D > 1) ua = ua + u[M::memory(1)] * accel[M::memory(1)];
+  if constexpr (S::D > 2) ua = ua + u[M::memory(2)] * accel[M::memory(2)];
   constexpr T inv_cs2 = (T)(1.0 / kCs2), inv_cs4 = (T)(1.0 / kCs4);
   const T ua_cs2 = ua * inv_cs2;
   // relaxed = f_q - (1 / tau_eff) (f_q - feq_q)  ->  relaxed + source_q
@@ -779,8 +800,8 @@ __device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF
     static_for<S::D>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
       constexpr int e = S::E[q][c];
-      if constexpr (e > 0) t = fma_t(p.accel[M::memory(c)], h, t);
-      else if constexpr (e < 0) t = fma_t(-p.accel[M::memory(c)], h, t);
+      if constexpr (e > 0) t = fma_t(accel[M::memory(c)], h, t);
+      else if constexpr (e < 0) t = fma_t(-accel[M::memory(c)], h, t);
     });
     return fma_t(p.source_scale, T(S::W[q]) * t, relaxed);
   };
@@ -842,6 +863,11 @@ __device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF
       f[q][k] = with_source(qc, f[q][k] - r * x[q]);
     });
   }
+}
+// ... with the uniform acceleration of the block: what the kernels of lt_plan_set_force call
+template <typename T, class S, int LAYOUT, int VEC, int k, int BASE, int EQ = 0>
+__device__ __forceinline__ void collide_forced(T (&f)[S::Q][VEC], const KParamsF<T> &p, T rho0 = T(0)) {
+  collide_forced<T, S, LAYOUT, VEC, k, BASE, EQ>(f, p, p.accel, p.shift, rho0);
 }
 
 // ---- boundaries -------------------------------------------------------------------------
@@ -946,20 +972,41 @@ __device__ __forceinline__ void abb_apply(const KParams<T> &p, int slot, T rn, c
 // number means and which fields of the parameter block P it reads.  smag_c2 is the collision's own scalar (unit.inc,
 // params_of): Smagorinsky's squared constant, TRT's 1 / (2 tau_minus) beside beta = 1 / (2 tau_plus), the regularised
 // collision's 1 - 1 / tau.  A body force and MRT read their own blocks (KParamsF, KParamsM).  kCollNone: nothing.
+// nf: the node's acceleration and shift, for the two numbers with a force field only (load_node_force; KParamsFF).
 template <typename T, class S, int LAYOUT, int VEC, int k, int COLL, class P>
-__device__ __forceinline__ void collide_node(T (&f)[S::Q][VEC], const P &p) {
+__device__ __forceinline__ void collide_node(T (&f)[S::Q][VEC], const P &p, const NodeForce<T> *nf = nullptr) {
   if constexpr (COLL == kCollBgk) collide_bgk<T, S, LAYOUT, VEC, k>(f, p.tau_inv);
   if constexpr (COLL == kCollKbc) collide_kbc<T, S, LAYOUT, VEC, k>(f, p.beta, p.inv_beta);
   if constexpr (COLL == kCollSmagorinsky) collide_smagorinsky<T, S, LAYOUT, VEC, k>(f, p.tau, p.smag_c2);
   if constexpr (COLL == kCollTrt) collide_trt<T, S, LAYOUT, VEC, k>(f, p.beta, p.smag_c2);
   if constexpr (COLL == kCollRegularized) collide_regularized<T, S, LAYOUT, VEC, k>(f, p.smag_c2);
   if constexpr (coll_forced(COLL) && !coll_incompressible(COLL)) collide_forced<T, S, LAYOUT, VEC, k, coll_base(COLL)>(f, p);
+  if constexpr (coll_field(COLL)) collide_forced<T, S, LAYOUT, VEC, k, coll_field_base(COLL)>(f, p, nf->accel, nf->shift);
   // ... with the incompressible equilibrium (KParamsI / KParamsFI: rho0)
   if constexpr (COLL == (kCollBgk | kCollIncompressible)) collide_bgk<T, S, LAYOUT, VEC, k, 1>(f, p.tau_inv, p.rho0);
   if constexpr (COLL == (kCollTrt | kCollIncompressible)) collide_trt<T, S, LAYOUT, VEC, k, 1>(f, p.beta, p.smag_c2, p.rho0);
   if constexpr (COLL == (kCollRegularized | kCollIncompressible)) collide_regularized<T, S, LAYOUT, VEC, k, 1>(f, p.smag_c2, p.rho0);
   if constexpr (COLL == (kCollBgk | kCollForce | kCollIncompressible)) collide_forced<T, S, LAYOUT, VEC, k, kCollBgk, 1>(f, p, p.rho0);
   if constexpr (coll_mrt(COLL)) collide_mrt<T, S, mrt_transform_of<S, COLL>(), LAYOUT, VEC, k>(f, p.r);
+}
+
+// The acceleration of node `own` from a plan's force field (KParamsFF) and its velocity shift: component c of the
+// LOGICAL axes lies at c * N + own -- consecutive lanes, consecutive addresses -- and goes to the memory axis the layout
+// gives it, as set_force (unit.inc) permutes the uniform acceleration.  The shift is the product the host forms for the
+// uniform force, ueq_scale * a in T and not contracted into anything: a field that is constant in space gives the bits
+// of the uniform kernels.  own < N for every node of a launch (the field has no ghost planes: reference layout only).
+template <typename T, class S, int LAYOUT>
+__device__ __forceinline__ void load_node_force(const KParamsFF<T> &p, unsigned own, NodeForce<T> &nf) {
+#pragma clang fp contract(off)
+  using M = MemMap<S, LAYOUT>;
+  nf.accel[0] = nf.accel[1] = nf.accel[2] = T(0);
+  nf.shift[0] = nf.shift[1] = nf.shift[2] = T(0);
+  static_for<S::D>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    const T a = load<T>(p.accel_field + (long long)c * p.N + own);
+    nf.accel[M::memory(c)] = a;
+    nf.shift[M::memory(c)] = p.ueq_scale * a;
+  });
 }
 
 // (rho, j) of the node (c0, c1, c2), as Flow.rho()/Flow.u() would see it when the AntiBounceBackOutlet with
@@ -1063,6 +1110,9 @@ __device__ __forceinline__ void apply_boundaries(const P &p, int b, int c0k, int
       // (anti_bounce_back_outlet.py:81-91, _simulation.py:186-188).  The constant-pressure outlet as well, for the same
       // reason (equilibrium_outlet_p.py:70-73): a bounce-back or inlet node of its plane has had its own boundary
       // applied at its (lower) index and is overwritten here
+      // (no outlet on a plan with a force field: lt_plan_set_force_field refuses the pair, and its kernels hold no
+      // gather of the neighbour)
+      if constexpr (!coll_field(COLL)) {
       const int ax = p.bt->mem_axis[slot];
       const int coord = ax == 0 ? c0k : (ax == 1 ? c1 : c2);
       if (coord == p.bt->plane[slot]) {
@@ -1080,6 +1130,7 @@ __device__ __forceinline__ void apply_boundaries(const P &p, int b, int c0k, int
         } else {
           abb_outlet<T, S, LAYOUT, STREAM, true, VEC, k, COLL, ABBD>(p, slot, c0k, c1, c2, f);
         }
+      }
       }
     } else if (b == slot) {
       if (kind == kBounceBack) {
@@ -1126,6 +1177,10 @@ __device__ __forceinline__ void lbm_body(const P &p) {
 
   T f[S::Q][1];
   gather<T, S, LAYOUT, STREAM, (TUNE & 1) != 0>(p, c, f);
+  // a force field: the node's acceleration, D coalesced loads issued with the gather's (a boundary node loads its
+  // values too and does not use them: the field is dense, and the loads need not wait for the node's byte)
+  [[maybe_unused]] NodeForce<T> nf;
+  if constexpr (COLLIDE && coll_field(COLL)) load_node_force<T, S, LAYOUT>(p, own, nf);
 
   unsigned char nd;
   if constexpr (MASKED) {
@@ -1165,7 +1220,11 @@ __device__ __forceinline__ void lbm_body(const P &p) {
     [&] {
       int b = 0;
       if constexpr (MASKED) b = nd & 0x7f;
-      if (b == 0) collide_node<T, S, LAYOUT, 1, 0, COLL>(f, p);
+      if constexpr (coll_field(COLL)) {
+        if (b == 0) collide_node<T, S, LAYOUT, 1, 0, COLL>(f, p, &nf);
+      } else {
+        if (b == 0) collide_node<T, S, LAYOUT, 1, 0, COLL>(f, p);
+      }
       if constexpr (MASKED)
         apply_boundaries<T, S, LAYOUT, STREAM, 1, 0, COLL, ABBD>(p, b, c0, c1, c2, own, f, lane_slot, lane_rho, lane_j);
     }();
@@ -1210,6 +1269,17 @@ template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, 
 __global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsF<T> p) {
   static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
   static_assert(coll_forced(COLL), "a body force exists for BGK (5) and Smagorinsky (7)");
+  lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
+}
+
+// ... with a body force whose acceleration is a per-node field (COLL = 36 + the collision: 37, 39): the same body on
+// KParamsFF.  One-step kernels of the reference layout, no outlet depth, no packing (unit.inc, part force_field)
+template <typename T, class S, int LAYOUT, int COLL, bool STREAM, bool COLLIDE, bool MASKED,
+          int VEC, int SHIFT, int TUNE = 0, bool PACK = false, int ABBD = 0>
+__global__ void __launch_bounds__(kThreads) lbm_kernel(const KParamsFF<T> p) {
+  static_assert(VEC == 1 && SHIFT == 0, "one node per thread");
+  static_assert(coll_field(COLL) && LAYOUT == 0 && !PACK && ABBD == 0,
+                "a force field exists for BGK (37) and Smagorinsky (39), reference layout, plans without outlets");
   lbm_body<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, TUNE, PACK, ABBD>(p);
 }
 

@@ -65,6 +65,10 @@
 //                         (boundary_force.hpp) -- an object of its own again
 //   links (inst15_)       2-D and 3-D units: the pass of the interpolated bounce-back over a plan's link list and the two
 //                         launches of the momentum-exchange force over it (link_bounce.hpp) -- an object of its own again
+//   force_field (inst16_) every unit: the kernels with a body force whose acceleration is a per-node field (the kernels'
+//                         COLL | kCollForce | kCollField: BGK 37, Smagorinsky 39) -- the one-step variants of the
+//                         reference layout without the outlet depths, on a parameter block of their own (KParamsFF); no
+//                         launch of several steps.  Objects of their own again: every other plan launches what it did
 // LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
@@ -81,6 +85,7 @@
 #define LT_PART_spectrum 13
 #define LT_PART_boundary_force 14
 #define LT_PART_links 15
+#define LT_PART_force_field 16
 #define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
 #if LT_PART_IS(main)
@@ -101,14 +106,14 @@
 #elif LT_PART_IS(relaxations)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 1
-#elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible)
+#elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible) || LT_PART_IS(force_field)
 #define LT_ONE_STEP 1
 #define LT_SWEEP 0
 #elif LT_PART_IS(spectrum) || LT_PART_IS(boundary_force) || LT_PART_IS(links)
 #define LT_ONE_STEP 0
 #define LT_SWEEP 0
 #else
-#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible, spectrum, boundary_force or links"
+#error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible, spectrum, boundary_force, links or force_field"
 #endif
 #if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
 #error "the MRT collision exists on D2Q9 and D3Q27"
@@ -134,7 +139,8 @@ constexpr UnitTile kTile = two_step_tile<S, T>();
 // The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
 // to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
 template <int COLL>
-using ParamsOfQuadratic = std::conditional_t<coll_mrt(COLL), KParamsM<T>, std::conditional_t<coll_forced(COLL), KParamsF<T>, KParams<T>>>;
+using ParamsOfQuadratic = std::conditional_t<coll_mrt(COLL), KParamsM<T>, std::conditional_t<coll_forced(COLL), KParamsF<T>,
+                                             std::conditional_t<coll_field(COLL), KParamsFF<T>, KParams<T>>>>;
 template <int COLL>
 using ParamsOf = std::conditional_t<coll_incompressible(COLL), std::conditional_t<coll_forced(COLL), KParamsFI<T>, KParamsI<T>>,
                                     ParamsOfQuadratic<COLL>>;
@@ -183,6 +189,14 @@ void set_force(KParamsF<T> &p, const StepArgs &a) {
     p.accel[M::memory(c)] = (T)a.accel[c];
     p.shift[M::memory(c)] = (T)a.ueq_scale * (T)a.accel[c];     // guo.py:27-29: the product in the tensor's precision
   }
+  p.source_scale = (T)a.source_scale;
+}
+
+// per-node body force (lt_plan_set_force_field): the field and the two scales, each rounded to T once as set_force
+// rounds them; the kernels form the node's shift (kernels.hpp, load_node_force)
+void set_force_field(KParamsFF<T> &p, const StepArgs &a) {
+  p.accel_field = static_cast<const T *>(a.accel_field);
+  p.ueq_scale = (T)a.ueq_scale;
   p.source_scale = (T)a.source_scale;
 }
 
@@ -235,6 +249,7 @@ int launch(const StepArgs &a, const NameBuf *name) {
   P p = params_of<P>(a, a.n2);
   p.nvec_total = (unsigned)((long long)p.nv0 * a.n1 * a.planes);
   if constexpr (coll_forced(COLL)) set_force<LAYOUT>(p, a);
+  if constexpr (coll_field(COLL)) set_force_field(p, a);
   if constexpr (coll_mrt(COLL)) set_mrt(p, a);
   // the incompressible equilibrium's rho0: rounded once, as a Python float times a tensor of the plan's dtype is
   if constexpr (coll_incompressible(COLL)) p.rho0 = (T)a.rho0;
@@ -316,6 +331,19 @@ int one_step_incompressible_of(const StepArgs &a, const NameBuf *name) {
 #endif
   if (a.abb_depth > 1) return kNoKernel;
   LT_TRY_TWO_OUTLETS(0, C, kFused) LT_TRY_TWO_OUTLETS(0, C, kCollideOnly)
+  LT_COLLISION_SET(0, C, 0)
+  LT_COLLISION_SET(0, C, 1)
+  return kNoKernel;
+}
+#endif
+
+#if LT_PART_IS(force_field)
+// The one-step kernels of collision C with a force field: the variants of the reference layout that one_step_of gives
+// the uniform force, without the outlet depths (lt_plan_set_force_field refuses slab plans and every outlet)
+template <int C>
+int one_step_field_of(const StepArgs &a, const NameBuf *name) {
+  if (!a.accel_field && !name) return kNoKernel;      // a launch reads the field
+  if (a.n_pout > 0 || a.n_abb > 0 || a.abb_depth > 0 || a.pack_lo || a.pack_hi) return kNoKernel;
   LT_COLLISION_SET(0, C, 0)
   LT_COLLISION_SET(0, C, 1)
   return kNoKernel;
@@ -578,6 +606,7 @@ int dispatch(const StepArgs &a, const NameBuf *name) {
   // a constant-pressure outlet: part outlets has the kernels that apply boundaries (streaming alone applies none)
   if (a.n_pout > 0 && a.mode != kStreamOnly) return LT_CAT(outlets_, LT_TAG)(a, name);
   if (coll_forced(coll)) return LT_CAT(forced_, LT_TAG)(a, name);   // body force: part forced
+  if (coll_field(coll)) return LT_CAT(force_field_, LT_TAG)(a, name);   // ... as a per-node field: part force_field
   if (coll == kCollTrt || coll == kCollRegularized) return LT_CAT(relax_, LT_TAG)(a, name);   // part relaxations
 #if LT_HAS_MRT
   if (coll_mrt(coll)) return LT_CAT(mrt_, LT_TAG)(a, name);   // MRT: part mrt
@@ -812,6 +841,15 @@ int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
       return (int)hipGetLastError();
     }
   }
+  return kNoKernel;
+}
+#elif LT_PART_IS(force_field)
+// one-step kernels only; a.coll carries kCollField (api.hip, kernel_coll)
+int LT_CAT(force_field_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
+  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
+  if (a.coll == (kCollBgk | kCollForce | kCollField)) return one_step_field_of<kCollBgk | kCollForce | kCollField>(a, name);
+  if (a.coll == (kCollSmagorinsky | kCollForce | kCollField))
+    return one_step_field_of<kCollSmagorinsky | kCollForce | kCollField>(a, name);
   return kNoKernel;
 }
 #elif LT_PART_IS(spectrum)

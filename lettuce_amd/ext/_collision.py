@@ -5,7 +5,8 @@ Each ``__call__`` is a pure whole-field function ``flow -> tensor`` usable outsi
 ``Simulation`` (the reference's tests call ``collision(flow)`` directly).  On a native context
 and for the flow's grid-shaped state it is one launch of the engine's collide kernel;
 otherwise the reference's torch expressions are evaluated.  BGK and Smagorinsky take a body force
-(``force=Guo(...)`` / ``ShanChen(...)``, ext/_force.py), on the engine when its acceleration is uniform.
+(``force=Guo(...)`` / ``ShanChen(...)``, ext/_force.py), on the engine when its acceleration is uniform, and
+``force=GuoField(...)`` / ``ShanChenField(...)`` with an acceleration per node, on the engine as well.
 TRT and the regularised collision are on the engine for every lattice as well (one-step kernels; the plain two-step
 sweep on D3Q19 fp32); neither takes a force, as in the reference.  MRT takes a moment transform of
 ``lettuce_amd.moments``: with D2Q9Dellar, D2Q9Lallemand or D3Q27Hermite it is on the engine (one-step kernels), with any
@@ -53,7 +54,7 @@ def _engine_collide(flow, desc: NativeCollision):
         plan.set_equilibrium(*equilibrium)
     settings = desc.settings(flow)
     settings.apply(plan)
-    if kind in ("bgk", "smagorinsky") and settings.force is None:
+    if kind in ("bgk", "smagorinsky") and settings.force is None and settings.force_field is None:
         # the plan is shared by every collision object of this kind on the flow: one with a force may have used it last
         plan.set_force(None)
     return plan.collide(flow.f, torch.empty_like(flow.f), desc.tau(flow))

@@ -25,7 +25,7 @@ from ._equilibrium import QuadraticEquilibrium
 
 __all__ = ["ExtFlow", "TaylorGreenVortex", "TaylorGreenVortex2D", "TaylorGreenVortex3D",
            "Obstacle", "DoublyPeriodicShear2D", "DoublyPeriodicShear3D", "PoiseuilleFlow2D", "DecayingTurbulence",
-           "flow_by_name"]
+           "KolmogorovFlow2D", "flow_by_name"]
 
 
 class ExtFlow(Flow, ABC):
@@ -559,6 +559,72 @@ class DecayingTurbulence(ExtFlow):
         xyz = tuple(torch.linspace(0, endpoints[n], steps=self.resolution[n], device=self.context.device,
                                    dtype=self.context.dtype) for n in range(self.stencil.d))
         return torch.meshgrid(*xyz, indexing="ij")
+
+    @property
+    def boundaries(self) -> List["Boundary"]:
+        return []
+
+
+class KolmogorovFlow2D(ExtFlow):
+    """Kolmogorov flow: a doubly periodic box driven by the body force a_x = A sin(k y), the standard forced case (not in
+    the reference).  The force is a field: pass ``flow.acceleration_lu()`` to a ``GuoField`` or ``ShanChenField`` of
+    the collision.  The box is 2 pi x 2 pi in physical units and ``resolution[1]`` lattice nodes are the characteristic
+    length; ``wavenumber`` whole waves of the force fit into it, k = 2 pi wavenumber / ny per lattice node.  The
+    amplitude A = u_char_lu nu_lu k^2 makes the laminar steady state u_x = A / (nu k^2) sin(k y) peak at the
+    characteristic velocity (``analytic_solution``); a wavenumber > 1 at a high Reynolds number, started from a
+    perturbed state, is the forced-turbulence case."""
+
+    def __init__(self, context: "Context", resolution: Union[int, List[int]], reynolds_number, mach_number,
+                 wavenumber: int = 1, stencil: Optional["Stencil"] = None,
+                 equilibrium: Optional["Equilibrium"] = None):
+        self.wavenumber = int(wavenumber)
+        if self.wavenumber < 1:
+            raise LettuceException(f"KolmogorovFlow2D: wavenumber {wavenumber} (a whole number >= 1)")
+        self.stencil = D2Q9() if stencil is None else (stencil() if callable(stencil) else stencil)
+        super().__init__(context, resolution, reynolds_number, mach_number, self.stencil, equilibrium)
+
+    def make_resolution(self, resolution, stencil=None) -> List[int]:
+        if isinstance(resolution, int):
+            return [resolution] * 2
+        assert len(resolution) == 2, "the Kolmogorov flow is two-dimensional"
+        return list(resolution)
+
+    def make_units(self, reynolds_number, mach_number, resolution) -> "UnitConversion":
+        return UnitConversion(reynolds_number=reynolds_number, mach_number=mach_number,
+                              characteristic_length_lu=resolution[1], characteristic_length_pu=2 * torch.pi,
+                              characteristic_velocity_pu=1)
+
+    @property
+    def grid(self):
+        return torch.meshgrid(*_periodic_axes(self.resolution, 2 * torch.pi, self.context), indexing="ij")
+
+    def _sine(self):
+        """sin(k y_index) on the grid, [nx, ny]"""
+        nx, ny = self.resolution
+        j = torch.arange(ny, device=self.context.device, dtype=self.context.dtype)
+        return torch.sin(2 * torch.pi * self.wavenumber / ny * j)[None, :].expand(nx, ny)
+
+    @property
+    def amplitude_lu(self) -> float:
+        """A = u_char_lu nu_lu k^2, lattice units"""
+        k = 2 * torch.pi * self.wavenumber / self.resolution[1]
+        return float(self.units.characteristic_velocity_lu * self.units.viscosity_lu * k ** 2)
+
+    def acceleration_lu(self) -> torch.Tensor:
+        """the force field in lattice units, dense [2, nx, ny]: a_x = A sin(k y_index), a_y = 0"""
+        a = self.context.zero_tensor([2, *self.resolution])
+        a[0] = self.amplitude_lu * self._sine()
+        return a
+
+    def initial_pu(self) -> (torch.Tensor, torch.Tensor):
+        zeros = self.context.zero_tensor(self.resolution)
+        return zeros[None, ...], torch.stack(2 * [zeros], dim=0)
+
+    def analytic_solution(self, t: float = 0) -> (torch.Tensor, torch.Tensor):
+        """the laminar steady state in physical units (any t): p = 0, u_x = u_char sin(wavenumber y), u_y = 0"""
+        ux = self.units.characteristic_velocity_pu * self._sine()
+        u = torch.stack([ux, self.context.zero_tensor(self.resolution)], dim=0)
+        return self.context.zero_tensor(self.resolution)[None, ...], u
 
     @property
     def boundaries(self) -> List["Boundary"]:

@@ -9,13 +9,13 @@ kernels take.
 What a collision hands to a plan before a launch, apart from ``tau``, is one value record: ``CollisionSettings``.
 ``NativeCollision.settings(flow)`` reads it and ``CollisionSettings.apply(engine)`` calls the plan's setters; the
 steppers (``Simulation``, the slab drivers) and ``collision(flow)`` do nothing else with these values.  A new per-batch
-setting is therefore added in three places of this file: its late-bound field in ``NativeCollision``, its line in
+setting (the latest: a force field, ``set_force_field``) is therefore added in three places of this file: its late-bound field in ``NativeCollision``, its line in
 ``settings()``, and its field and line in ``CollisionSettings`` (``calls()``).
 """
 from dataclasses import dataclass, field
-from typing import Callable, Optional, Tuple
+from typing import Any, Callable, Optional, Tuple
 
-__all__ = ["NativeEquilibrium", "NativeCollision", "CollisionSettings", "NativeBoundary", "NativeForce"]
+__all__ = ["NativeEquilibrium", "NativeCollision", "CollisionSettings", "NativeBoundary", "NativeForce", "FieldRef"]
 
 
 @dataclass
@@ -37,13 +37,41 @@ class NativeForce:
     late, per batch, because the reference's schemes read ``force.acceleration`` and ``force.tau`` on every call
     (lettuce/ext/_force/guo.py:14-31, shan_chen.py:14-25)."""
     kind: str                                  # 'guo' | 'shan_chen'
-    acceleration: Callable[[], Tuple[float, ...]]      # lattice units, logical order x, y, z
+    acceleration: Optional[Callable[[], Tuple[float, ...]]]    # lattice units, logical order x, y, z; None with a field
     ueq_scale: Callable[[], float]             # u* = j / rho + ueq_scale * a / rho
     source_scale: Callable[[], float]          # factor of the source term (0: none)
+    # an acceleration that varies in space (``lt_plan_set_force_field``; GuoField, ShanChenField): the tensor
+    # [d, *resolution], read late like the acceleration -- the object may be replaced between batches, and the kernels
+    # read its memory at every launch, so values edited in place are seen without a call.  None: uniform
+    field: Optional[Callable[[], Any]] = None
 
     def plan_args(self) -> Tuple[Tuple[float, ...], float, float]:
         """the arguments of ``Plan.set_force`` now (hashable: part of the steppers' carry key)"""
         return (tuple(float(a) for a in self.acceleration()), float(self.ueq_scale()), float(self.source_scale()))
+
+    def field_args(self) -> Tuple["FieldRef", float, float]:
+        """the arguments of ``Plan.set_force_field`` now, the tensor inside a ``FieldRef`` (hashable as well)"""
+        return (FieldRef(self.field()), float(self.ueq_scale()), float(self.source_scale()))
+
+
+class FieldRef:
+    """A tensor inside a value record: compared and hashed by what the tensor IS now -- the object, its memory, its
+    version counter and its shape -- so that ``CollisionSettings`` stays hashable and two records are equal exactly when
+    nothing assigned or edited the field in between.  ``tensor`` is what ``Plan.set_force_field`` takes."""
+    __slots__ = ("tensor", "_key")
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+        self._key = (id(tensor), tensor.data_ptr(), tensor._version, tuple(tensor.shape))
+
+    def __eq__(self, other):
+        return isinstance(other, FieldRef) and self._key == other._key
+
+    def __hash__(self):
+        return hash(self._key)
+
+    def __repr__(self):
+        return f"FieldRef(shape={self._key[3]}, version={self._key[2]})"
 
 
 @dataclass(frozen=True)
@@ -55,6 +83,7 @@ class CollisionSettings:
     tau_minus: Optional[float] = None          # TRT
     mrt: Optional[Tuple[str, Tuple[float, ...]]] = None                    # the transform's name and its q rates
     force: Optional[Tuple[Tuple[float, ...], float, float]] = None         # NativeForce.plan_args()
+    force_field: Optional[Tuple[FieldRef, float, float]] = None            # NativeForce.field_args()
 
     def calls(self):
         """(setter, its arguments) for every value that is not None, in the one order every site calls them"""
@@ -67,6 +96,9 @@ class CollisionSettings:
             calls.append(("set_mrt", self.mrt))
         if self.force is not None:
             calls.append(("set_force", self.force))
+        if self.force_field is not None:
+            ref, ueq_scale, source_scale = self.force_field
+            calls.append(("set_force_field", (ref.tensor, ueq_scale, source_scale)))
         return calls
 
     @property
@@ -99,7 +131,7 @@ class NativeCollision:
     # 'trt': tau_minus, evaluated per batch like tau (the reference reads collision.tau_minus on every call,
     # lettuce/ext/_collision/trt_collision.py:25; `tau` is its tau_plus); None for the other kinds
     tau_minus: Optional[Callable[["Flow"], float]] = None
-    # 'bgk' / 'smagorinsky': the body force of the collision, or None
+    # 'bgk' / 'smagorinsky': the body force of the collision (uniform, or a field: NativeForce.field), or None
     force: Optional[NativeForce] = None
     # 'mrt': the class name of the moment transform ('D2Q9Dellar' | 'D2Q9Lallemand' | 'D3Q27Hermite') and its q
     # relaxation rates as a tuple of floats (hashable: part of the steppers' carry key), evaluated per batch like tau
@@ -115,7 +147,8 @@ class NativeCollision:
             smagorinsky=None if self.constant is None else float(self.constant(flow)),
             tau_minus=None if self.tau_minus is None else float(self.tau_minus(flow)),
             mrt=None if self.rates is None else (self.transform, tuple(self.rates(flow))),
-            force=None if self.force is None else self.force.plan_args())
+            force=None if self.force is None or self.force.field is not None else self.force.plan_args(),
+            force_field=None if self.force is None or self.force.field is None else self.force.field_args())
 
 
 @dataclass
