@@ -200,11 +200,9 @@ typedef const char *(*NameFn)(const StepArgs &, const NameBuf &);     // the buf
 #define LT_FIELD_kbc(s, t, q, d, kbc, roles) kbc
 #define LT_FIELD_roles(s, t, q, d, kbc, roles) roles
 
-// What the objects of a unit export (unit.inc, LT_PART).  Part main: the three entry points api.hip calls, which pass
-// on to the unit's other objects -- forced (the kernels with a body force) and relaxations (TRT and the regularised
-// collision) and outlets (plans with a constant-pressure outlet) and incompressible (the kernels of the incompressible
-// equilibrium) and force_field (the kernels with a per-node body force), every unit, sweeps and smagorinsky (3-D
-// units), roles (units with a role-wave sweep), mrt and mrt_outlets (D2Q9 and D3Q27), spectrum, boundary_force and links (2-D and 3-D units).  Declared for every unit, defined where the Makefile builds the part.
+// What the objects of a unit export.  The parts of a unit, what each holds and which of them pass on to which are
+// listed once, in the header of unit.inc (LT_PART).  Part main has the three entry points api.hip calls; declared for
+// every unit, defined where the Makefile builds the part.
 #define LT_DECLARE_UNIT(tag)                                   \
   int step_##tag(const StepArgs &);                            \
   int aux_##tag(const AuxArgs &);                              \

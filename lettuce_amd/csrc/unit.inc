@@ -24,7 +24,8 @@
 // the lattices of the moment transforms with an equilibrium of their own (mrt.hpp): D2Q9 and D3Q27
 #define LT_HAS_MRT (LT_FIELD(q, LT_UNIT) == 9 || LT_FIELD(q, LT_UNIT) == 27)
 
-// LT_PART names the object of the unit that is being built (Makefile: build/inst<N>_<tag>.o):
+// LT_PART names the object of the unit that is being built (Makefile: build/inst<N>_<tag>.o).  Which collisions a part
+// holds: its list below; which kernels of a collision exist: one_step_exists and sweep_exists.  Here: why it is an object
 //   main (inst_)          dispatch(), the auxiliary kernels and the three entry points api.hip calls; the one-step
 //                         kernels without a body force, the many-step, the 2-D and the masked two-step launches.  A 3-D
 //                         unit (LT_IS_3D) leaves its unmasked two-step launches and its Smagorinsky kernels to the next
@@ -36,40 +37,54 @@
 //                         kernel's SCHED = 1) -- that schedule wants another scheduler setting than the one-role kernels
 //   smagorinsky (inst4_)  3-D units: the one-step kernels of the Smagorinsky collision -- an object of its own so that
 //                         the build takes no longer than before (D3Q27 fp32 with its KBC kernels is the longest job)
-//   forced (inst5_)       every unit: the kernels with a body force (the kernels' COLL | kCollForce: BGK, Smagorinsky) -- every
-//                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; objects
-//                         of their own, so that the objects of the unforced kernels are what they were
-//   relaxations (inst6_)  every unit: the TRT and the regularised collision (kCollTrt, kCollRegularized) -- every
-//                         one-step variant BGK has and, where a unit has it (D3Q19 fp32), the plain two-step sweep; again
-//                         objects of their own: the earlier objects stay what they were and none of these is the longest job
+//   forced (inst5_)       every unit: the kernels with a uniform body force (the kernels' COLL | kCollForce), one-step
+//                         and the plain two-step sweep -- objects of their own, so that the objects of the unforced
+//                         kernels are what they were
+//   relaxations (inst6_)  every unit: the TRT and the regularised collision, one-step and the plain two-step sweep -- the
+//                         earlier objects stay what they were and none of these is the longest job
 //   outlets (inst7_)      every unit: the one-step kernels of plans with a constant-pressure outlet (EquilibriumOutletP;
-//                         the kernels' ABBD = kOutletsP + chain) -- every collision and every one-step variant the masked
-//                         kernels have, at the deepest chain of the layout only; objects of their own once more, so that
-//                         every plan without such an outlet launches the code it launched before.  This object: no
-//                         collision, BGK and KBC, and the entry point that passes on to the next two
-//   outlets2 (inst8_)     ... Smagorinsky, TRT and the regularised collision
-//   outlets3 (inst9_)     ... BGK and Smagorinsky with a body force -- three objects, because the chain of depth 2 inlines
-//                         the gather and the collision three times and one object per unit would be the longest job
+//                         the kernels' ABBD = kOutletsP + chain), so that every plan without such an outlet launches the
+//                         code it launched before.  This object: the entry point, which passes on to the next three
+//   outlets2 (inst8_), outlets3 (inst9_)  ... three objects, because the chain of depth 2 inlines the gather and the
+//                         collision three times and one object per unit would be the longest job
 //   mrt (inst10_)         units with LT_HAS_MRT: the multiple-relaxation-time collision (kCollMrt: Dellar on D2Q9,
-//                         Hermite on D3Q27; kCollMrtLallemand: Lallemand on D2Q9) -- every one-step variant BGK has, on
-//                         a parameter block of their own (KParamsM); no launch of several steps
+//                         Hermite on D3Q27; kCollMrtLallemand: Lallemand on D2Q9); no launch of several steps
 //   mrt_outlets (inst11_) ... and its kernels of plans with a constant-pressure outlet
 //   incompressible (inst12_)  every unit: the kernels of the incompressible equilibrium (the kernels' COLL |
-//                         kCollIncompressible: BGK, BGK with a body force, TRT, the regularised collision) -- the
-//                         one-step variants of the reference layout, on parameter
-//                         blocks of their own (KParamsI, KParamsFI), and the equilibrium and f_neq kernels; no launch of
-//                         several steps.  Objects of their own again: every other plan launches what it launched before
+//                         kCollIncompressible), and the equilibrium and f_neq kernels; no launch of several steps
 //   spectrum (inst13_)    2-D and 3-D units: the two launches of the energy spectrum (spectrum.hpp), which depend on the
-//                         scalar type and the dimension only -- an object of its own, so that no other object changes
+//                         scalar type and the dimension only
 //   boundary_force (inst14_)  2-D and 3-D units: the two launches of the momentum-exchange force on a bounce-back body
-//                         (boundary_force.hpp) -- an object of its own again
+//                         (boundary_force.hpp)
 //   links (inst15_)       2-D and 3-D units: the pass of the interpolated bounce-back over a plan's link list and the two
-//                         launches of the momentum-exchange force over it (link_bounce.hpp) -- an object of its own again
+//                         launches of the momentum-exchange force over it (link_bounce.hpp)
 //   force_field (inst16_) every unit: the kernels with a body force whose acceleration is a per-node field (the kernels'
-//                         COLL | kCollForce | kCollField: BGK 37, Smagorinsky 39) -- the one-step variants of the
-//                         reference layout without the outlet depths, on a parameter block of their own (KParamsFF); no
-//                         launch of several steps.  Objects of their own again: every other plan launches what it did
-// LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
+//                         COLL | kCollForce | kCollField); no launch of several steps
+// (parts 12 to 16: objects of their own so that every other plan launches what it launched before)
+// A part states the collision numbers it holds once: LT_COLLS_<part> those of its one-step kernels (which of their
+// variants exist: one_step_exists, below; a collision the unit lacks, unit_has, is skipped), LT_SWEEPS_<part> those of its
+// two-step sweeps (sweep_exists).  A new family: its list here, and its struct among the families below.
+#if LT_IS_3D
+#define LT_COLLS_main kCollNone, kCollBgk, kCollKbc
+#else
+#define LT_COLLS_main kCollNone, kCollBgk, kCollKbc, kCollSmagorinsky
+#endif
+#define LT_COLLS_smagorinsky kCollSmagorinsky
+#define LT_COLLS_forced kCollBgk | kCollForce, kCollSmagorinsky | kCollForce
+#define LT_COLLS_relaxations kCollTrt, kCollRegularized
+#define LT_COLLS_outlets kCollNone, kCollBgk, kCollKbc
+#define LT_COLLS_outlets2 kCollSmagorinsky, kCollTrt, kCollRegularized
+#define LT_COLLS_outlets3 LT_COLLS_forced
+#define LT_COLLS_mrt kCollMrt, kCollMrtLallemand
+#define LT_COLLS_mrt_outlets LT_COLLS_mrt
+#define LT_COLLS_incompressible                                                                               \
+  kCollBgk | kCollIncompressible, kCollBgk | kCollForce | kCollIncompressible, kCollTrt | kCollIncompressible, \
+      kCollRegularized | kCollIncompressible
+#define LT_COLLS_force_field kCollBgk | kCollForce | kCollField, kCollSmagorinsky | kCollForce | kCollField
+#define LT_SWEEPS_sweeps kCollNone, kCollBgk, kCollSmagorinsky
+#define LT_SWEEPS_roles kCollBgk
+#define LT_SWEEPS_forced kCollBgk | kCollForce
+#define LT_SWEEPS_relaxations kCollTrt, kCollRegularized
 #define LT_PART_main 1
 #define LT_PART_sweeps 2
 #define LT_PART_roles 3
@@ -88,31 +103,12 @@
 #define LT_PART_force_field 16
 #define LT_PART_IS_OUTLETS (LT_PART_IS(outlets) || LT_PART_IS(outlets2) || LT_PART_IS(outlets3) || LT_PART_IS(mrt_outlets))
 #define LT_PART_IS(name) (LT_CAT(LT_PART_, LT_PART) == LT_PART_##name)
-#if LT_PART_IS(main)
-#define LT_ONE_STEP 1
-#define LT_SWEEP 0
-#elif LT_PART_IS(sweeps)
-#define LT_ONE_STEP 0
-#define LT_SWEEP 1
-#elif LT_PART_IS(roles)
-#define LT_ONE_STEP 0
-#define LT_SWEEP 1
-#elif LT_PART_IS(smagorinsky)
-#define LT_ONE_STEP 1
-#define LT_SWEEP 0
-#elif LT_PART_IS(forced)
-#define LT_ONE_STEP 1
-#define LT_SWEEP 1
-#elif LT_PART_IS(relaxations)
-#define LT_ONE_STEP 1
-#define LT_SWEEP 1
-#elif LT_PART_IS_OUTLETS || LT_PART_IS(mrt) || LT_PART_IS(incompressible) || LT_PART_IS(force_field)
-#define LT_ONE_STEP 1
-#define LT_SWEEP 0
-#elif LT_PART_IS(spectrum) || LT_PART_IS(boundary_force) || LT_PART_IS(links)
-#define LT_ONE_STEP 0
-#define LT_SWEEP 0
-#else
+// LT_ONE_STEP: the object holds the one-step launcher and its ladder; LT_SWEEP: the two-step sweep launcher
+#define LT_ONE_STEP                                                                                                  \
+  (LT_PART_IS(main) || LT_PART_IS(smagorinsky) || LT_PART_IS(forced) || LT_PART_IS(relaxations) || LT_PART_IS_OUTLETS || \
+   LT_PART_IS(mrt) || LT_PART_IS(incompressible) || LT_PART_IS(force_field))
+#define LT_SWEEP (LT_PART_IS(sweeps) || LT_PART_IS(roles) || LT_PART_IS(forced) || LT_PART_IS(relaxations))
+#if !LT_ONE_STEP && !LT_SWEEP && !LT_PART_IS(spectrum) && !LT_PART_IS(boundary_force) && !LT_PART_IS(links)
 #error "LT_PART: main, sweeps, roles, smagorinsky, forced, relaxations, outlets, outlets2, outlets3, mrt, mrt_outlets, incompressible, spectrum, boundary_force, links or force_field"
 #endif
 #if (LT_PART_IS(mrt) || LT_PART_IS(mrt_outlets)) && !LT_HAS_MRT
@@ -136,14 +132,8 @@ using T = LT_T;
 // the unit's 3-D two-step tile (launch_limits.hpp)
 constexpr UnitTile kTile = two_step_tile<S, T>();
 
-// The parameter block of a kernel with collision COLL, and a launch's: zeroed, then every field that means the same
-// to all launchers.  A launcher sets what is its own on top.  n2: the planes of the field (the 2-D launchers: 1)
-template <int COLL>
-using ParamsOfQuadratic = std::conditional_t<coll_mrt(COLL), KParamsM<T>, std::conditional_t<coll_forced(COLL), KParamsF<T>,
-                                             std::conditional_t<coll_field(COLL), KParamsFF<T>, KParams<T>>>>;
-template <int COLL>
-using ParamsOf = std::conditional_t<coll_incompressible(COLL), std::conditional_t<coll_forced(COLL), KParamsFI<T>, KParamsI<T>>,
-                                    ParamsOfQuadratic<COLL>>;
+// A launch's parameter block: zeroed, then every field that means the same to all launchers.  A launcher sets what is
+// its own on top (the one-step kernels: their family's fill, below).  n2: the planes of the field (the 2-D launchers: 1)
 template <class P>
 P params_of(const StepArgs &a, int n2) {
   P p{};
@@ -178,33 +168,81 @@ P params_of(const StepArgs &a, int n2) {
   return p;
 }
 
-// uniform body force (lt_plan_set_force): the acceleration permuted from the logical order x, y, z to the memory axes
-// of the layout, as the kernels read the velocity
-template <int LAYOUT>
-void set_force(KParamsF<T> &p, const StepArgs &a) {
-  using M = MemMap<S, LAYOUT>;
-  p.accel[0] = p.accel[1] = p.accel[2] = T(0);
-  p.shift[0] = p.shift[1] = p.shift[2] = T(0);
-  for (int c = 0; c < S::D; ++c) {
-    p.accel[M::memory(c)] = (T)a.accel[c];
-    p.shift[M::memory(c)] = (T)a.ueq_scale * (T)a.accel[c];     // guo.py:27-29: the product in the tensor's precision
+// ---- The families of collisions ----
+// A family: the parameter block its kernels take (kernels.hpp: a type of its own each, so that every other kernel keeps
+// its argument block and with it its code), what a launch fills in beyond params_of, and which one-step variants the family
+// has beside the plain kernels of the reference layout:
+//   slab      the slab layout of a 3-D unit (multi-GPU z-slabs), and with it the packed plane launch
+//   depths    the deepest chain of anti-bounce-back outlets (kernels.hpp, neighbour_moments DEPTH): 2 = all of them
+//   pressure  the kernels of plans with a constant-pressure outlet (ABBD = kOutletsP + chain)
+// A new family is one struct here, one line in FamilyOf and one list for its part (LT_COLLS_<part>, above).
+struct Quadratic {      // none, BGK, KBC, Smagorinsky, TRT, the regularised collision: every variant there is
+  using P = KParams<T>;
+  static constexpr bool slab = true, pressure = true;
+  static constexpr int depths = 2;
+  template <int LAYOUT>
+  static void fill(P &, const StepArgs &) {}
+};
+// uniform body force (lt_plan_set_force; 5, 7): every variant BGK has.  The acceleration permuted from the logical order
+// x, y, z to the memory axes of the layout, as the kernels read the velocity
+struct Forced : Quadratic {
+  using P = KParamsF<T>;
+  template <int LAYOUT>
+  static void fill(P &p, const StepArgs &a) {
+    using M = MemMap<S, LAYOUT>;
+    p.accel[0] = p.accel[1] = p.accel[2] = T(0);
+    p.shift[0] = p.shift[1] = p.shift[2] = T(0);
+    for (int c = 0; c < S::D; ++c) {
+      p.accel[M::memory(c)] = (T)a.accel[c];
+      p.shift[M::memory(c)] = (T)a.ueq_scale * (T)a.accel[c];     // guo.py:27-29: the product in the tensor's precision
+    }
+    p.source_scale = (T)a.source_scale;
   }
-  p.source_scale = (T)a.source_scale;
-}
-
-// per-node body force (lt_plan_set_force_field): the field and the two scales, each rounded to T once as set_force
-// rounds them; the kernels form the node's shift (kernels.hpp, load_node_force)
-void set_force_field(KParamsFF<T> &p, const StepArgs &a) {
-  p.accel_field = static_cast<const T *>(a.accel_field);
-  p.ueq_scale = (T)a.ueq_scale;
-  p.source_scale = (T)a.source_scale;
-}
-
-// the rates of an MRT plan (lt_plan_set_mrt): r_i = 1 / s_i with both the rate and the quotient in T -- the reference
-// converts the rates to the context's dtype and divides there on every call (mrt_collision.py:18-24)
-void set_mrt(KParamsM<T> &p, const StepArgs &a) {
-  for (int i = 0; i < kMrtMaxQ; ++i) p.r[i] = i < S::Q ? T(1) / (T)a.mrt_rates[i] : T(0);
-}
+};
+// MRT (lt_plan_set_mrt; 10, 11): every variant BGK has.  r_i = 1 / s_i with both the rate and the quotient in T -- the
+// reference converts the rates to the context's dtype and divides there on every call (mrt_collision.py:18-24)
+struct Mrt : Quadratic {
+  using P = KParamsM<T>;
+  template <int LAYOUT>
+  static void fill(P &p, const StepArgs &a) {
+    for (int i = 0; i < kMrtMaxQ; ++i) p.r[i] = i < S::Q ? T(1) / (T)a.mrt_rates[i] : T(0);
+  }
+};
+// the incompressible equilibrium (lt_plan_set_equilibrium, which refuses slab plans and the constant-pressure outlet; 17,
+// 24, 25 and with a body force 21): the reference layout with its outlet depths.  rho0 rounded once, as a Python float
+// times a tensor of the plan's dtype is
+template <class Base, class Block>
+struct Incompressible : Base {
+  using P = Block;
+  static constexpr bool slab = false, pressure = false;
+  template <int LAYOUT>
+  static void fill(P &p, const StepArgs &a) {
+    Base::template fill<LAYOUT>(p, a);
+    p.rho0 = (T)a.rho0;
+  }
+};
+// per-node body force (lt_plan_set_force_field, which refuses slab plans and every outlet; 37, 39): the reference layout
+// without the outlet depths.  The field and the two scales, each rounded to T once as the uniform force rounds them; the
+// kernels form the node's shift (kernels.hpp, load_node_force)
+struct ForceField : Quadratic {
+  using P = KParamsFF<T>;
+  static constexpr bool slab = false, pressure = false;
+  static constexpr int depths = 0;
+  template <int LAYOUT>
+  static void fill(P &p, const StepArgs &a) {
+    p.accel_field = static_cast<const T *>(a.accel_field);
+    p.ueq_scale = (T)a.ueq_scale;
+    p.source_scale = (T)a.source_scale;
+  }
+};
+template <int COLL>
+using FamilyOf =
+    std::conditional_t<coll_field(COLL), ForceField,
+    std::conditional_t<coll_incompressible(COLL), std::conditional_t<coll_forced(COLL), Incompressible<Forced, KParamsFI<T>>,
+                                                                     Incompressible<Quadratic, KParamsI<T>>>,
+    std::conditional_t<coll_forced(COLL), Forced, std::conditional_t<coll_mrt(COLL), Mrt, Quadratic>>>>;
+template <int COLL>
+using ParamsOf = typename FamilyOf<COLL>::P;
 
 // Kernel names, as lt_plan_kernel_name reports them: the kernel's identifier and its template arguments behind the
 // scalar type and the lattice, "lbm2m_kernel<float, lt::D3Q19, 0, 1, 64, 8, 2>".  An argument wrapped in elided() is a
@@ -232,9 +270,53 @@ int kernel_name(const NameBuf &out, const char *kernel, A... args) {
 
 #if LT_ONE_STEP
 
+// ---- Which one-step kernels exist ----
+// The collisions of the unit: KBC where the lattice has it, the MRT transforms of mrt.hpp (Lallemand on D2Q9 only)
+constexpr bool unit_has(int coll) {
+  if (coll == kCollKbc) return LT_HAS_KBC;
+  if (coll_mrt(coll)) return LT_HAS_MRT && (coll == kCollMrt || !LT_IS_3D);
+  return true;
+}
+
+// Plans with a constant-pressure outlet, alone or beside anti-bounce-back outlets, have one chain depth per layout, the
+// deepest a plan of that layout can need (api.hip, abb_depth_of): outlets on all three axes in the reference layout of a
+// 3-D unit (2), on two axes in the slab layout and in 2-D (1); two outlets on the one axis of a 1-D lattice count as
+// depth 1 too (on a lattice of two nodes each outlet's neighbour lies in the other's plane).  A plan with fewer axes or
+// one outlet takes the same kernel: the chain is followed only where a lower outlet's plane holds the neighbour.
+constexpr int outlet_chain(int d, int layout) { return d == 3 && layout == 0 ? 2 : 1; }
+
+// Whether the library has lbm_kernel<T, S, LAYOUT, COLL, MODE's STREAM and COLLIDE, MASKED, 1, 0, TUNE, PACK, ABBD> on a
+// lattice of d dimensions: the one statement of the set.  one_step_of instantiates what holds here and nothing else.
+// Product kernels, one node per thread (VEC = 1).  Measured on MI355X (profiles/r01_variant_sweep*): for this 2q-stream
+// kernel 8 waves/SIMD of scalar accesses beat 16-byte accesses at 3-4 waves/SIMD by 8-13 %, and nontemporal stores
+// (+3-4 %) and loads (+1.6 %) help once the populations exceed the caches (TUNE 3).  TUNE 0 (cached accesses) is kept
+// for grids that fit in L2 / Infinity Cache.
+template <int COLL>
+constexpr bool one_step_exists(int d, int layout, int mode, bool masked, int tune, bool pack, int abbd) {
+  using F = FamilyOf<COLL>;
+  if (!unit_has(COLL)) return false;
+  // the slab layout: 3-D units
+  if (layout != 0 && !(layout == 1 && d == 3 && F::slab)) return false;
+  // the slab boundary-plane launch with fused halo packing: fused, cached accesses; otherwise both cache policies
+  if (pack ? !(layout == 1 && mode == kFused && tune == 0) : !(tune == 0 || tune == 3)) return false;
+  // the one kernel that does not collide: no outlet depth (streaming alone applies no boundary)
+  if (mode == kStreamOnly) return COLL == kCollNone && abbd == 0;
+  if (mode != kFused && mode != kCollideOnly) return false;
+  if (abbd == 0) return true;
+  // the outlet depths: masked kernels that apply boundaries, i.e. fused and collide-only
+  if (!masked) return false;
+  // plans with a constant-pressure outlet: both cache policies and the packed launch
+  if (abbd == kOutletsP + outlet_chain(d, layout)) return F::pressure;
+  if (abbd > F::depths || tune != 0 || pack) return false;
+  // two anti-bounce-back outlets (DEPTH 1): both layouts; outlets on all three axes of a 3-D flow (their planes meet in
+  // corners: DEPTH 2): reference layout
+  return abbd == 1 || (abbd == 2 && d == 3 && layout == 0);
+}
+
 // one node per thread: the kernels' VEC = 1, SHIFT = 0
 template <int LAYOUT, int COLL, int MODE, bool MASKED, int TUNE = 0, bool PACK = false, int ABBD = 0>
 int launch(const StepArgs &a, const NameBuf *name) {
+  static_assert(one_step_exists<COLL>(S::D, LAYOUT, MODE, MASKED, TUNE, PACK, ABBD), "a kernel of the set above");
   constexpr bool STREAM = MODE != kCollideOnly, COLLIDE = MODE != kStreamOnly;
   constexpr bool OCC4 = (COLL == kCollKbc && MASKED && sizeof(T) == 4 && S::Q == 27 && ABBD == 0);
   using P = ParamsOf<COLL>;
@@ -248,11 +330,7 @@ int launch(const StepArgs &a, const NameBuf *name) {
     kern = lbm_kernel<T, S, LAYOUT, COLL, STREAM, COLLIDE, MASKED, 1, 0, TUNE, PACK, ABBD>;
   P p = params_of<P>(a, a.n2);
   p.nvec_total = (unsigned)((long long)p.nv0 * a.n1 * a.planes);
-  if constexpr (coll_forced(COLL)) set_force<LAYOUT>(p, a);
-  if constexpr (coll_field(COLL)) set_force_field(p, a);
-  if constexpr (coll_mrt(COLL)) set_mrt(p, a);
-  // the incompressible equilibrium's rho0: rounded once, as a Python float times a tensor of the plan's dtype is
-  if constexpr (coll_incompressible(COLL)) p.rho0 = (T)a.rho0;
+  FamilyOf<COLL>::template fill<LAYOUT>(p, a);
   p.abb0_slot = a.n0 % 64 == 0 ? a.abb0_slot : 0;
   if (p.nvec_total == 0) return 0;
   const unsigned grid = (p.nvec_total + kThreads - 1) / kThreads;
@@ -262,224 +340,185 @@ int launch(const StepArgs &a, const NameBuf *name) {
   return (int)hipGetLastError();
 }
 
-// Product kernels: one node per thread (VEC = 1).  Measured on MI355X (profiles/r01_variant_sweep*):
-// for this 2q-stream kernel 8 waves/SIMD of scalar accesses beat 16-byte accesses at 3-4
-// waves/SIMD by 8-13 %, and nontemporal stores (+3-4 %) and loads (+1.6 %) help once the
-// populations exceed the caches (TUNE 3).  TUNE 0 (cached accesses) is kept for grids that fit in
-// L2 / Infinity Cache.
-#define LT_TRY(LAYOUT, COLL, MODE, MASKED)                                    \
-  if (a.layout == LAYOUT && a.mode == MODE && a.masked == MASKED) {           \
-    if (a.tune == 0) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 0>(a, name); \
-    if (a.tune == 3) return launch<LAYOUT, COLL, MODE, (MASKED != 0), 3>(a, name); \
+// ---- The one ladder ----
+// A one-step kernel's template axes as one number: the variant is the cache policy 0 or 3, or the packed launch; the
+// depth slot is ABBD 0, 1, 2 or kOutletsP + 1, kOutletsP + 2
+// how many values each axis has: layouts, modes (fused, collide-only, stream-only), masked, variants, depth slots
+constexpr int kLayouts = 2, kModes = 3, kMaskings = 2, kVariants = 3, kSlots = 5;
+constexpr int kOneSteps = kLayouts * kModes * kMaskings * kVariants * kSlots;
+struct OneStep {
+  int layout, mode, masked, variant, slot;
+  constexpr int index() const { return (((layout * kModes + mode) * kMaskings + masked) * kVariants + variant) * kSlots + slot; }
+  constexpr int tune() const { return variant == 1 ? 3 : 0; }
+  constexpr bool pack() const { return variant == 2; }
+  constexpr int abbd() const { return slot < 3 ? slot : kOutletsP + slot - 2; }
+};
+constexpr OneStep one_step_at(int i) {
+  return {i / (kSlots * kVariants * kMaskings * kModes), i / (kSlots * kVariants * kMaskings) % kModes,
+          i / (kSlots * kVariants) % kMaskings, i / kSlots % kVariants, i % kSlots};
+}
+constexpr bool one_steps_numbered() {
+  for (int i = 0; i < kOneSteps; ++i)
+    if (one_step_at(i).index() != i || one_step_at(i).layout >= kLayouts) return false;
+  return true;
+}
+static_assert(one_steps_numbered(), "index() and one_step_at() are inverses over all candidates");
+
+// candidate I of collision C: launched (or named) if this object has it and the arguments want it.  An outlets part
+// holds the kernels of the plans with a constant-pressure outlet, every other part the rest
+template <int C, int I>
+bool take(int wanted, const StepArgs &a, const NameBuf *name, int &result) {
+  constexpr OneStep k = one_step_at(I);
+  if constexpr ((k.abbd() > kOutletsP) == (LT_PART_IS_OUTLETS != 0) &&
+                one_step_exists<C>(S::D, k.layout, k.mode, k.masked != 0, k.tune(), k.pack(), k.abbd())) {
+    if (wanted != I) return false;
+    result = launch<k.layout, C, k.mode, (k.masked != 0), k.tune(), k.pack(), k.abbd()>(a, name);
+    return true;
+  } else {
+    return false;
   }
+}
+template <int C, int... I>
+int take_any(int wanted, const StepArgs &a, const NameBuf *name, std::integer_sequence<int, I...>) {
+  int result = kNoKernel;
+  (void)(take<C, I>(wanted, a, name, result) || ...);
+  return result;
+}
 
-// slab boundary-plane launch with fused halo packing (fused mode, slab layout)
-#define LT_TRY_PACK(COLL, MASKED)                                                                             \
-  if (a.layout == 1 && a.mode == kFused && a.masked == MASKED && a.pack_lo != nullptr && a.abb_depth == 0)    \
-    return launch<1, COLL, kFused, (MASKED != 0), 0, true>(a, name);
-
-// plans with two anti-bounce-back outlets (kernels.hpp, neighbour_moments DEPTH 1): masked kernels that
-// apply boundaries, i.e. fused and collide-only
-#define LT_TRY_TWO_OUTLETS(LAYOUT, COLL, MODE)                                 \
-  if (a.layout == LAYOUT && a.mode == MODE && a.masked && a.abb_depth == 1)    \
-    return launch<LAYOUT, COLL, MODE, true, 0, false, 1>(a, name);
-
-// outlets on all three axes of a 3-D flow (their planes meet in corners: DEPTH 2), reference layout
-#define LT_TRY_THREE_AXES(COLL, MODE)                                   \
-  if (a.layout == 0 && a.mode == MODE && a.masked && a.abb_depth == 2)  \
-    return launch<0, COLL, MODE, true, 0, false, 2>(a, name);
-
-#define LT_COLLISION_SET(LAYOUT, COLL, MASKED) \
-  LT_TRY(LAYOUT, COLL, kFused, MASKED)         \
-  LT_TRY(LAYOUT, COLL, kCollideOnly, MASKED)
-
-// The one-step kernels of collision C, fused and collide-only: main has them for 0 (none), 1 (BGK) and, with
-// LT_HAS_KBC, 2; Smagorinsky (3) has every variant BGK has, and so have BGK and Smagorinsky with a body force (5, 7),
-// TRT (8), the regularised collision (9) and MRT (10, 11).
-// The order matters where the conditions overlap: the outlet depths before the rest, packed before the plain slab set.
+// The one-step kernel of collision C that the arguments select: what they want, derived once, then the walk over the
+// set.  Launching and naming are the same path down to launch(), so a plan's kernel name is the kernel a launch takes.
 template <int C>
 int one_step_of(const StepArgs &a, const NameBuf *name) {
-#if LT_IS_3D
-  LT_TRY_THREE_AXES(C, kFused) LT_TRY_THREE_AXES(C, kCollideOnly)
-#endif
-  if (a.abb_depth > 1) return kNoKernel;
-  LT_TRY_TWO_OUTLETS(0, C, kFused) LT_TRY_TWO_OUTLETS(0, C, kCollideOnly)
-#if LT_IS_3D
-  LT_TRY_TWO_OUTLETS(1, C, kFused) LT_TRY_TWO_OUTLETS(1, C, kCollideOnly)
-#endif
-  // reference layout
-  LT_COLLISION_SET(0, C, 0)
-  LT_COLLISION_SET(0, C, 1)
-#if LT_IS_3D
-  // slab layout (multi-GPU z-slabs)
-  LT_TRY_PACK(C, 0)
-  LT_TRY_PACK(C, 1)
-  LT_COLLISION_SET(1, C, 0)
-  LT_COLLISION_SET(1, C, 1)
-#endif
-  return kNoKernel;
-}
-
-#if LT_PART_IS(incompressible)
-// The one-step kernels of collision C with the incompressible equilibrium: every variant of the reference layout that
-// one_step_of has (lt_plan_set_equilibrium refuses slab plans and the constant-pressure outlet)
-template <int C>
-int one_step_incompressible_of(const StepArgs &a, const NameBuf *name) {
-  if (a.n_pout > 0 || a.pack_lo || a.pack_hi) return kNoKernel;
-#if LT_IS_3D
-  LT_TRY_THREE_AXES(C, kFused) LT_TRY_THREE_AXES(C, kCollideOnly)
-#endif
-  if (a.abb_depth > 1) return kNoKernel;
-  LT_TRY_TWO_OUTLETS(0, C, kFused) LT_TRY_TWO_OUTLETS(0, C, kCollideOnly)
-  LT_COLLISION_SET(0, C, 0)
-  LT_COLLISION_SET(0, C, 1)
-  return kNoKernel;
-}
-#endif
-
-#if LT_PART_IS(force_field)
-// The one-step kernels of collision C with a force field: the variants of the reference layout that one_step_of gives
-// the uniform force, without the outlet depths (lt_plan_set_force_field refuses slab plans and every outlet)
-template <int C>
-int one_step_field_of(const StepArgs &a, const NameBuf *name) {
-  if (!a.accel_field && !name) return kNoKernel;      // a launch reads the field
-  if (a.n_pout > 0 || a.n_abb > 0 || a.abb_depth > 0 || a.pack_lo || a.pack_hi) return kNoKernel;
-  LT_COLLISION_SET(0, C, 0)
-  LT_COLLISION_SET(0, C, 1)
-  return kNoKernel;
-}
-#endif
-
-#if LT_PART_IS_OUTLETS
-// Plans with a constant-pressure outlet, alone or beside anti-bounce-back outlets: masked kernels that apply boundaries
-// (fused and collide-only), both cache policies, the packed plane launch of the slabs.  One chain depth per layout, the
-// deepest a plan of that layout can need (api.hip, abb_depth_of): outlets on all three axes in the reference layout of a
-// 3-D unit (2), on two axes in the slab layout and in 2-D (1); two outlets on the one axis of a 1-D lattice count as depth 1
-// too (on a lattice of two nodes each outlet's neighbour lies in the other's plane).  A plan with fewer axes or one outlet
-// takes the same kernel: the chain is followed only where a lower outlet's plane holds the neighbour.
-template <int LAYOUT>
-constexpr int kOutletChain = S::D == 3 && LAYOUT == 0 ? 2 : 1;
-
-template <int C, int LAYOUT>
-int pressure_outlets_in(const StepArgs &a, const NameBuf *name) {
-  constexpr int ABBD = kOutletsP + kOutletChain<LAYOUT>;
-  if (a.abb_depth > kOutletChain<LAYOUT>) return kNoKernel;
-  if constexpr (LAYOUT == 1) {
-    if (a.mode == kFused && a.pack_lo != nullptr) return launch<1, C, kFused, true, 0, true, ABBD>(a, name);
+  using F = FamilyOf<C>;
+  if (a.layout < 0 || a.layout > 1 || a.mode < kFused || a.mode > kStreamOnly) return kNoKernel;
+  if constexpr (coll_field(C)) {
+    if (!a.accel_field && !name) return kNoKernel;      // a launch reads the field
   }
-  if (a.mode == kFused && a.tune == 0) return launch<LAYOUT, C, kFused, true, 0, false, ABBD>(a, name);
-  if (a.mode == kFused && a.tune == 3) return launch<LAYOUT, C, kFused, true, 3, false, ABBD>(a, name);
-  if (a.mode == kCollideOnly && a.tune == 0) return launch<LAYOUT, C, kCollideOnly, true, 0, false, ABBD>(a, name);
-  if (a.mode == kCollideOnly && a.tune == 3) return launch<LAYOUT, C, kCollideOnly, true, 3, false, ABBD>(a, name);
-  return kNoKernel;
+  OneStep w = {a.layout, a.mode, a.masked != 0, a.tune == 0 ? 0 : (a.tune == 3 ? 1 : -1), 0};
+  if (a.mode != kStreamOnly) {      // streaming alone applies no boundary: no check of the outlets
+    // a family without the slab layout takes no message buffer, one without outlet depths no outlet
+    if (!F::slab && (a.pack_lo || a.pack_hi)) return kNoKernel;
+    if (F::depths == 0 && (a.n_abb > 0 || a.abb_depth > 0)) return kNoKernel;
+    if (a.abb_depth < 0 || a.abb_depth > 2) return kNoKernel;
+    const int chain = outlet_chain(S::D, a.layout);
+    if (a.n_pout > 0) {
+      // a constant-pressure outlet: the chain kernel of the layout, which covers every depth up to its own
+      if (!a.masked || a.abb_depth > chain) return kNoKernel;
+      w.slot = 2 + chain;
+    } else if (a.masked || a.abb_depth > 1) {
+      // without masks nothing applies an outlet: depth 1 takes the plain kernel, depth 2 has none
+      w.slot = a.abb_depth;
+    }
+    // the depths of the anti-bounce-back outlets and the packed launch ignore a.tune; a.tune == 1 has no plain kernel.
+    // Packed comes before the plain slab set, and only at depth 0 or with a constant-pressure outlet
+    if (w.slot == 1 || w.slot == 2) w.variant = 0;
+    else if (a.layout == 1 && a.mode == kFused && a.pack_lo != nullptr && (a.abb_depth == 0 || a.n_pout > 0)) w.variant = 2;
+  }
+  if (w.variant < 0) return kNoKernel;
+  return take_any<C>(w.index(), a, name, std::make_integer_sequence<int, kOneSteps>());
 }
 
-template <int C>
-int pressure_outlets_of(const StepArgs &a, const NameBuf *name) {
-  if (!a.masked) return kNoKernel;
-  if (a.layout == 0) return pressure_outlets_in<C, 0>(a, name);
-#if LT_IS_3D
-  if (a.layout == 1) return pressure_outlets_in<C, 1>(a, name);
-#endif
-  return kNoKernel;
+template <int... C>
+constexpr bool is_one_of(int coll) { return ((coll == C) || ...); }
+
+// the collision of the list that is `coll` (the arguments', or none for a launch that only streams)
+template <int... C>
+int one_step_in(int coll, const StepArgs &a, const NameBuf *name) {
+  int result = kNoKernel;
+  (void)((coll == C && ((result = one_step_of<C>(a, name)), true)) || ...);
+  return result;
 }
-#endif
 
 #endif  // LT_ONE_STEP
 
 #if LT_SWEEP
-// Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
-// returns kNoKernel when this (lattice, dtype) has no instantiation or the grid does not tile.
-// one node per thread and per block: the kernel's NPT = NPB = 1
-// SCHED 1: separate producer and consumer waves (twostep_roles.hpp)
-// Smagorinsky (COLL 3), BGK with a body force (COLL 5), TRT (8) and the regularised collision (9): the plain one-role
-// sweep of D3Q19 fp32
-template <int LAYOUT, int COLL, int T0, int T1, int MODE = 0, int SCHED = 0>
-int launch_twice(const StepArgs &a, const NameBuf *name) {
-  if constexpr (S::D == 3 && T0 > 0 &&
-                (COLL == kCollNone || COLL == kCollBgk ||
-                 ((COLL == kCollSmagorinsky || COLL == (kCollBgk | kCollForce) || COLL == kCollTrt || COLL == kCollRegularized) &&
-                  S::Q == 19 && sizeof(T) == 4 && MODE == 0 && SCHED == 0))) {
-    using B = TwoStep<T, S, T0, T1>;
-    if (name) return kernel_name(*name, "lbm2_kernel", LAYOUT, COLL, T0, T1, 1, MODE, 1, elided(SCHED));
-    if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < min_segment(false) || a.masked || a.planes < 1 || a.p_stride != 1 ||
-        !plane_addressable(a.n0, a.n1, sizeof(T)))
-      return kNoKernel;
-    if (MODE == 2 && (!a.signal || a.planes2 < 2 || a.planes2 > a.seg_len || a.seg_len < 2)) return kNoKernel;
-    using P = ParamsOf<COLL>;
-    P p = params_of<P>(a, a.n2);
-    // the output planes: [p_begin, p_end) and, at a slab's other edge, [p_begin2, p_end2); a.seg_len of them per workgroup
-    p.p_end = a.p_begin + a.planes;
-    p.p_begin2 = a.p_begin2;
-    p.p_end2 = a.p_begin2 + a.planes2;
-    if constexpr (coll_forced(COLL)) set_force<LAYOUT>(p, a);
-    p.nb = a.shift == 3 ? 1 : (a.shift == 4 ? 2 : 0);   // A/B: 1 = no XCD-aware renumbering of the workgroups, 2 = per segment layer
-    // MODE 2: the edge workgroups first, each adds 1 to *signal (kernels.hpp, KParams)
-    p.signal = MODE == 2 ? a.signal : nullptr;
-    p.edge_first = MODE == 2 ? 1 : 0;
-    p.ghost_lo = static_cast<const T *>(a.ghost_lo);
-    p.ghost_hi = static_cast<const T *>(a.ghost_hi);
-    p.lo = a.interior_begin; p.hi = a.interior_end;
-    const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len +
-                                                                   (a.planes2 + a.seg_len - 1) / a.seg_len));
-    constexpr int threads = SCHED ? RoleWaves<B::NI, B::NO>::THREADS : (B::NI + 63) / 64 * 64;
-    void (*kern)(const P, const int) = lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1, SCHED>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, a.stream, p, a.seg_len);
-    return (int)hipGetLastError();
-  } else {
-    return kNoKernel;
-  }
+// ---- Which two-step sweeps exist ----
+// Whether the unit has lbm2_kernel<T, S, LAYOUT, COLL, W, R, 1, MODE, 1, SCHED> on its tile of W x R nodes (kTile): the
+// one statement of the set.  sweep_in instantiates what holds here and nothing else.
+constexpr bool sweep_exists(int coll, int layout, int mode, int sched) {
+  if (S::D != 3 || kTile.rows == 0 || layout < 0 || layout > 1) return false;
+  // MODE 1: the slab edge launch with fused halo packing; MODE 2: the whole slab, edge workgroups first -- slab layout
+  if (mode != 0 && !(layout == 1 && (mode == 1 || mode == 2))) return false;
+  // SCHED 1: separate producer and consumer waves (twostep_roles.hpp) -- plain BGK, where they won their A/B (DESIGN.md
+  // section 7)
+  if (sched != 0) return sched == 1 && LT_HAS_ROLES && coll == kCollBgk && mode == 0;
+  if (coll == kCollNone || coll == kCollBgk) return true;
+  // Smagorinsky, BGK with a body force, TRT and the regularised collision: the plain one-role sweep of D3Q19 fp32 -- no
+  // edge launch with packing, no signalling launch.  (Smagorinsky with a force, COLL 7: 168 VGPRs and 84-92 bytes of
+  // scratch per lane under every scheduler setting where the unforced sweep has 168 and none -- not built, the plan
+  // keeps the one-step kernel: DESIGN.md section 4)
+  return (coll == kCollSmagorinsky || coll == (kCollBgk | kCollForce) || coll == kCollTrt || coll == kCollRegularized) &&
+         S::Q == 19 && sizeof(T) == 4 && mode == 0;
 }
 
-// the sweeps of this object
-int sweep(const StepArgs &a, const NameBuf *name) {
-  constexpr int W = kTile.width, R = kTile.rows;
-  if constexpr (R > 0) {
-#if LT_PART_IS(roles)
-    // BGK with separate producer and consumer waves, where they won their A/B (DESIGN.md section 7)
-    if (a.layout == 0) return launch_twice<0, kCollBgk, W, R, 0, 1>(a, name);
-    return launch_twice<1, kCollBgk, W, R, 0, 1>(a, name);
-#elif LT_PART_IS(forced)
-    // with a body force: plain sweeps of periodic plans (no packing, no signalling launch)
-    if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
-    if (a.layout == 0 && a.coll == (kCollBgk | kCollForce)) return launch_twice<0, kCollBgk | kCollForce, W, R>(a, name);
-    if (a.layout == 1 && a.coll == (kCollBgk | kCollForce)) return launch_twice<1, kCollBgk | kCollForce, W, R>(a, name);
-    // (Smagorinsky with a force, COLL 7: 168 VGPRs and 84-92 bytes of scratch per lane under every scheduler setting
-    // where the unforced sweep has 168 and none -- not built, the plan keeps the one-step kernel: DESIGN.md section 4)
-#elif LT_PART_IS(relaxations)
-    // TRT and the regularised collision: plain sweeps of periodic plans (no packing, no signalling launch)
-    if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
-    if (a.layout == 0 && a.coll == kCollTrt) return launch_twice<0, kCollTrt, W, R>(a, name);
-    if (a.layout == 1 && a.coll == kCollTrt) return launch_twice<1, kCollTrt, W, R>(a, name);
-    if (a.layout == 0 && a.coll == kCollRegularized) return launch_twice<0, kCollRegularized, W, R>(a, name);
-    if (a.layout == 1 && a.coll == kCollRegularized) return launch_twice<1, kCollRegularized, W, R>(a, name);
-#else
-    // the unmasked two-step launches of a 3-D unit
-    const int coll = a.coll;
-#if LT_HAS_ROLES
-    // the plain BGK sweep: part roles; shift policy 6 runs the one-role schedule (A/B)
-    if (coll == kCollBgk && a.shift != 6 && (a.layout == 0 || !(a.pack_lo || a.pack_hi || a.signal)))
-      return LT_CAT(roles_, LT_TAG)(a, name);
-#endif
-    if (a.layout == 0 && coll == kCollNone) return launch_twice<0, kCollNone, W, R>(a, name);
-    if (a.layout == 0 && coll == kCollBgk) return launch_twice<0, kCollBgk, W, R>(a, name);
-    if (a.layout == 0 && coll == kCollSmagorinsky) return launch_twice<0, kCollSmagorinsky, W, R>(a, name);
-    // Smagorinsky has the plain sweep only: no edge launch with packing, no signalling launch
-    if (coll == kCollSmagorinsky && (a.pack_lo || a.pack_hi || a.signal)) return kNoKernel;
-    if (a.layout == 1 && (a.pack_lo || a.pack_hi)) {     // slab edge launch with fused halo packing
-      if (coll == kCollNone) return launch_twice<1, kCollNone, W, R, 1>(a, name);
-      if (coll == kCollBgk) return launch_twice<1, kCollBgk, W, R, 1>(a, name);
-    }
-    if (a.layout == 1 && a.signal) {                     // whole slab, edge workgroups first
-      if (coll == kCollNone) return launch_twice<1, kCollNone, W, R, 2>(a, name);
-      if (coll == kCollBgk) return launch_twice<1, kCollBgk, W, R, 2>(a, name);
-    }
-    if (a.layout == 1 && coll == kCollNone) return launch_twice<1, kCollNone, W, R>(a, name);
-    if (a.layout == 1 && coll == kCollBgk) return launch_twice<1, kCollBgk, W, R>(a, name);
-    if (a.layout == 1 && coll == kCollSmagorinsky) return launch_twice<1, kCollSmagorinsky, W, R>(a, name);
-#endif
+// Two fused steps per launch (kernels.hpp, lbm2_kernel): whole periodic grid, no masks.
+// returns kNoKernel when the grid does not tile.
+// one node per thread and per block: the kernel's NPT = NPB = 1
+template <int LAYOUT, int COLL, int T0, int T1, int MODE, int SCHED>
+int launch_twice(const StepArgs &a, const NameBuf *name) {
+  static_assert(sweep_exists(COLL, LAYOUT, MODE, SCHED) && T0 == kTile.width && T1 == kTile.rows, "a sweep of the set above");
+  using B = TwoStep<T, S, T0, T1>;
+  if (name) return kernel_name(*name, "lbm2_kernel", LAYOUT, COLL, T0, T1, 1, MODE, 1, elided(SCHED));
+  if (a.n0 % T0 != 0 || a.n1 % T1 != 0 || a.seg_len < min_segment(false) || a.masked || a.planes < 1 || a.p_stride != 1 ||
+      !plane_addressable(a.n0, a.n1, sizeof(T)))
+    return kNoKernel;
+  if (MODE == 2 && (!a.signal || a.planes2 < 2 || a.planes2 > a.seg_len || a.seg_len < 2)) return kNoKernel;
+  using P = ParamsOf<COLL>;
+  P p = params_of<P>(a, a.n2);
+  // the output planes: [p_begin, p_end) and, at a slab's other edge, [p_begin2, p_end2); a.seg_len of them per workgroup
+  p.p_end = a.p_begin + a.planes;
+  p.p_begin2 = a.p_begin2;
+  p.p_end2 = a.p_begin2 + a.planes2;
+  FamilyOf<COLL>::template fill<LAYOUT>(p, a);
+  p.nb = a.shift == 3 ? 1 : (a.shift == 4 ? 2 : 0);   // A/B: 1 = no XCD-aware renumbering of the workgroups, 2 = per segment layer
+  // MODE 2: the edge workgroups first, each adds 1 to *signal (kernels.hpp, KParams)
+  p.signal = MODE == 2 ? a.signal : nullptr;
+  p.edge_first = MODE == 2 ? 1 : 0;
+  p.ghost_lo = static_cast<const T *>(a.ghost_lo);
+  p.ghost_hi = static_cast<const T *>(a.ghost_hi);
+  p.lo = a.interior_begin; p.hi = a.interior_end;
+  const unsigned grid = (unsigned)((a.n0 / T0) * (a.n1 / T1) * ((a.planes + a.seg_len - 1) / a.seg_len +
+                                                                 (a.planes2 + a.seg_len - 1) / a.seg_len));
+  constexpr int threads = SCHED ? RoleWaves<B::NI, B::NO>::THREADS : (B::NI + 63) / 64 * 64;
+  void (*kern)(const P, const int) = lbm2_kernel<T, S, LAYOUT, COLL, T0, T1, 1, MODE, 1, SCHED>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, a.stream, p, a.seg_len);
+  return (int)hipGetLastError();
+}
+
+// candidate I (layout and mode) of collision C, in this object's schedule
+template <int C, int I>
+bool take_sweep(int wanted, const StepArgs &a, const NameBuf *name, int &result) {
+  constexpr int SCHED = LT_PART_IS(roles) ? 1 : 0;
+  if constexpr (sweep_exists(C, I / 3, I % 3, SCHED)) {
+    if (wanted != I) return false;
+    result = launch_twice<I / 3, C, kTile.width, kTile.rows, I % 3, SCHED>(a, name);
+    return true;
+  } else {
+    return false;
   }
-  return kNoKernel;
+}
+template <int C, int... I>
+bool sweep_of(int wanted, const StepArgs &a, const NameBuf *name, int &result, std::integer_sequence<int, I...>) {
+  return a.coll == C && (take_sweep<C, I>(wanted, a, name, result) || ...);
+}
+
+// the sweep of the list's collisions that the arguments select
+template <int... C>
+int sweep_in(const StepArgs &a, const NameBuf *name) {
+#if LT_PART_IS(forced) || LT_PART_IS(relaxations)
+  // plain sweeps of periodic plans (no packing, no signalling launch)
+  if (a.masked || a.pack_lo || a.pack_hi || a.signal) return kNoKernel;
+#elif LT_PART_IS(sweeps) && LT_HAS_ROLES
+  // the plain BGK sweep: part roles; shift policy 6 runs the one-role schedule (A/B)
+  if (a.coll == kCollBgk && a.shift != 6 && (a.layout == 0 || !(a.pack_lo || a.pack_hi || a.signal)))
+    return LT_CAT(roles_, LT_TAG)(a, name);
+#endif
+  if (a.layout < 0 || a.layout > 1) return kNoKernel;
+  // the slab's edge launch where there is a message buffer, else its signalling launch where there is a signal
+  const int mode = a.layout == 0 ? 0 : ((a.pack_lo || a.pack_hi) ? 1 : (a.signal ? 2 : 0));
+  int result = kNoKernel;
+  (void)(sweep_of<C>(a.layout * 3 + mode, a, name, result, std::make_integer_sequence<int, 6>()) || ...);
+  return result;
 }
 #endif  // LT_SWEEP
 
@@ -627,26 +666,10 @@ int dispatch(const StepArgs &a, const NameBuf *name) {
     return kNoKernel;
 #endif
   }
-  if (a.mode == kStreamOnly) {      // the one kernel that does not collide: no check of the outlet depth
-    LT_TRY(0, kCollNone, kStreamOnly, 0)
-    LT_TRY(0, kCollNone, kStreamOnly, 1)
-#if LT_IS_3D
-    LT_TRY(1, kCollNone, kStreamOnly, 0)
-    LT_TRY(1, kCollNone, kStreamOnly, 1)
-#endif
-    return kNoKernel;
-  }
-  if (coll == kCollNone) return one_step_of<kCollNone>(a, name);
-  if (coll == kCollBgk) return one_step_of<kCollBgk>(a, name);
-#if LT_HAS_KBC
-  if (coll == kCollKbc) return one_step_of<kCollKbc>(a, name);
-#endif
 #if LT_IS_3D
   if (coll == kCollSmagorinsky) return LT_CAT(smag_, LT_TAG)(a, name);       // part smagorinsky
-#else
-  if (coll == kCollSmagorinsky) return one_step_of<kCollSmagorinsky>(a, name);
 #endif
-  return kNoKernel;
+  return one_step_in<LT_COLLS_main>(coll, a, name);
 }
 
 // A scalar observable: `kern` over the plan's fixed grid leaves a partial per workgroup, then one workgroup takes the
@@ -748,80 +771,43 @@ int LT_CAT(aux_, LT_TAG)(const AuxArgs &a) {
   return aux_impl<0>(a);
 }
 #elif LT_PART_IS(sweeps)
-int LT_CAT(twice_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep(a, name); }
+int LT_CAT(twice_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep_in<LT_SWEEPS_sweeps>(a, name); }
 #elif LT_PART_IS(roles)
-int LT_CAT(roles_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep(a, name); }
+int LT_CAT(roles_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return sweep_in<LT_SWEEPS_roles>(a, name); }
 #elif LT_PART_IS(smagorinsky)
-int LT_CAT(smag_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_of<kCollSmagorinsky>(a, name); }
+int LT_CAT(smag_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_smagorinsky>(a.coll, a, name); }
 #elif LT_PART_IS(forced)
 int LT_CAT(forced_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
-  if (a.coll == (kCollBgk | kCollForce)) return one_step_of<kCollBgk | kCollForce>(a, name);
-  if (a.coll == (kCollSmagorinsky | kCollForce)) return one_step_of<kCollSmagorinsky | kCollForce>(a, name);
-  return kNoKernel;
+  if (a.mode == kFusedTwice) return sweep_in<LT_SWEEPS_forced>(a, name);
+  return one_step_in<LT_COLLS_forced>(a.coll, a, name);
 }
 #elif LT_PART_IS(relaxations)
-// one-step kernels and the plain sweep only: no many-step, 2-D or masked two-step launch
 int LT_CAT(relax_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.mode == kFusedTwice) return S::D == 3 ? sweep(a, name) : kNoKernel;
-  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == kCollTrt) return one_step_of<kCollTrt>(a, name);
-  if (a.coll == kCollRegularized) return one_step_of<kCollRegularized>(a, name);
-  return kNoKernel;
+  if (a.mode == kFusedTwice) return sweep_in<LT_SWEEPS_relaxations>(a, name);
+  return one_step_in<LT_COLLS_relaxations>(a.coll, a, name);
 }
 #elif LT_PART_IS(outlets)
-// one-step kernels only: no many-step, 2-D, masked two-step or slab two-step launch takes this boundary
+// the entry point of the outlets parts: its own collisions, else on to the part whose list has a.coll
 int LT_CAT(outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  switch (a.coll) {
-    case kCollNone: return pressure_outlets_of<kCollNone>(a, name);
-    case kCollBgk: return pressure_outlets_of<kCollBgk>(a, name);
-#if LT_HAS_KBC
-    case kCollKbc: return pressure_outlets_of<kCollKbc>(a, name);
-#endif
-    case kCollSmagorinsky: case kCollTrt: case kCollRegularized: return LT_CAT(outlets2_, LT_TAG)(a, name);
-    case kCollBgk | kCollForce: case kCollSmagorinsky | kCollForce: return LT_CAT(outlets3_, LT_TAG)(a, name);
+  if (is_one_of<LT_COLLS_outlets2>(a.coll)) return LT_CAT(outlets2_, LT_TAG)(a, name);
+  if (is_one_of<LT_COLLS_outlets3>(a.coll)) return LT_CAT(outlets3_, LT_TAG)(a, name);
 #if LT_HAS_MRT
-    case kCollMrt: case kCollMrtLallemand: return LT_CAT(mrt_outlets_, LT_TAG)(a, name);
+  if (is_one_of<LT_COLLS_mrt_outlets>(a.coll)) return LT_CAT(mrt_outlets_, LT_TAG)(a, name);
 #endif
-    default: return kNoKernel;
-  }
+  return one_step_in<LT_COLLS_outlets>(a.coll, a, name);
 }
 #elif LT_PART_IS(outlets2)
-int LT_CAT(outlets2_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.coll == kCollSmagorinsky) return pressure_outlets_of<kCollSmagorinsky>(a, name);
-  if (a.coll == kCollTrt) return pressure_outlets_of<kCollTrt>(a, name);
-  if (a.coll == kCollRegularized) return pressure_outlets_of<kCollRegularized>(a, name);
-  return kNoKernel;
-}
+int LT_CAT(outlets2_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_outlets2>(a.coll, a, name); }
 #elif LT_PART_IS(outlets3)
-int LT_CAT(outlets3_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.coll == (kCollBgk | kCollForce)) return pressure_outlets_of<kCollBgk | kCollForce>(a, name);
-  if (a.coll == (kCollSmagorinsky | kCollForce)) return pressure_outlets_of<kCollSmagorinsky | kCollForce>(a, name);
-  return kNoKernel;
-}
+int LT_CAT(outlets3_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_outlets3>(a.coll, a, name); }
+#elif LT_PART_IS(mrt_outlets)
+int LT_CAT(mrt_outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_mrt_outlets>(a.coll, a, name); }
 #elif LT_PART_IS(mrt)
-// one-step kernels only; the transform picks the kernels' COLL (api.hip, kernel_coll)
-int LT_CAT(mrt_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == kCollMrt) return one_step_of<kCollMrt>(a, name);
-#if !LT_IS_3D
-  if (a.coll == kCollMrtLallemand) return one_step_of<kCollMrtLallemand>(a, name);
-#endif
-  return kNoKernel;
-}
+int LT_CAT(mrt_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_mrt>(a.coll, a, name); }
+#elif LT_PART_IS(force_field)
+int LT_CAT(force_field_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_force_field>(a.coll, a, name); }
 #elif LT_PART_IS(incompressible)
-// one-step kernels only; a.coll carries kCollIncompressible (api.hip, kernel_coll)
-int LT_CAT(incompressible_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == (kCollBgk | kCollIncompressible)) return one_step_incompressible_of<kCollBgk | kCollIncompressible>(a, name);
-  if (a.coll == (kCollBgk | kCollForce | kCollIncompressible))
-    return one_step_incompressible_of<kCollBgk | kCollForce | kCollIncompressible>(a, name);
-  if (a.coll == (kCollTrt | kCollIncompressible)) return one_step_incompressible_of<kCollTrt | kCollIncompressible>(a, name);
-  if (a.coll == (kCollRegularized | kCollIncompressible))
-    return one_step_incompressible_of<kCollRegularized | kCollIncompressible>(a, name);
-  return kNoKernel;
-}
+int LT_CAT(incompressible_, LT_TAG)(const StepArgs &a, const NameBuf *name) { return one_step_in<LT_COLLS_incompressible>(a.coll, a, name); }
 
 // lt_equilibrium (kAuxEquilibrium) and lt_init_fneq (kAuxFneq) of a plan with the incompressible equilibrium, reference layout
 int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
@@ -841,15 +827,6 @@ int LT_CAT(incompressible_aux_, LT_TAG)(const AuxArgs &a) {
       return (int)hipGetLastError();
     }
   }
-  return kNoKernel;
-}
-#elif LT_PART_IS(force_field)
-// one-step kernels only; a.coll carries kCollField (api.hip, kernel_coll)
-int LT_CAT(force_field_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.mode != kFused && a.mode != kCollideOnly) return kNoKernel;
-  if (a.coll == (kCollBgk | kCollForce | kCollField)) return one_step_field_of<kCollBgk | kCollForce | kCollField>(a, name);
-  if (a.coll == (kCollSmagorinsky | kCollForce | kCollField))
-    return one_step_field_of<kCollSmagorinsky | kCollForce | kCollField>(a, name);
   return kNoKernel;
 }
 #elif LT_PART_IS(spectrum)
@@ -894,14 +871,6 @@ int LT_CAT(links_, LT_TAG)(const LinkArgs &a) {
   hipLaunchKernelGGL((finish_components_kernel<T, S::D>), dim3(1), dim3(kLinkThreads), 0, a.stream, a.partial, a.blocks,
                      a.out);
   return (int)hipGetLastError();
-}
-#elif LT_PART_IS(mrt_outlets)
-int LT_CAT(mrt_outlets_, LT_TAG)(const StepArgs &a, const NameBuf *name) {
-  if (a.coll == kCollMrt) return pressure_outlets_of<kCollMrt>(a, name);
-#if !LT_IS_3D
-  if (a.coll == kCollMrtLallemand) return pressure_outlets_of<kCollMrtLallemand>(a, name);
-#endif
-  return kNoKernel;
 }
 #endif
 

@@ -23,7 +23,7 @@ struct KParamsF {            // what collide_forced reads
 
 template <typename T, class S, int EQ>
 void collide(const char *op, T (&g)[S::Q][1], double tau, double tau_minus, double ax, double rho0_) {
-  // the scalars as params_of, set_force and launch (unit.inc) form them
+  // the scalars as params_of and the families' fill (unit.inc) form them
   const T rho0 = (T)rho0_;
   if (!strcmp(op, "trt")) {
     lt::collide_trt<T, S, 0, 1, 0, EQ>(g, (T)(1. / (2 * tau)), (T)(1.0 / (2.0 * tau_minus)), rho0);

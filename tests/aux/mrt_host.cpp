@@ -17,7 +17,7 @@ int run(const char *in, const char *out, long n, char **rates) {
   FILE *fp = fopen(in, "rb");
   if (!fp || fread(f.data(), sizeof(T), f.size(), fp) != f.size()) return 2;
   fclose(fp);
-  // r_i as set_mrt (unit.inc) forms them: the rate rounded to T, the reciprocal in T
+  // r_i as Mrt::fill (unit.inc) forms them: the rate rounded to T, the reciprocal in T
   T r[lt::kMrtMaxQ] = {};
   for (int i = 0; i < S::Q; ++i) r[i] = T(1) / (T)atof(rates[i]);
   for (long i = 0; i < n; ++i) {

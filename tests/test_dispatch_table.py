@@ -1,9 +1,9 @@
 """Which kernel a unit picks for which arguments is behaviour: bench.py, the profiling tools and the tests match on
 the names, and a refactoring of csrc/unit.inc must not move a plan to another kernel.  tests/aux/dispatch_table.cpp
-asks every unit's name function (nothing launches) for every combination of the arguments that path reads -- 388 800
+asks every unit's name function (nothing launches) for every combination of the arguments that path reads -- 451 584
 selectors per unit -- and prints, per unit, the distinct names, the number of selectors with a kernel and a hash over
-the whole ordered table; tests/dispatch_table.txt is that output of the library before the launchers and ladders of
-unit.inc were folded (made with a variant of the program for the name function's earlier signature)."""
+the whole ordered table; tests/dispatch_table.txt is that output of the library as it was before the ladders of
+unit.inc became one walk over a stated set (the program linked against a library built from that commit's csrc/)."""
 import os
 import shutil
 import subprocess
