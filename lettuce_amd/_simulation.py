@@ -19,6 +19,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from ._kept import KeptState, _version
 from .util import LettuceException, NativeEngineError
 
 __all__ = ["Collision", "Reporter", "Simulation"]
@@ -74,18 +75,13 @@ def build_masks(flow, boundaries, context):
     return ncm, nsm
 
 
-def _version(t: Optional[torch.Tensor]):
-    return None if t is None else (id(t), t.data_ptr(), t._version, tuple(t.shape))
-
-
 class _NativeStepper:
     """Owns the engine plan of one Simulation and advances it in batches.
 
-    A batch of k steps is ``lt_run``: one collide launch, k-1 fused stream-collide launches
-    and one stream launch, so that ``flow.f`` again holds post-streaming populations (the
-    reference's state convention) whenever Python can look at it.  If nothing touched
-    ``flow.f`` between two batches the engine carries on from the post-collision buffer
-    (``lt_continue``) and saves the collide pass.
+    A batch of k steps is ``lt_run``: one collide launch, k-1 fused stream-collide launches and one stream launch, so
+    that ``flow.f`` holds post-streaming populations (the reference's state convention) whenever Python looks at it.
+    What a batch leaves behind -- the pass it owes, the post-collision buffer the next batch may carry on from
+    (``lt_continue``, saving the collide pass) and what must be untouched for that -- is ``self.kept`` (_kept.KeptState).
     """
 
     def __init__(self, sim: "Simulation"):
@@ -142,8 +138,7 @@ class _NativeStepper:
         self._link_bodies = [(i, sim.boundaries[i + 1]) for i, b in enumerate(self.boundaries)
                              if b.kind == "link_bounce_back"]
         self._mask_state = None
-        self._carry = None      # state that allows lt_continue
-        self._lazy = None       # (f*, scratch, versions) while flow.f is one streaming pass short
+        self.kept = KeptState()     # what the last batch left for the next one (lt_continue) and for whoever looks
         # optional (start, end) torch.cuda.Event pair: when set, lt_run / lt_continue record them on
         # the launch stream around the fused launches of a batch (lt_plan_set_fused_events;
         # bench.py times the dominant kernel live with them, plan.last_run_info() says what they bracket)
@@ -185,7 +180,7 @@ class _NativeStepper:
             for i, links in lists:
                 self.plan.set_links(i, *links)
         self._mask_state = state
-        self._carry = None
+        self.kept.invalidate()
 
     def _sync_boundaries(self):
         entries = [b.plan_entry(self.sim.flow) for b in self.boundaries]
@@ -194,7 +189,7 @@ class _NativeStepper:
                           or (not isinstance(v, torch.Tensor) and v != old[k]) for k, v in new.items())
             if changed:
                 self.plan.update_boundary(i, new)
-                self._carry = None
+                self.kept.invalidate()
         self._entries = entries
 
     # ---- stepping ----------------------------------------------------------------------------
@@ -213,112 +208,74 @@ class _NativeStepper:
         return f, nxt
 
     def batch(self, k: int):
-        """Advance ``k`` whole steps.  The engine stops one streaming pass short (``lt_plan_set_deferred_stream``):
-        the post-collision populations of the last step stay in one buffer, and ``flow.f`` completes the pass
-        when it is read (Flow.f) -- a caller that steps in batches without looking in between (reporters every
-        k steps, benchmark loops) pays k fused launches per batch and nothing else."""
-        flow = self.sim.flow
+        """Advance ``k`` whole steps.  The engine stops one streaming pass short (``lt_plan_set_deferred_stream``) and
+        ``flow.f`` completes the pass when it is read (Flow.f): a caller that steps in batches without looking in
+        between (reporters every k steps, benchmark loops) pays k fused launches per batch and nothing else."""
+        flow, plan, kept = self.sim.flow, self.plan, self.kept
         self._sync_masks()
         self._sync_boundaries()
         tau = float(self.collision.tau(flow))
         # the collision's settings (Smagorinsky's constant, tau_minus, MRT's rates, a body force) are re-read per batch
         # like tau and handed to the plan (no new plan)
         settings = self.collision.settings(flow)
-        settings.apply(self.plan)
+        settings.apply(plan)
         # the flow's equilibrium: kind and rho0 are re-read per batch too
         equilibrium = flow._stepper_equilibrium()
         if equilibrium is None:
             raise NativeEngineError(f"the HIP engine has no kernel for equilibrium '{type(flow.equilibrium).__name__}'")
-        self.plan.set_equilibrium(*equilibrium)
+        plan.set_equilibrium(*equilibrium)
         # what a batch must share with the one before it to carry on from its state: a change starts from flow.f
         key = (tau, settings, equilibrium)
-        if self.plan.resident_enabled()[0]:
+        if plan.resident_enabled()[0]:
             try:
-                return self._batch_resident(k, tau, key)
+                return self._batch_resident(k, tau, key + (KeptState.ENGINE,))   # the launch path is part of the key
             except NativeEngineError as exc:
                 # the engine's own padded buffers could not be allocated (two more population fields, raw
                 # hipMalloc; torch's cache was emptied and the allocation tried again).  "Automatic" then carries on
                 # with the caller's dense tensors; a plan on which resident populations were REQUESTED keeps the error
-                if getattr(exc, "code", None) != 4 or self.plan.resident_mode == 1:
+                if getattr(exc, "code", None) != 4 or plan.resident_mode == 1:
                     raise
                 warnings.warn(f"resident populations unavailable ({exc}); stepping on flow.f / flow.f_next", stacklevel=3)
-                self.plan.set_resident(0)
-                self._carry = None
-        changed = self._carry is None                         # first batch, or masks / boundaries were replaced
-        pending = flow._pending is not None and self._lazy is not None
-        if pending:
-            fstar, scratch, token = self._lazy
-            pending = token == (_version(fstar), _version(scratch), key) and self._carry == "lazy"
-        if pending:
-            a, b, from_fstar = fstar, scratch, True
-        else:
+                plan.set_resident(0)
+                kept.invalidate()
+        start = kept.resume(key)                              # nobody looked: (f*, scratch) of the batch before
+        if start is None:
             f, nxt = self._state_buffers()                    # reading flow.f completes a pending batch
-            carry = not changed and self._carry == (_version(f), _version(nxt), key)
-            a, b, from_fstar = (nxt, f, True) if carry else (f, nxt, False)
+            start = kept.resume(key, (f, nxt))                # what was shown is untouched: f* is still in flow.f_next
         if self.fused_events is not None:
-            self.plan.set_fused_events(*self.fused_events)    # recorded by lt_run around its fused launches
-        self.plan.set_deferred_stream(True)
+            plan.set_fused_events(*self.fused_events)         # recorded by lt_run around its fused launches
+        plan.set_deferred_stream(True)
         try:
-            fstar, scratch = self.plan.run(a, b, tau, k, from_fstar=from_fstar)
+            fstar, scratch = plan.run(*(start or (f, nxt)), tau, k, from_fstar=start is not None)
         finally:
-            self.plan.set_deferred_stream(False)
+            plan.set_deferred_stream(False)
             if self.fused_events is not None:
-                self.plan.set_fused_events(None, None)
-        self._lazy = (fstar, scratch, (_version(fstar), _version(scratch), key))
-        self._carry = "lazy"
-        flow._f, flow._f_next = None, None                    # nobody may see the buffers until the pass is done
-
-        def finish():
-            result = self.plan.stream(fstar, scratch)
-            self._lazy = None
-            self._carry = (_version(result), _version(fstar), key)
-            return result, fstar
-
-        def drop():                                           # flow.f was assigned while the pass was pending
-            self._lazy = None
-            self._carry = None
-        finish.drop = drop
-        flow._pending = finish
+                plan.set_fused_events(None, None)
+        kept.defer((fstar, scratch), key, lambda: (plan.stream(fstar, scratch), fstar))
+        flow._pending, flow._f, flow._f_next = kept, None, None    # nobody may see the buffers until the pass is done
 
     def _batch_resident(self, k: int, tau: float, key):
         """The same batch with the post-collision populations in the ENGINE's padded ping-pong buffers
         (``lt_resident_*``): ``flow.f`` / ``flow.f_next`` stay the reference's plain ``[q, *res]`` tensors
-        (lettuce/_flow.py:90,124-134) and are written only by the pass that presents the populations when somebody
-        looks.  k steps from ``flow.f`` are load (collide) + k - 1 fused steps; a batch that carries on -- nobody
-        looked, or what was shown has not been touched since -- is k fused steps."""
-        flow, plan = self.sim.flow, self.plan
+        (lettuce/_flow.py:90,124-134), written only by the pass that presents the populations when somebody looks.
+        k steps from ``flow.f`` are load (collide) + k - 1 fused steps; a batch that carries on is k fused steps."""
+        flow, plan, kept = self.sim.flow, self.plan, self.kept
         if self.fused_events is not None:
             plan.set_fused_events(*self.fused_events)
         try:
-            if flow._pending is not None and self._carry == ("resident-pending", key):
-                plan.resident_advance(tau, k)
-            else:
+            complete = kept.completion                        # nobody looked: the pass goes where it was to go
+            if kept.resume(key) is None:
                 f, nxt = self._state_buffers()                # reading flow.f completes a pending batch
-                if self._carry == ("resident", _version(f), key):
-                    plan.resident_advance(tau, k)             # what was shown is still what the engine holds
-                else:
+                if kept.resume(key, (f,)) is None:            # else what was shown is still what the engine holds
                     plan.resident_load(f, tau)
-                    plan.resident_advance(tau, k - 1)
-                self._lazy = (f, nxt, None)                   # the two dense buffers of the flow
+                    k -= 1
+                complete = lambda: (plan.resident_store(nxt), f)    # noqa: E731  (the buffer shown last keeps its content)
+            plan.resident_advance(tau, k)
         finally:
             if self.fused_events is not None:
                 plan.set_fused_events(None, None)
-        self._carry = ("resident-pending", key)
-        flow._f, flow._f_next = None, None                    # nobody may see the buffers until the pass is done
-
-        def finish():
-            f, nxt, _ = self._lazy
-            result = plan.resident_store(nxt)                 # the buffer shown last keeps its content
-            self._lazy = None
-            self._carry = ("resident", _version(result), key)
-            return result, f
-
-        def drop():                                           # flow.f was assigned while the pass was pending
-            self._lazy = None
-            self._carry = None
-            plan.resident_free()                              # the state they held is void: give the two fields back
-        finish.drop = drop
-        flow._pending = finish
+        kept.defer(kept.ENGINE, key, complete, release=plan.resident_free)    # flow.f assigned meanwhile voids the two fields
+        flow._pending, flow._f, flow._f_next = kept, None, None    # nobody may see the buffers until the pass is done
 
     def single_step(self, *_, **__):
         self.batch(1)

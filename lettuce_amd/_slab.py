@@ -46,6 +46,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from ._kept import KeptState, Phase
 from .util import LettuceException
 
 __all__ = ["ZSlab", "SlabSimulation", "TwoStepSlabSimulation", "SlabKineticEnergy", "SlabEnstrophy", "SlabMass"]
@@ -496,6 +497,7 @@ class SlabSimulation:
         if slab.halo < self.GHOST:
             raise LettuceException(f"ZSlab.halo = {slab.halo} planes, the driver needs {self.GHOST} ghost planes")
         self.flow, self.collision, self.slab = flow, collision, slab
+        self._kept = KeptState()
         self.context = flow.context
         self.reporter = reporter if reporter is not None else []
         for r in self.reporter:
@@ -625,61 +627,49 @@ class SlabSimulation:
         return self._halo.host
 
     # ---- the populations -------------------------------------------------------------------------
-    # ``f`` holds post-streaming populations (lettuce's convention) whenever somebody looks; between batches
-    # the driver keeps the post-collision populations of the last step (ghost planes exchanged) and carries on
-    # from them, and the streaming pass that presents ``f`` runs when ``f`` / ``f_next`` are read (local_f,
-    # gather_f, the observables).  A batch that nobody looks at costs its fused steps only.
-    _pending = None          # (f*, scratch) while ``f`` is one streaming pass short
-    _carry = None            # version of ``_f`` when ``_f_next`` held the f* it was streamed from
-    _f = None
-    _f_next = None
-
+    # ``f`` holds post-streaming populations (lettuce's convention) whenever somebody looks (local_f, gather_f, the
+    # observables); between batches the driver keeps the post-collision populations of the last step, ghost planes
+    # exchanged: ``_kept``, the record ``Simulation``'s stepper keeps too (_kept.KeptState), here without a key.
     @property
     def f(self) -> torch.Tensor:
-        if self._pending is not None:
-            self._present()
+        self._present()
         return self._f
 
     @f.setter
     def f(self, value):
-        self._pending, self._carry = None, None
+        self._kept.drop()
         self._f = value
 
     @property
     def f_next(self) -> torch.Tensor:
-        if self._pending is not None:
-            self._present()
+        self._present()
         return self._f_next
 
     @f_next.setter
     def f_next(self, value):
-        if self._pending is not None:
-            self._present()
-        self._carry = None
+        self._present()
+        self._kept.drop()                             # f* lived in the buffer that is replaced
         self._f_next = value
 
     def _present(self):
-        from ._simulation import _version
-        (cur, nxt), self._pending = self._pending, None
-        self.engine.stream_planes(cur, nxt, self.lo, self.hi)
-        self._f, self._f_next = nxt, cur
-        self._carry = (_version(nxt), _version(cur))      # both buffers: f* lives in the second one
+        if self._kept.phase is Phase.PENDING:
+            self._f, self._f_next = self._kept.present()
+
+    def _defer(self, cur, nxt, first=lambda buf: None):
+        """the batch ended one pass short: ``cur`` is streamed into ``nxt`` when somebody looks, behind ``first(cur)``"""
+        def complete():
+            first(cur)
+            self.engine.stream_planes(cur, nxt, self.lo, self.hi)
+            return nxt, cur
+        self._kept.defer((cur, nxt), None, complete)
 
     def _start_batch(self, tau):
         """(f*, scratch, fused steps already owed): the post-collision populations to carry on from -- kept from
         the batch before, or one collide pass + exchange away from ``f``"""
-        # Unlike the single-GPU stepper, whose carry key holds tau and the collision's settings, the slab drivers carry
-        # on from the kept post-collision populations even when tau or a setting changed between two batches: the last
-        # collide of the batch before then ran with the earlier values.
-        from ._simulation import _version
-        if self._pending is not None:
-            (cur, nxt), self._pending = self._pending, None
-            return cur, nxt, True
-        if self._carry is not None and self._carry == (_version(self._f), _version(self._f_next)):
-            self._carry = None
-            return self._f_next, self._f, True
-        self._carry = None
-        cur, nxt = self._f, self._f_next
+        start = self._kept.resume(None, (self._f, self._f_next))
+        if start is not None:
+            return (*start, True)
+        cur, nxt = self.f, self.f_next
         self.engine.collide_planes(cur, nxt, tau, self.lo, self.hi)
         self._exchange(nxt)()
         return nxt, cur, False
@@ -795,7 +785,7 @@ class SlabSimulation:
         for _ in range(n if carried else n - 1):
             self._fused_step(cur, nxt, tau)
             cur, nxt = nxt, cur
-        self._pending = (cur, nxt)                    # streamed when somebody looks (``f``)
+        self._defer(cur, nxt)                         # streamed when somebody looks (``f``)
 
     def _next_report(self, limit):
         k = limit
@@ -1056,11 +1046,6 @@ class TwoStepSlabSimulation(SlabSimulation):
         if self._ghost_src is not None:
             self._unpack_messages(buf, *self._ghost_src)
 
-    def _present(self):
-        if self._pending is not None:
-            self._field_ghosts(self._pending[0])
-        super()._present()
-
     def _double_step_direct(self, cur, nxt, tau):
         eng, lo, hi, edge, halo = self.engine, self.lo, self.hi, self.edge_planes, self._halo
         send_down, send_up = halo.targets()
@@ -1186,7 +1171,7 @@ class TwoStepSlabSimulation(SlabSimulation):
             eng.stream_collide_planes(cur, nxt, tau, lo, hi)
             cur, nxt = nxt, cur
             self._exchange(cur)()
-        self._pending = (cur, nxt)                    # streamed when somebody looks (``f``)
+        self._defer(cur, nxt, first=self._field_ghosts)     # streamed when somebody looks, behind the scatter
         if signalled_steps and self._signalled_ok() and eng.wait_timed_out():
             # the polling wave gave up before the edge workgroups reported (it waits about a second): the
             # exchange that followed sent planes that were not written yet

@@ -77,7 +77,7 @@ class FieldRef:
 @dataclass(frozen=True)
 class CollisionSettings:
     """The values a collision hands to a plan before a launch, read now: what ``Plan.set_*`` take, nothing late-bound.
-    Hashable and compared by value: part of the steppers' carry key.  ``tau`` is not among them: it is a launch argument
+    Hashable and compared by value: part of the steppers' carry key (``_kept.KeptState.key``).  ``tau`` is not among them: it is a launch argument
     of the engine, and KBC and the regularised collision fix theirs at the first read."""
     smagorinsky: Optional[float] = None        # the constant
     tau_minus: Optional[float] = None          # TRT

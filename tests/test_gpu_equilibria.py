@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import lettuce_amd as lt
+from lettuce_amd._kept import Phase
 from conftest import golden, TORCH_DT
 from test_gpu_engine import ATOL, dev
 from test_gpu_paths_vs_oracle import perturbed_state
@@ -186,8 +187,8 @@ def test_a_change_of_rho0_between_two_batches_restarts_from_flow_f(dt):
         sim = lt.Simulation(flow, lt.BGKCollision(float(g["tau"])), [])
         sim(3)
         if context.use_native:
-            carry = sim._native._carry
-            assert carry is not None
+            kept = sim._native.kept                   # something is kept that the next batch could carry on from
+            assert kept.phase is Phase.PENDING and kept.valid and kept.resume(kept.key) is not None
         flow.equilibrium.rho0 = 1.0
         sim(2)
         flows.append(flow)
